@@ -12,6 +12,11 @@ Weights: seeded random init of the ViT-B/16 architecture (no checkpoints offline
 
 Contract: `python bench.py --gpus N --steps K --warmup W`; for N > 1 launched by
 torch.distributed.run, one rank per GPU (RCCL).  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times the K steps and prints the line (with what those K steps' own timers
+give: roofline, per-kernel milliseconds, clock, power).  `--full` adds everything else the line can carry:
+the other dataflows re-timed, the CPU baselines and parity, and the secondary rates.
+`--dump-outputs DIR` writes the last timed step's features as DIR/features.npy (same arguments = same inputs:
+seeded slide, seeded weights).
 """
 from __future__ import annotations
 
@@ -137,15 +142,41 @@ def parse_args():
     ap.add_argument("--dump-features", default=None,
                     help="rank 0 saves the float32 feature matrix of the timed steps (the gathered [N*K*B, D] matrix for N > 1) "
                          "as .npy -- used by the N > 1 rehearsal test")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step returned as DIR/<name>.npy (float32, 64 MB at most: a seeded "
+                         "row sample beyond that): features = the step's [B, D] feature block; for N > 1 every rank's "
+                         "last-step block of the assembled matrix, in rank order [N*B, D]")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: warm coords repeats, the other dataflows of the same encoder "
+                         "(full last block, f32 stream, plain 16-bit stream), the CPU baselines and parity, and (vit_b_16) the "
+                         "secondary rates; without it a run sets up, warms up, times the steps and prints the line")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary rates (ring / end-to-end / boundary / f32 / uni_v1 / conch_v1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: skip the secondary rates (ring / end-to-end / boundary / f32 / uni_v1 / conch_v1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-sample", type=int, default=0,
-                    help="patches timed on the CPU oracle (default: 192 vit_b_16, 64 uni_v1, 32 conch_v1 = 10-20 s)")
+                    help="with --full: patches timed on the CPU oracle (default: 192 vit_b_16, 64 uni_v1, 32 conch_v1 = 10-20 s)")
     return ap.parse_args()
 
 
-def slide_tiles(device, side, seed, count):
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy in float32.  Over the 64 MB budget (shared in proportion to size) an
+    array keeps a fixed, seeded sample of its rows, in row order, so two builds given the same arguments write the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.size * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if total > DUMP_BUDGET_BYTES and a.shape[0] > 1:
+            row_bytes = a.nbytes // a.shape[0]
+            keep = max(1, int(DUMP_BUDGET_BYTES * (a.nbytes / total)) // row_bytes)
+            if keep < a.shape[0]:
+                a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def slide_tiles(device, side, seed, count, warm_repeats=10):
     """Device coords path + on-device tile synthesis -> uint8 [count, 256, 256, 3] in HBM."""
     import ctypes as C
     from atlaspatch_amd import _lib
@@ -160,13 +191,15 @@ def slide_tiles(device, side, seed, count):
     coords, geom = coords_from_mask(mask, **kw)             # cold: first use of the kernels + allocations in this process
     cold_s = time.perf_counter() - t0
     warm = []
-    for _ in range(10):                                     # warm, repeated: what every later slide of a run pays
+    for _ in range(warm_repeats):                           # warm, repeated: what every later slide of a run pays
         t0 = time.perf_counter()
         again, _ = coords_from_mask(mask, **kw)
         warm.append(time.perf_counter() - t0)
-    assert np.array_equal(again, coords)
-    coords_stats = {"cold_seconds": round(cold_s, 5), "warm_seconds_median": round(float(np.median(warm)), 5),
-                    "warm_seconds_min": round(min(warm), 5), "warm_repeats": len(warm)}
+    coords_stats = {"cold_seconds": round(cold_s, 5)}
+    if warm:
+        assert np.array_equal(again, coords)
+        coords_stats.update({"warm_seconds_median": round(float(np.median(warm)), 5),
+                             "warm_seconds_min": round(min(warm), 5), "warm_repeats": len(warm)})
     cells = int(math.ceil(side / 256) ** 2)
     n_slide = coords.shape[0]
     reps = int(math.ceil(count / max(1, n_slide)))
@@ -724,7 +757,8 @@ def main():
                                  expect_size=None, mean=enc.get("mean"), std=enc.get("std"))
     B, K, W = args.batch, args.steps, args.warmup
     pool_steps = min(K, 12)                       # distinct tile batches cycled through the timed steps
-    tiles, n_slide, cells, coords_stats, dev_coords = slide_tiles(device, args.slide, args.slide_seed + rank, pool_steps * B)
+    tiles, n_slide, cells, coords_stats, dev_coords = slide_tiles(device, args.slide, args.slide_seed + rank, pool_steps * B,
+                                                                  warm_repeats=10 if args.full else 0)
     feats = torch.empty((K * B, ex.embedding_dim), dtype=torch.float32, device=device)
 
     def step(i, dst):
@@ -792,16 +826,20 @@ def main():
                 "all_gather_ms": round(ev[1].elapsed_time(ev[2]), 3)}
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
-    if args.dump_features and rank == 0:
+    if (args.dump_features or args.dump_outputs) and rank == 0:
         whole = feats if dist is None else (torch.cat(assembled, 0) if isinstance(assembled, list) else assembled)
-        np.save(args.dump_features, whole.cpu().numpy())
+        if args.dump_features:
+            np.save(args.dump_features, whole.cpu().numpy())
+        if args.dump_outputs:                  # rank r's block of the assembled matrix is rows [r*K*B, (r+1)*K*B)
+            last = torch.cat([whole[(r * K + K - 1) * B:(r * K + K) * B] for r in range(world)], 0)
+            dump_outputs(args.dump_outputs, {"features": last.cpu().numpy()})
 
-    # Secondary, untimed-for-`value` measurement: the same K steps with the last block computed for every token
+    # Secondary, untimed-for-`value` measurement (--full): the same K steps with the last block computed for every token
     # (option full_last_block), so the line shows what the CLS-only tail is worth.
     full_value = None
     full_last = bool(os.environ.get("AP_VIT_FULL_LAST_BLOCK"))      # the default the encoder object was created with
     cls_tail_possible = geo["executed"] != geo["model"]
-    if world == 1 and not full_last and cls_tail_possible:
+    if args.full and world == 1 and not full_last and cls_tail_possible:
         ex.vit.set_option("full_last_block", True)
         try:
             step(0, feats[:B])
@@ -817,7 +855,7 @@ def main():
     # ... and with the float32 residual stream + standalone add+LayerNorm launches (round 1's dataflow, option f32_stream)
     f32s = None
     fused = short != "f32" and not os.environ.get("AP_VIT_F32_STREAM")
-    if world == 1 and fused:
+    if args.full and world == 1 and fused:
         ex.vit.set_option("f32_stream", True)
         try:
             step(0, feats[:B])
@@ -837,7 +875,7 @@ def main():
     # ... and without the class rows' float32 side stream (option exact_cls off: the plain 16-bit stream of rounds 2-3)
     plain16 = None
     exact_cls_on = fused and not os.environ.get("AP_VIT_NO_EXACT_CLS") and arch.get("pool", "cls") in ("cls", "cls_mean")
-    if world == 1 and exact_cls_on:
+    if args.full and world == 1 and exact_cls_on:
         ex.vit.set_option("exact_cls", False)
         try:
             step(0, feats[:B])
@@ -930,7 +968,7 @@ def main():
                    "encoder": args.encoder,
                    "tiles_per_step": B, "slide_tissue_tiles": int(n_slide), "grid_cells": cells,
                    "parallelism": f"slide-per-rank x{world}" + (" + RCCL all-gather of features" if world > 1 else ""),
-                   "gpus_requested": args.gpus, "ranks_in_process_group": world},
+                   "gpus_requested": args.gpus, "ranks_in_process_group": world, "full": args.full},
         "roofline": {"bound": "mfma", "kernel": ((f"gemm256_kernel<T,EPI_NORM_GELU> (fc1 with the LayerNorm statistics applied "
                                                           f"in the epilogue: {shape}, " if fused else
                                                           f"gemm256_kernel<T,EPI_BIAS_GELU> (fc1: {shape}, ") +
@@ -969,9 +1007,11 @@ def main():
         "f32_stream_dataflow": f32s,
         "kernel_ms_per_step": kernel_ms, "hbm_kernels": hbm_kernels,
         "coords": {"cells": cells, "rows": int(n_slide), **coords_stats,
-                   "cells_per_s": round(cells / coords_stats["warm_seconds_median"], 1),
-                   "what": "mask -> contours -> grid scan -> rows on the host, one slide; warm = median of 10 repeats after the "
-                           "first (cold) call"},
+                   **({"cells_per_s": round(cells / coords_stats["warm_seconds_median"], 1),
+                       "what": "mask -> contours -> grid scan -> rows on the host, one slide; warm = median of 10 repeats after "
+                               "the first (cold) call"} if "warm_seconds_median" in coords_stats else
+                      {"what": "mask -> contours -> grid scan -> rows on the host, one slide, first (cold) call; the warm "
+                               "repeats run with --full"})},
     }
     if per_rank is not None:
         line["per_rank"] = per_rank
@@ -980,7 +1020,7 @@ def main():
                               "what": ("one all_gather_into_tensor of every rank's float32 [K*B, D] block" if gather_algo != "pairs" else
                                        "all-pairs batch_isend_irecv of every rank's float32 [K*B, D] block (ATLASPATCH_GATHER_ALGO=pairs)")
                                       + ", inside the timed region"}
-    if not args.no_cpu_baseline and world == 1:          # the CPU leg runs at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:          # the CPU leg runs at N = 1 only
         sample = args.cpu_sample if args.cpu_sample else {"vit_b_16": 192, "uni_v1": 64, "conch_v1": 32, "vit_b_32": 256,
                                                           "vit_l_32": 128, "vit_h_14": 4, "uni_v2": 24}[args.encoder]
         out_cpu, patches, cpu_rate, cpu_threads = cpu_baseline(args.encoder, sample, seed=0)
@@ -1027,7 +1067,7 @@ def main():
                                           "cores": 1, "kind": "port",
                                           "sample": "the bench slide's mask through oracle/coords_oracle.py (NumPy)",
                                           "rows_equal_device_path": bool(np.array_equal(np.asarray(cpu_coords), np.asarray(dev_coords)))}
-    if not args.no_extras and world == 1 and args.encoder == "vit_b_16":
+    if args.full and not args.no_extras and world == 1 and args.encoder == "vit_b_16":
         line["rates"] = {"kernel_only": {"patches_per_s": round(value, 1), "what": "= value"}}
         line["rates"].update(secondary_rates(device, ex, tiles, B))
         seg = line["rates"].get("sam2_segmentation")

@@ -102,8 +102,8 @@ def test_a_line_is_refused_when_the_ranks_that_ran_are_not_the_gpus_asked_for():
 @pytest.mark.gpu
 def test_encoder_option_runs_conch_fp16_with_its_own_roofline_shape():
     """Config 5's encoder (CONCH v1 visual tower, fp16, 785 tokens) has a bench line of its own."""
-    line = _run(["--encoder", "conch_v1", "--steps", "2", "--warmup", "1", "--batch", "32", "--slide", "12000", "--no-extras",
-                 "--cpu-sample", "4"])
+    line = _run(["--encoder", "conch_v1", "--steps", "2", "--warmup", "1", "--batch", "32", "--slide", "12000", "--full",
+                 "--no-extras", "--cpu-sample", "4"])
     assert line["config"]["encoder"] == "conch_v1" and "conch_v1" in line["metric"] and line["dtype"] == "f16"
     assert "[B*785,768]x[768,3072]" in line["roofline"]["kernel"]
     assert line["roofline"]["algorithmic_flop_per_launch"] == 2.0 * 32 * 785 * 3072 * 768
