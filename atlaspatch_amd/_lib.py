@@ -47,6 +47,18 @@ class VitConfig(C.Structure):
         super().__init__(C.sizeof(type(self)), *args, **kw)
 
 
+class ResnetConfig(C.Structure):
+    """``ap_resnet_config`` (additive to ABI v20); ``struct_size`` is filled in here."""
+    _fields_ = [("struct_size", C.c_uint32), ("block", C.c_int), ("depths", C.c_int * 4), ("stem_width", C.c_int),
+                ("compute_dtype", C.c_int), ("image_size", C.c_int)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(C.sizeof(type(self)), *args, **kw)
+
+
+RESNET_PROF_KINDS = ("stem", "conv1x1", "conv3x3", "pool")
+
+
 # name -> (restype, argtypes); every symbol include/atlaspatch_hip.h declares
 SIGNATURES = {
     "ap_abi_version": (C.c_int, []),
@@ -86,6 +98,22 @@ SIGNATURES = {
                                     C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ap_vit_forward_chw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p]),
+    "ap_sizeof_resnet_config": (C.c_size_t, []),
+    "ap_resnet_config_init": (C.c_int, [C.POINTER(ResnetConfig), C.c_size_t]),
+    "ap_resnet_create": (C.c_int, [C.POINTER(ResnetConfig), C.POINTER(C.c_void_p)]),
+    "ap_resnet_destroy": (None, [C.c_void_p]),
+    "ap_resnet_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]),
+    "ap_resnet_finalize": (C.c_int, [C.c_void_p]),
+    "ap_resnet_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "ap_resnet_embed_dim": (C.c_int, [C.c_void_p]),
+    "ap_resnet_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "ap_resnet_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_int]),
+    "ap_resnet_forward_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                       C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ap_conv2d_nhwc": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                 C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "ap_maxpool3x3s2_nhwc": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ap_avgpool_nhwc": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ap_gemm": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ap_gemm_fused": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

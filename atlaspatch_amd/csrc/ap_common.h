@@ -262,6 +262,14 @@ int launch_sattention(const float* q, long ldq, const float* k, long ldk, const 
                       int tk, int d, float scale, float* out, long ldo, hipStream_t stream, bool exact);
 
 // content statistics (content.hip): counts [n, 2] = (#gray < black_thresh, #(S < sat_thresh && V >= value_thresh))
+// conv.hip: the ResNet family's kernels (NHWC activations in the compute type)
+int launch_conv2d_nhwc(int dtype, const void* x, int n, int h, int w, int cin, const void* weight, const float* bias, int cout,
+                       int ksize, int stride, int pad, const void* resid, int relu, void* out, hipStream_t stream);
+int launch_preproc_nhwc8(const uint8_t* src, int n, int h, int w, int top, int left, int S, const float mean[3],
+                         const float stdv[3], void* dst, int dtype, hipStream_t stream);
+int launch_maxpool3x3s2_nhwc(int dtype, const void* x, int n, int h, int w, int c, void* out, hipStream_t stream);
+int launch_avgpool_nhwc(int dtype, const void* x, int n, int hw, int c, float* out, hipStream_t stream);
+
 int tile_content_counts(const uint8_t* tiles, int n, int h, int w, int black_thresh, int sat_thresh,
                         int value_thresh, unsigned* counts, hipStream_t stream);
 

@@ -5,14 +5,15 @@ import torch
 
 from .base import FeatureExtractor, HipViTFeatureExtractor, PatchFeatureExtractor
 from .custom import (CustomEncoderComponents, CustomEncoderLoader, register_custom_encoder,
-                     register_feature_extractors_from_module, register_hip_vit_encoder)
+                     register_feature_extractors_from_module, register_hip_resnet_encoder,
+                     register_hip_vit_encoder)
 from .registry import PatchFeatureExtractorRegistry
 from .vit import register_clip, register_conch, register_dinov2, register_dinov3, register_more_vits, register_phikon, register_uni, register_vits
 
 __all__ = ["FeatureExtractor", "HipViTFeatureExtractor", "PatchFeatureExtractor",
            "PatchFeatureExtractorRegistry", "build_default_registry", "CustomEncoderComponents",
            "CustomEncoderLoader", "register_custom_encoder", "register_hip_vit_encoder",
-           "register_feature_extractors_from_module"]
+           "register_feature_extractors_from_module", "register_hip_resnet_encoder"]
 
 
 def build_default_registry(*, device="cuda", num_workers: int = 0,

@@ -6,8 +6,8 @@
   loader=..., device=..., dtype=..., num_workers=0, non_blocking=False)`` whose ``loader(device,
   dtype)`` returns ``CustomEncoderComponents(model, preprocess, forward_fn=None)``.
 
-MI355X addition: ``register_hip_vit_encoder`` lets a plugin hand over a ViT state dict and have
-it run in the native HIP kernels instead of as a torch module.
+MI355X addition: ``register_hip_vit_encoder`` / ``register_hip_resnet_encoder`` let a plugin hand over a ViT / ResNet
+state dict and have it run in the native HIP kernels instead of as a torch module.
 """
 from __future__ import annotations
 
@@ -69,6 +69,20 @@ def register_hip_vit_encoder(*, registry: PatchFeatureExtractorRegistry, name: s
     registry.register(name, build)
 
 
+def register_hip_resnet_encoder(*, registry: PatchFeatureExtractorRegistry, name: str,
+                                state_dict_loader: Callable[[], dict], arch, device: torch.device,
+                                dtype: torch.dtype, mean=None, std=None, source: str = "auto") -> None:
+    """Register a ResNet checkpoint (torchvision or transformers ResNetModel keys; ``arch`` one of resnet18 .. resnet152 or
+    a dict ``{"block": "basic" | "bottleneck", "depths": (d1, d2, d3, d4)}``) to run in the native HIP kernels (lazy)."""
+    from .resnet import build_hip_resnet_extractor
+
+    def build():
+        return build_hip_resnet_extractor(name=name, arch=arch, state_dict=state_dict_loader(), device=device,
+                                          dtype=dtype, mean=mean, std=std, source=source)
+
+    registry.register(name, build)
+
+
 class CustomRegistryHook(Protocol):
     def __call__(self, registry: PatchFeatureExtractorRegistry, device: torch.device,
                  dtype: torch.dtype, num_workers: int) -> None: ...
@@ -96,5 +110,5 @@ def register_feature_extractors_from_module(module_path, registry: PatchFeatureE
 
 
 __all__ = ["CustomEncoderComponents", "CustomEncoderLoader", "CustomRegistryHook",
-           "register_custom_encoder", "register_hip_vit_encoder",
+           "register_custom_encoder", "register_hip_vit_encoder", "register_hip_resnet_encoder",
            "register_feature_extractors_from_module"]

@@ -1,0 +1,355 @@
+"""ResNet-18 / 34 / 50 / 101 / 152 encoders on the native HIP convolution kernels (models/patch/resnet.py of the reference).
+
+The reference builds torchvision ``resnetXX(weights=IMAGENET1K_V1)`` with ``fc = Identity``: the feature is the flattened
+global average pool (512-d for 18 / 34, 2048-d for 50 / 101 / 152), preprocessing ``weights.transforms()`` =
+``ImageClassification(crop_size=224)`` -- Pillow BILINEAR resize of the shorter side to 256, centre crop 224, ImageNet
+normalisation.  On the default 256-px tiles that is a pure centre crop (the transform of ``vit_b_16``).
+
+Here every convolution, both pools and the preprocess run in the kernels of ``conv.hip`` behind ``ap_resnet_*``, with
+BatchNorm folded into the convolutions on the host (f32).  Checkpoints come in torchvision keys (``conv1``, ``bn1``,
+``layerX.Y.convK`` / ``bnK``, ``downsample.0/1``; ``fc.*`` dropped) or transformers ``ResNetModel`` keys
+(``embedder.embedder.*``, ``encoder.stages.S.layers.L.{layer.K,shortcut}.*``); both are detected.
+
+These names are not in ``build_default_registry``: they are registered by ``register_resnets``, which the shipped plugin
+``atlaspatch_amd/plugins/torchvision_resnets.py`` calls (``--feature-plugin``).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import logging
+import re
+from typing import Optional
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from .. import _lib
+from .base import HipViTFeatureExtractor
+from .vit import IMAGENET_MEAN, IMAGENET_STD, _env_seed, load_checkpoint, weights_path
+
+logger = logging.getLogger("atlaspatch_amd.encoders.resnet")
+
+BN_EPS = 1e-5
+TRANSFORM_RESIZE = (256, "bilinear")      # ImageClassification(crop_size=224): resize 256 (Pillow BILINEAR), crop 224
+
+ARCHS = {
+    "resnet18": {"block": "basic", "depths": (2, 2, 2, 2), "embed_dim": 512},
+    "resnet34": {"block": "basic", "depths": (3, 4, 6, 3), "embed_dim": 512},
+    "resnet50": {"block": "bottleneck", "depths": (3, 4, 6, 3), "embed_dim": 2048},
+    "resnet101": {"block": "bottleneck", "depths": (3, 4, 23, 3), "embed_dim": 2048},
+    "resnet152": {"block": "bottleneck", "depths": (3, 8, 36, 3), "embed_dim": 2048},
+}
+DEFAULTS = {"stem_width": 64, "image_size": 224}
+MAX_BATCH = 256         # device batch: resnet50's four activation buffers at 256 tiles are 1.6 GB in float16
+
+
+def _spec(arch) -> dict:
+    spec = dict(DEFAULTS)
+    spec.update(ARCHS[arch] if isinstance(arch, str) else arch)
+    return spec
+
+
+def conv_layers(arch) -> list:
+    """[(name, cout, cin, k, stride, has_bn)] of every convolution in forward order, torchvision names (``downsample`` for
+    the projection shortcut).  The order is the one ``ap_resnet_create`` allocates."""
+    spec = _spec(arch)
+    w = int(spec["stem_width"])
+    expansion = 4 if spec["block"] == "bottleneck" else 1
+    out = [("conv1", w, 3, 7, 2)]
+    inplanes = w
+    for s, depth in enumerate(spec["depths"]):
+        planes = w << s
+        outc = planes * expansion
+        for b in range(depth):
+            stride = 2 if (s > 0 and b == 0) else 1
+            pre = f"layer{s + 1}.{b}."
+            if spec["block"] == "bottleneck":
+                out += [(pre + "conv1", planes, inplanes, 1, 1), (pre + "conv2", planes, planes, 3, stride),
+                        (pre + "conv3", outc, planes, 1, 1)]
+            else:
+                out += [(pre + "conv1", planes, inplanes, 3, stride), (pre + "conv2", planes, planes, 3, 1)]
+            if stride != 1 or inplanes != outc:
+                out.append((pre + "downsample", outc, inplanes, 1, stride))
+            inplanes = outc
+    return out
+
+
+def _bn_name(conv: str) -> str:
+    """torchvision BatchNorm name of a convolution: conv1 -> bn1, layerX.Y.convK -> layerX.Y.bnK, downsample -> downsample.1"""
+    if conv.endswith("downsample"):
+        return conv + ".1"
+    head, _, last = conv.rpartition(".")
+    return (head + "." if head else "") + "bn" + last[len("conv"):]
+
+
+def _conv_key(conv: str) -> str:
+    return conv + (".0.weight" if conv.endswith("downsample") else ".weight")
+
+
+def canonical_keys(arch) -> dict:
+    """{torchvision key: shape} of the unfolded checkpoint (no ``fc``, no ``num_batches_tracked``)."""
+    keys = {}
+    for name, cout, cin, k, _ in conv_layers(arch):
+        keys[_conv_key(name)] = (cout, cin, k, k)
+        for p in ("weight", "bias", "running_mean", "running_var"):
+            keys[f"{_bn_name(name)}.{p}"] = (cout,)
+    return keys
+
+
+_HF_CONV = re.compile(r"^encoder\.stages\.(\d+)\.layers\.(\d+)\.(layer\.(\d+)|shortcut)\.(convolution|normalization)\.(.+)$")
+
+
+def _hf_to_torchvision(key: str) -> Optional[str]:
+    if key.startswith("embedder.embedder."):
+        rest = key[len("embedder.embedder."):]
+        if rest.startswith("convolution."):
+            return "conv1." + rest[len("convolution."):]
+        if rest.startswith("normalization."):
+            return "bn1." + rest[len("normalization."):]
+        return None
+    m = _HF_CONV.match(key)
+    if m is None:
+        return None
+    stage, layer, part, k, kind, param = m.groups()
+    pre = f"layer{int(stage) + 1}.{int(layer)}."
+    if part == "shortcut":
+        return pre + ("downsample.0." if kind == "convolution" else "downsample.1.") + param
+    return pre + (f"conv{int(k) + 1}." if kind == "convolution" else f"bn{int(k) + 1}.") + param
+
+
+def detect_source(sd: dict) -> str:
+    keys = list(sd)
+    if any(k.startswith(("embedder.", "encoder.stages.", "resnet.embedder.")) for k in keys):
+        return "hf"
+    if any(k.startswith(("conv1.", "layer1.")) for k in keys):
+        return "torchvision"
+    raise ValueError("ResNet checkpoint: neither torchvision keys (conv1.*, layerX.Y.*) nor transformers ResNetModel keys "
+                     f"(embedder.embedder.*, encoder.stages.*) found; first keys: {keys[:5]}")
+
+
+def canonical_state_dict(sd: dict, *, arch, source: str = "auto") -> dict:
+    """The checkpoint as unfolded float32 tensors under torchvision keys (``canonical_keys``).  ``source``: "torchvision",
+    "hf" (transformers ``ResNetModel``; a ``ResNetForImageClassification`` dict's ``resnet.`` prefix is stripped) or "auto".
+    The classifier (``fc.*`` / ``classifier.*``) and ``num_batches_tracked`` are dropped; any other unknown key, a missing
+    key or a wrong shape is a ``ValueError``."""
+    if source == "auto":
+        source = detect_source(sd)
+    if source not in ("torchvision", "hf"):
+        raise ValueError(f"unknown ResNet checkpoint layout {source!r}")
+    want = canonical_keys(arch)
+    out, unknown = {}, []
+    for key, value in sd.items():
+        if key.endswith("num_batches_tracked"):
+            continue
+        if source == "hf":
+            k = key[len("resnet."):] if key.startswith("resnet.") else key
+            if k.startswith("classifier."):
+                continue
+            name = _hf_to_torchvision(k)
+        else:
+            name = key[len("module."):] if key.startswith("module.") else key
+            if name.startswith("fc."):
+                continue
+        if name is None or name not in want:
+            unknown.append(key)
+            continue
+        out[name] = torch.as_tensor(value).detach().to(torch.float32).cpu().contiguous()
+    if unknown:
+        raise ValueError(f"ResNet checkpoint ({source} layout): {len(unknown)} unknown key(s) for this architecture, e.g. "
+                         f"{unknown[:5]}")
+    missing = [k for k in want if k not in out]
+    if missing:
+        raise ValueError(f"ResNet checkpoint ({source} layout): {len(missing)} missing key(s), e.g. {missing[:5]}")
+    for k, shape in want.items():
+        if tuple(out[k].shape) != shape:
+            raise ValueError(f"ResNet checkpoint: {k} has shape {tuple(out[k].shape)}, expected {shape}")
+    return out
+
+
+def fold_batchnorm(canonical: dict, *, arch, dtype: torch.dtype = torch.float32, eps: float = BN_EPS) -> dict:
+    """Conv + BatchNorm (eval) -> one conv with bias, in float32: W' = W g / sqrt(var + eps), b' = beta - mean g / sqrt(var + eps).
+    Keys ``<conv>.weight`` / ``<conv>.bias`` (``downsample`` for the projection), what ``ap_resnet_set_param`` takes.  A folded
+    weight that is not finite in ``dtype`` (or a bias that is not finite) is refused."""
+    out = {}
+    for name, *_ in conv_layers(arch):
+        bn = _bn_name(name)
+        g, beta = canonical[f"{bn}.weight"], canonical[f"{bn}.bias"]
+        mean, var = canonical[f"{bn}.running_mean"], canonical[f"{bn}.running_var"]
+        scale = g / torch.sqrt(var + eps)
+        w = canonical[_conv_key(name)] * scale.view(-1, 1, 1, 1)
+        b = beta - mean * scale
+        if not bool(torch.isfinite(w.to(dtype)).all()) or not bool(torch.isfinite(b).all()):
+            raise ValueError(f"{name}: the BatchNorm-folded weights are not finite in {dtype} (max |w'| = "
+                             f"{float(w.abs().max()):.3g}); this checkpoint cannot run in that precision")
+        out[f"{name}.weight"] = w.contiguous()
+        out[f"{name}.bias"] = b.contiguous()
+    return out
+
+
+def _forward_calibrate(sd: dict, arch, x: torch.Tensor) -> None:
+    """Seeded random init: one CPU float32 forward that sets every BatchNorm's running statistics to the batch statistics of
+    its input (rounded to float16 precision so that they do not depend on the host's summation order)."""
+    spec = _spec(arch)
+
+    def bn(t, name):
+        mean = t.mean(dim=(0, 2, 3))
+        var = t.var(dim=(0, 2, 3), unbiased=False)
+        sd[f"{name}.running_mean"] = mean.half().float()
+        sd[f"{name}.running_var"] = var.half().float()
+        return F.batch_norm(t, sd[f"{name}.running_mean"], sd[f"{name}.running_var"], sd[f"{name}.weight"], sd[f"{name}.bias"],
+                            False, 0.0, BN_EPS)
+
+    layers = {name: (k, stride) for name, _, _, k, stride in conv_layers(arch)}
+
+    def conv(t, name):
+        k, stride = layers[name]
+        return F.conv2d(t, sd[_conv_key(name)], stride=stride, padding=k // 2)
+
+    x = F.relu(bn(conv(x, "conv1"), "bn1"))
+    x = F.max_pool2d(x, 3, 2, 1)
+    n_conv = 3 if spec["block"] == "bottleneck" else 2
+    for s, depth in enumerate(spec["depths"]):
+        for b in range(depth):
+            pre = f"layer{s + 1}.{b}."
+            y = x
+            for i in range(1, n_conv + 1):
+                y = bn(conv(y, f"{pre}conv{i}"), f"{pre}bn{i}")
+                if i < n_conv:
+                    y = F.relu(y)
+            sc = bn(conv(x, pre + "downsample"), pre + "downsample.1") if pre + "downsample" in layers else x
+            x = F.relu(y + sc)
+
+
+def random_canonical_state_dict(arch, seed: int = 0) -> dict:
+    """Seeded, well-conditioned random weights in canonical (torchvision, unfolded) form: He-normal convolutions, BatchNorm
+    gains near 1 (the last BatchNorm of every block scaled by 1 / sqrt(blocks in its stage), so that the residual sums of a
+    stage stay O(1)), small shifts, and running statistics calibrated on a seeded random image batch -- activations stay
+    O(1) through all stages, in float16's range with room to spare."""
+    spec = _spec(arch)
+    g = torch.Generator().manual_seed(int(seed))
+    sd = {}
+    n_conv = 3 if spec["block"] == "bottleneck" else 2
+    for name, cout, cin, k, _ in conv_layers(arch):
+        sd[_conv_key(name)] = torch.randn(cout, cin, k, k, generator=g) * float(np.sqrt(2.0 / (cin * k * k)))
+        bn = _bn_name(name)
+        gain = 0.8 + 0.4 * torch.rand(cout, generator=g)
+        m = re.match(r"layer(\d+)\.\d+\.conv(\d+)$", name)
+        if m and int(m.group(2)) == n_conv:
+            gain = gain / float(np.sqrt(spec["depths"][int(m.group(1)) - 1]))
+        sd[f"{bn}.weight"] = gain
+        sd[f"{bn}.bias"] = 0.1 * torch.randn(cout, generator=g)
+    x = torch.randn(2, 3, 128, 128, generator=g)
+    with torch.no_grad():
+        _forward_calibrate(sd, arch, x)
+    return {k: sd[k].contiguous() for k in canonical_keys(arch)}
+
+
+# ----------------------------------------------------------------------------- device object
+class HipResNet:
+    """Device-resident ResNet behind ``ap_resnet_*`` (the ``vit`` object ``HipViTFeatureExtractor`` drives: ``forward_u8``,
+    ``embed_dim``, ``release``, ``device``)."""
+
+    def __init__(self, arch, folded: dict, *, device: torch.device, dtype: torch.dtype) -> None:
+        if torch.device(device).type != "cuda":
+            raise _lib.HipLibraryError("HipResNet needs a HIP device ('cuda' on PyTorch-ROCm); there is no CPU fallback")
+        spec = _spec(arch)
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        self.dtype = dtype
+        cfg = _lib.ResnetConfig(1 if spec["block"] == "bottleneck" else 0, (C.c_int * 4)(*spec["depths"]),
+                                int(spec["stem_width"]), _lib.torch_dtype_code(dtype), int(spec["image_size"]))
+        handle = C.c_void_p()
+        arrs = {k: np.ascontiguousarray(v.detach().to(torch.float32).cpu().numpy()) for k, v in folded.items()}
+        # hipMalloc / hipMemcpy on the legacy stream must not fall into another thread's stream capture (the SAM2 hipGraph)
+        with _lib.HIP_CAPTURE_LOCK, torch.cuda.device(self.device):
+            _lib.check(self.lib.ap_resnet_create(C.byref(cfg), C.byref(handle)), "ap_resnet_create")
+            self._handle = handle
+            for k, a in arrs.items():
+                _lib.check(self.lib.ap_resnet_set_param(self._handle, k.encode(), a.ctypes.data, a.size), f"ap_resnet_set_param({k})")
+            _lib.check(self.lib.ap_resnet_finalize(self._handle), "ap_resnet_finalize")
+        self.embed_dim = int(self.lib.ap_resnet_embed_dim(self._handle))
+        self._workspace: Optional[torch.Tensor] = None
+
+    def _ws(self, n: int) -> torch.Tensor:
+        need = int(self.lib.ap_resnet_workspace_bytes(self._handle, n))
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = None
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._workspace
+
+    def forward_u8(self, tiles: torch.Tensor, mean, std, out: torch.Tensor) -> torch.Tensor:
+        """tiles: uint8 [n, H, W, 3] on the device; out: float32 [n, embed_dim] on the device (written)."""
+        if self._handle is None:
+            raise _lib.HipLibraryError("HipResNet used after release()")
+        assert tiles.dtype == torch.uint8 and tiles.is_contiguous() and tiles.dim() == 4 and tiles.shape[3] == 3
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (tiles.shape[0], self.embed_dim)
+        n, h, w, _ = tiles.shape
+        if n == 0:
+            return out
+        ws = self._ws(n)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.ap_resnet_forward_u8(self._handle, tiles.data_ptr(), n, h, w, _lib.f3(mean), _lib.f3(std),
+                                                     out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                     _lib.current_stream_ptr(self.device)), "ap_resnet_forward_u8")
+        return out
+
+    def profile(self, on: bool) -> None:
+        _lib.check(self.lib.ap_resnet_profile_enable(self._handle, 1 if on else 0), "ap_resnet_profile_enable")
+
+    def profile_read(self) -> dict:
+        """{kind: (milliseconds, launches)} accumulated since the last read (HIP events)."""
+        k = len(_lib.RESNET_PROF_KINDS)
+        ms = (C.c_double * k)()
+        cnt = (C.c_longlong * k)()
+        _lib.check(self.lib.ap_resnet_profile_read(self._handle, ms, cnt, k), "ap_resnet_profile_read")
+        return {name: (float(ms[i]), int(cnt[i])) for i, name in enumerate(_lib.RESNET_PROF_KINDS)}
+
+    def release(self) -> None:
+        if getattr(self, "_handle", None) is not None:
+            torch.cuda.synchronize(self.device)
+            self.lib.ap_resnet_destroy(self._handle)
+            self._handle = None
+            self._workspace = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+# ----------------------------------------------------------------------------- builders
+def build_hip_resnet_extractor(*, name: str, arch, device, dtype, state_dict: Optional[dict] = None, source: str = "auto",
+                               mean=None, std=None, max_batch: int = MAX_BATCH,
+                               random_init_seed: Optional[int] = None) -> HipViTFeatureExtractor:
+    """A ResNet checkpoint (``state_dict``, else ``$ATLASPATCH_WEIGHTS_DIR/<name>.{safetensors,pt,pth}``, else seeded random
+    weights when ``random_init_seed`` is given) as an extractor on the HIP kernels, behind the same device front end as the
+    ViTs: Pillow-exact device resize (shorter side -> 256, bilinear) for tiles that are not 256 px, then centre crop 224."""
+    if state_dict is None:
+        path = weights_path(name)
+        if path is not None:
+            canonical = canonical_state_dict(load_checkpoint(path), arch=arch, source=source)
+        elif random_init_seed is not None:
+            logger.warning("%s: using seeded RANDOM weights (seed %d); features are not meaningful", name, random_init_seed)
+            canonical = random_canonical_state_dict(arch, random_init_seed)
+        else:
+            raise FileNotFoundError(
+                f"No weights for '{name}': set ATLASPATCH_WEIGHTS_DIR to a directory holding {name}.safetensors/.pt "
+                "(torchvision or transformers ResNetModel key names), or set ATLASPATCH_RANDOM_INIT=<seed> for seeded "
+                "random weights (benchmarks/tests).")
+    else:
+        canonical = canonical_state_dict(state_dict, arch=arch, source=source)
+    folded = fold_batchnorm(canonical, arch=arch, dtype=dtype)
+    net = HipResNet(arch, folded, device=torch.device(device), dtype=dtype)
+    return HipViTFeatureExtractor(name=name, vit=net, mean=mean or IMAGENET_MEAN, std=std or IMAGENET_STD,
+                                  max_batch=max_batch, resize=TRANSFORM_RESIZE, expect_size=None)
+
+
+def register_resnets(registry, *, device, dtype=torch.float32, num_workers: int = 0) -> None:
+    """resnet18 / 34 / 50 / 101 / 152 (models/patch/resnet.py): torchvision ImageNet weights from ATLASPATCH_WEIGHTS_DIR
+    (torchvision or transformers keys), or ATLASPATCH_RANDOM_INIT=<seed>."""
+    dev = torch.device(device)
+    for name in ARCHS:
+        registry.register(name, lambda n=name: build_hip_resnet_extractor(
+            name=n, arch=n, device=dev, dtype=dtype, random_init_seed=_env_seed()))

@@ -439,6 +439,65 @@ int ap_layernorm(int out_dtype, const float* x, long stride, int rows, int dim,
 int ap_attention(int dtype, const void* qkv, void* out, int n, int tokens, int heads, int head_dim,
                  ap_stream_t stream);
 
+/* ---- ResNet encoder (additive to ABI v20) ------------------------------------------------
+ * Replaces the torchvision resnet18 / 34 / 50 / 101 / 152 forward of models/patch/resnet.py (fc = Identity: the flattened
+ * global average pool) with the implicit-GEMM convolution kernels of conv.hip.  Activations are NHWC in the compute type;
+ * BatchNorm is folded into the convolutions by the caller (f32 weight and bias per convolution); accumulation is f32.
+ * The structure follows the ap_vit_config rules: struct_size first, fields only ever appended, all-zero = the behaviour
+ * before a field existed; fill it through ap_resnet_config_init. */
+typedef struct ap_resnet ap_resnet;
+typedef struct ap_resnet_config {
+    uint32_t struct_size; /* sizeof(ap_resnet_config) as the caller sees it; written by ap_resnet_config_init */
+    int block;            /* AP_RESNET_BASIC (resnet18 / 34) or AP_RESNET_BOTTLENECK (resnet50 / 101 / 152, expansion 4,
+                             stride on the 3x3 conv as torchvision) */
+    int depths[4];        /* blocks per stage: 2 2 2 2 / 3 4 6 3 / 3 4 6 3 / 3 4 23 3 / 3 8 36 3 */
+    int stem_width;       /* 64: the stem's output channels and the first stage's width (multiple of 64) */
+    int compute_dtype;    /* AP_F16 / AP_BF16 / AP_F32 (exact f32 MFMA products) */
+    int image_size;       /* 224: the centre crop the network sees */
+} ap_resnet_config;
+#define AP_RESNET_CONFIG_SIZE_V20 36u   /* the smallest size ap_resnet_create accepts */
+#define AP_RESNET_BASIC 0
+#define AP_RESNET_BOTTLENECK 1
+size_t ap_sizeof_resnet_config(void);
+/* Zero-fills sizeof_caller bytes at cfg and records sizeof_caller in cfg->struct_size (AP_ERR_INVALID for NULL or a size
+ * below AP_RESNET_CONFIG_SIZE_V20 / not a multiple of 4). */
+int ap_resnet_config_init(ap_resnet_config* cfg, size_t sizeof_caller);
+int ap_resnet_create(const ap_resnet_config* cfg, ap_resnet** out);
+void ap_resnet_destroy(ap_resnet* m);
+/* Upload one parameter (host float32, torch layout, `count` elements); synchronous.  Names (torchvision's, BatchNorm folded):
+ *   conv1.weight [W, 3, 7, 7] | conv1.bias [W]
+ *   layer<s>.<b>.conv<k>.weight [Cout, Cin, kh, kw] | .bias [Cout]     (k = 1, 2 basic; 1, 2, 3 bottleneck)
+ *   layer<s>.<b>.downsample.weight [Cout, Cin, 1, 1] | .bias [Cout]     (the first block of a stage whose shape changes)
+ * The host permutes the weights to [Cout][ky][kx][Cin] (the stem's Cin padded to 8 with zeros).  Setting a parameter
+ * un-finalises the object. */
+int ap_resnet_set_param(ap_resnet* m, const char* name, const float* host, size_t count);
+int ap_resnet_finalize(ap_resnet* m);          /* AP_ERR_STATE if a parameter was never set */
+size_t ap_resnet_workspace_bytes(const ap_resnet* m, int n);
+int ap_resnet_embed_dim(const ap_resnet* m);   /* 8 x stem_width (basic) or 32 x stem_width (bottleneck) */
+#define AP_RESNET_PROF_STEM 0      /* NHWC preprocess + 7x7 stem convolution */
+#define AP_RESNET_PROF_CONV1X1 1
+#define AP_RESNET_PROF_CONV3X3 2
+#define AP_RESNET_PROF_POOL 3      /* max pool + global average pool */
+#define AP_RESNET_PROF_KINDS 4
+int ap_resnet_profile_enable(ap_resnet* m, int on);
+int ap_resnet_profile_read(ap_resnet* m, double* ms_by_kind, long long* launches_by_kind, int kinds);
+/* patches: device uint8 [n, h, w, 3] (h, w >= image_size): centre crop, normalise, network, global average pool.
+ * out: device float32 [n, embed_dim].  Same arguments as ap_vit_forward_u8; asynchronous on `stream`. */
+int ap_resnet_forward_u8(ap_resnet* m, const uint8_t* patches, int n, int h, int w,
+                         const float mean[3], const float stdv[3],
+                         float* out, void* workspace, size_t workspace_bytes, ap_stream_t stream);
+
+/* Single operators of the ResNet forward (NHWC, T = dtype, device pointers 16-byte aligned):
+ * ap_conv2d_nhwc: out[n, Ho, Wo, cout] = act(conv(x, weight) + bias[co] (+ resid)), x T [n, h, w, cin] (cin % 8 == 0),
+ *   weight T [cout][ksize][ksize][cin] (cout % 64 == 0), bias f32 [cout], resid T [n, Ho, Wo, cout] or NULL, relu 0 / 1;
+ *   Ho = (h + 2 pad - ksize) / stride + 1; taps outside the image are zeros.
+ * ap_maxpool3x3s2_nhwc: out T [n, (h - 1) / 2 + 1, (w - 1) / 2 + 1, c] (padding 1; padded taps ignored), c % 8 == 0.
+ * ap_avgpool_nhwc: out f32 [n, c] = mean over the hw pixels of x T [n, hw, c], summed in f32. */
+int ap_conv2d_nhwc(int dtype, const void* x, int n, int h, int w, int cin, const void* weight, const float* bias, int cout,
+                   int ksize, int stride, int pad, const void* resid, int relu, void* out, ap_stream_t stream);
+int ap_maxpool3x3s2_nhwc(int dtype, const void* x, int n, int h, int w, int c, void* out, ap_stream_t stream);
+int ap_avgpool_nhwc(int dtype, const void* x, int n, int hw, int c, float* out, ap_stream_t stream);
+
 /* ---- float32 operator set of the SAM2 (Hiera-T) tissue segmenter ------------------------
  * Replaces the torch modules behind SAM2ImagePredictor.set_image / predict as the reference drives them
  * (services/segmentation.py:120-140: one 1024 x 1024 thumbnail per slide, box prompt = whole image,
