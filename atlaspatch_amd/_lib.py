@@ -59,6 +59,18 @@ class ResnetConfig(C.Structure):
 RESNET_PROF_KINDS = ("stem", "conv1x1", "conv3x3", "pool")
 
 
+class ConvnextConfig(C.Structure):
+    """``ap_convnext_config`` (additive to ABI v20); ``struct_size`` is filled in here."""
+    _fields_ = [("struct_size", C.c_uint32), ("depths", C.c_int * 4), ("widths", C.c_int * 4), ("compute_dtype", C.c_int),
+                ("image_size", C.c_int)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(C.sizeof(type(self)), *args, **kw)
+
+
+CONVNEXT_PROF_KINDS = ("stem", "dwconv_ln", "fc1", "fc2", "downsample", "pool")
+
+
 # name -> (restype, argtypes); every symbol include/atlaspatch_hip.h declares
 SIGNATURES = {
     "ap_abi_version": (C.c_int, []),
@@ -114,6 +126,24 @@ SIGNATURES = {
                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ap_maxpool3x3s2_nhwc": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ap_avgpool_nhwc": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ap_sizeof_convnext_config": (C.c_size_t, []),
+    "ap_convnext_config_init": (C.c_int, [C.POINTER(ConvnextConfig), C.c_size_t]),
+    "ap_convnext_create": (C.c_int, [C.POINTER(ConvnextConfig), C.POINTER(C.c_void_p)]),
+    "ap_convnext_destroy": (None, [C.c_void_p]),
+    "ap_convnext_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]),
+    "ap_convnext_finalize": (C.c_int, [C.c_void_p]),
+    "ap_convnext_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "ap_convnext_embed_dim": (C.c_int, [C.c_void_p]),
+    "ap_convnext_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "ap_convnext_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_int]),
+    "ap_convnext_forward_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                         C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ap_conv2d_nhwc_ex": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                    C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "ap_dwconv7_ln_nhwc": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "ap_layernorm_rows": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                    C.c_void_p]),
     "ap_gemm": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ap_gemm_fused": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

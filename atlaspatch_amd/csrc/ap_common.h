@@ -269,6 +269,14 @@ int launch_preproc_nhwc8(const uint8_t* src, int n, int h, int w, int top, int l
                          const float stdv[3], void* dst, int dtype, hipStream_t stream);
 int launch_maxpool3x3s2_nhwc(int dtype, const void* x, int n, int h, int w, int c, void* out, hipStream_t stream);
 int launch_avgpool_nhwc(int dtype, const void* x, int n, int hw, int c, float* out, hipStream_t stream);
+// conv.hip (ConvNeXt): the implicit GEMM with Cout % 32 == 0 and act 0 none / 1 ReLU / 2 GELU (erf)
+int launch_conv2d_nhwc_ex(int dtype, const void* x, int n, int h, int w, int cin, const void* weight, const float* bias, int cout,
+                          int ksize, int stride, int pad, const void* resid, int act, void* out, hipStream_t stream);
+// convnext.hip: fused depthwise 7x7 + bias + LayerNorm, and LayerNorm over T rows
+int launch_dwconv7_ln_nhwc(int dtype, const void* x, int n, int h, int w, int c, const float* dw_weight, const float* dw_bias,
+                           const float* ln_weight, const float* ln_bias, float eps, void* out, hipStream_t stream);
+int launch_layernorm_rows(int dtype, const void* x, int rows, int c, const float* weight, const float* bias, float eps, void* out,
+                          hipStream_t stream);
 
 int tile_content_counts(const uint8_t* tiles, int n, int h, int w, int black_thresh, int sat_thresh,
                         int value_thresh, unsigned* counts, hipStream_t stream);

@@ -14,6 +14,10 @@
 // current step's MFMAs.  Cout % 64 == 0 covers every layer of the five networks (64 .. 2048) with one tile; the M tail
 // (7 x 7 x n rows in the last stage) is masked row by row.  Epilogue: + bias (BatchNorm folded on the host, f32), + residual
 // (T, the output's shape), ReLU, store T.
+//
+// conv_implicit_gemm<T, EXT = true> is the ConvNeXt instantiation (ap_conv2d_nhwc_ex): Cout % 32 == 0, the last N tile's
+// upper 32 columns masked (no weight row read, no store), and a GELU (erf) epilogue beside ReLU.  EXT = false is the ResNet
+// kernel behind ap_conv2d_nhwc; its instruction stream is the one it had before EXT existed.
 #include "ap_common.h"
 
 namespace ap {
@@ -29,8 +33,11 @@ struct ConvArgs {
     const float* bias;      // f32 [Cout]
     const void* resid;      // T [M, Cout] or null
     void* out;              // T [M, Cout]
-    int H, W, Cin, Ho, Wo, Cout, ks, stride, pad, K, M, relu;
+    int H, W, Cin, Ho, Wo, Cout, ks, stride, pad, K, M;
+    int act;                // EXT = false: ReLU if nonzero; EXT = true: ACT_NONE / ACT_RELU / ACT_GELU
 };
+
+enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2 };
 
 template <typename T> struct ConvMma;
 template <> struct ConvMma<f16> {
@@ -54,7 +61,7 @@ template <> struct ConvMma<float> {
 
 template <typename T> __device__ __forceinline__ float to_f32(T v) { return (float)v; }
 
-template <typename T>
+template <typename T, bool EXT>
 __global__ __launch_bounds__(CTHREADS) void conv_implicit_gemm(ConvArgs a) {
     constexpr int CH = 16 / sizeof(T);                 // elements per 16-byte chunk
     constexpr int KT = KBYTES / sizeof(T);             // K elements per step
@@ -63,7 +70,7 @@ __global__ __launch_bounds__(CTHREADS) void conv_implicit_gemm(ConvArgs a) {
     __shared__ __attribute__((aligned(16))) char Bs[CBN * LDS_ROW];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ntiles = a.Cout / CBN;
+    const int ntiles = EXT ? (a.Cout + CBN - 1) / CBN : a.Cout / CBN;
     const int mt = blockIdx.x / ntiles, nt = blockIdx.x - mt * ntiles;
     const int m0 = mt * CBM, n0 = nt * CBN;
 
@@ -105,7 +112,11 @@ __global__ __launch_bounds__(CTHREADS) void conv_implicit_gemm(ConvArgs a) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             u32x4 v = {0u, 0u, 0u, 0u};
-            if (kin) v = *(const u32x4*)(w + (size_t)(n0 + r0 + 32 * i) * a.K + k);
+            if constexpr (EXT) {                       // the 32-wide tail: rows past Cout read as zeros
+                if (kin && n0 + r0 + 32 * i < a.Cout) v = *(const u32x4*)(w + (size_t)(n0 + r0 + 32 * i) * a.K + k);
+            } else {
+                if (kin) v = *(const u32x4*)(w + (size_t)(n0 + r0 + 32 * i) * a.K + k);
+            }
             rb[i] = v;
         }
     };
@@ -146,6 +157,9 @@ __global__ __launch_bounds__(CTHREADS) void conv_implicit_gemm(ConvArgs a) {
 
     // epilogue: C/D map col = lane & 31, row = (j & 3) + 8 (j >> 2) + 4 (lane >> 5)
     const int n = n0 + wn * 32 + fr;
+    if constexpr (EXT) {
+        if (n >= a.Cout) return;                       // a whole wave: the upper half of the 32-wide tail tile
+    }
     const float b = a.bias[n];
     const T* resid = (const T*)a.resid;
     T* out = (T*)a.out;
@@ -158,7 +172,12 @@ __global__ __launch_bounds__(CTHREADS) void conv_implicit_gemm(ConvArgs a) {
             const size_t o = (size_t)m * a.Cout + n;
             float v = acc[i][j] + b;
             if (resid) v += to_f32(resid[o]);
-            if (a.relu) v = v > 0.f ? v : 0.f;
+            if constexpr (EXT) {
+                if (a.act == ACT_RELU) v = v > 0.f ? v : 0.f;
+                else if (a.act == ACT_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+            } else {
+                if (a.act) v = v > 0.f ? v : 0.f;
+            }
             out[o] = from_f32<T>(v);
         }
 }
@@ -258,9 +277,38 @@ int launch_conv2d_nhwc(int dtype, const void* x, int n, int h, int w, int cin, c
     const size_t blocks = (M + CBM - 1) / CBM * (size_t)(cout / CBN);
     AP_REQUIRE(blocks < (size_t)1 << 31, "conv2d_nhwc: grid too large");
     switch (dtype) {
-        case AP_F16: conv_implicit_gemm<f16><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
-        case AP_BF16: conv_implicit_gemm<bf16><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
-        default: conv_implicit_gemm<float><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
+        case AP_F16: conv_implicit_gemm<f16, false><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
+        case AP_BF16: conv_implicit_gemm<bf16, false><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
+        default: conv_implicit_gemm<float, false><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
+    }
+    AP_HIP_CHECK(hipGetLastError());
+    return AP_OK;
+}
+
+int launch_conv2d_nhwc_ex(int dtype, const void* x, int n, int h, int w, int cin, const void* weight, const float* bias, int cout,
+                          int ksize, int stride, int pad, const void* resid, int act, void* out, hipStream_t stream) {
+    AP_REQUIRE(x && weight && bias && out, "conv2d_nhwc_ex: null pointer");
+    AP_REQUIRE(dtype == AP_F16 || dtype == AP_BF16 || dtype == AP_F32, "conv2d_nhwc_ex: dtype %d", dtype);
+    AP_REQUIRE(n >= 0 && h > 0 && w > 0, "conv2d_nhwc_ex: shape n %d h %d w %d", n, h, w);
+    AP_REQUIRE(cin > 0 && cin % 8 == 0, "conv2d_nhwc_ex: Cin %d must be a multiple of 8 (pad the channels with zeros)", cin);
+    AP_REQUIRE(cout > 0 && cout % 32 == 0, "conv2d_nhwc_ex: Cout %d must be a multiple of 32", cout);
+    AP_REQUIRE(ksize >= 1 && ksize <= 7 && stride >= 1 && stride <= 4 && pad >= 0 && pad < ksize,
+               "conv2d_nhwc_ex: kernel %d stride %d pad %d", ksize, stride, pad);
+    AP_REQUIRE(h + 2 * pad >= ksize && w + 2 * pad >= ksize, "conv2d_nhwc_ex: %dx%d input smaller than the %d kernel", h, w, ksize);
+    AP_REQUIRE((((uintptr_t)x | (uintptr_t)weight | (uintptr_t)out | (uintptr_t)resid) & 15) == 0,
+               "conv2d_nhwc_ex: pointers must be 16-byte aligned");
+    AP_REQUIRE(act == ACT_NONE || act == ACT_RELU || act == ACT_GELU, "conv2d_nhwc_ex: activation %d (0 none, 1 ReLU, 2 GELU)", act);
+    const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (w + 2 * pad - ksize) / stride + 1;
+    const size_t M = (size_t)n * ho * wo;
+    AP_REQUIRE(M < (size_t)1 << 31 && (size_t)ksize * ksize * cin < (size_t)1 << 24, "conv2d_nhwc_ex: problem too large");
+    if (M == 0) return AP_OK;
+    ConvArgs a{x, weight, bias, resid, out, h, w, cin, ho, wo, cout, ksize, stride, pad, ksize * ksize * cin, (int)M, act};
+    const size_t blocks = (M + CBM - 1) / CBM * (size_t)((cout + CBN - 1) / CBN);
+    AP_REQUIRE(blocks < (size_t)1 << 31, "conv2d_nhwc_ex: grid too large");
+    switch (dtype) {
+        case AP_F16: conv_implicit_gemm<f16, true><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
+        case AP_BF16: conv_implicit_gemm<bf16, true><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
+        default: conv_implicit_gemm<float, true><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
     }
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
@@ -325,6 +373,12 @@ int ap_conv2d_nhwc(int dtype, const void* x, int n, int h, int w, int cin, const
                    int ksize, int stride, int pad, const void* resid, int relu, void* out, ap_stream_t stream) {
     return ap::launch_conv2d_nhwc(dtype, x, n, h, w, cin, weight, bias, cout, ksize, stride, pad, resid, relu, out,
                                   (hipStream_t)stream);
+}
+
+int ap_conv2d_nhwc_ex(int dtype, const void* x, int n, int h, int w, int cin, const void* weight, const float* bias, int cout,
+                      int ksize, int stride, int pad, const void* resid, int act, void* out, ap_stream_t stream) {
+    return ap::launch_conv2d_nhwc_ex(dtype, x, n, h, w, cin, weight, bias, cout, ksize, stride, pad, resid, act, out,
+                                     (hipStream_t)stream);
 }
 
 int ap_maxpool3x3s2_nhwc(int dtype, const void* x, int n, int h, int w, int c, void* out, ap_stream_t stream) {

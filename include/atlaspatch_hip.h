@@ -498,6 +498,67 @@ int ap_conv2d_nhwc(int dtype, const void* x, int n, int h, int w, int cin, const
 int ap_maxpool3x3s2_nhwc(int dtype, const void* x, int n, int h, int w, int c, void* out, ap_stream_t stream);
 int ap_avgpool_nhwc(int dtype, const void* x, int n, int hw, int c, float* out, ap_stream_t stream);
 
+/* ---- ConvNeXt encoder (additive to ABI v20) ----------------------------------------------
+ * Replaces the torchvision convnext_tiny / small / base / large forward of models/patch/convnext.py (classifier = Identity:
+ * the flattened global average pool of the last stage, WITHOUT the head's LayerNorm) with the kernels of convnext.hip and
+ * conv.hip.  Activations are NHWC in the compute type; accumulation and LayerNorm statistics are f32; every LayerNorm has
+ * eps 1e-6 and every GELU is the erf form.  Same structure rules as ap_resnet_config. */
+typedef struct ap_convnext ap_convnext;
+typedef struct ap_convnext_config {
+    uint32_t struct_size; /* sizeof(ap_convnext_config) as the caller sees it; written by ap_convnext_config_init */
+    int depths[4];        /* blocks per stage: 3 3 9 3 (tiny) / 3 3 27 3 (small, base, large) */
+    int widths[4];        /* channels per stage (multiples of 32): 96 192 384 768 / 128 256 512 1024 / 192 384 768 1536 */
+    int compute_dtype;    /* AP_F16 / AP_BF16 / AP_F32 (exact f32 MFMA products) */
+    int image_size;       /* 224: the centre crop the network sees (a multiple of 32) */
+} ap_convnext_config;
+#define AP_CONVNEXT_CONFIG_SIZE_V20 44u   /* the smallest size ap_convnext_create accepts */
+size_t ap_sizeof_convnext_config(void);
+int ap_convnext_config_init(ap_convnext_config* cfg, size_t sizeof_caller);
+int ap_convnext_create(const ap_convnext_config* cfg, ap_convnext** out);
+void ap_convnext_destroy(ap_convnext* m);
+/* Upload one parameter (host float32, torch layout, `count` elements); synchronous.  Names (torchvision's; s = 1, 3, 5, 7
+ * for the four stages, d = 2, 4, 6 for the downsampling layers in front of stages 2 - 4):
+ *   features.0.0.weight [C0, 3, 4, 4] | .bias [C0]            stem convolution (stride 4)
+ *   features.0.1.weight [C0] | .bias [C0]                      stem LayerNorm
+ *   features.<s>.<j>.block.0.weight [C, 1, 7, 7] | .bias [C]   depthwise 7x7 convolution (padding 3)
+ *   features.<s>.<j>.block.2.weight [C] | .bias [C]            LayerNorm
+ *   features.<s>.<j>.block.3.weight [4C, C] | .bias [4C]       fc1 (GELU follows)
+ *   features.<s>.<j>.block.5.weight [C, 4C] | .bias [C]        fc2 WITH layer_scale folded in by the caller (gamma_o * W[o],
+ *                                                              gamma_o * b[o], in f32)
+ *   features.<d>.0.weight [C] | .bias [C]                      downsampling LayerNorm
+ *   features.<d>.1.weight [2C, C, 2, 2] | .bias [2C]           downsampling convolution (stride 2)
+ * Setting a parameter un-finalises the object. */
+int ap_convnext_set_param(ap_convnext* m, const char* name, const float* host, size_t count);
+int ap_convnext_finalize(ap_convnext* m);          /* AP_ERR_STATE if a parameter was never set */
+size_t ap_convnext_workspace_bytes(const ap_convnext* m, int n);
+int ap_convnext_embed_dim(const ap_convnext* m);   /* widths[3] */
+#define AP_CONVNEXT_PROF_STEM 0        /* preprocess + stem convolution + stem LayerNorm */
+#define AP_CONVNEXT_PROF_DWCONV_LN 1
+#define AP_CONVNEXT_PROF_FC1 2
+#define AP_CONVNEXT_PROF_FC2 3
+#define AP_CONVNEXT_PROF_DOWNSAMPLE 4  /* LayerNorm + 2x2 stride-2 convolution */
+#define AP_CONVNEXT_PROF_POOL 5
+#define AP_CONVNEXT_PROF_KINDS 6
+int ap_convnext_profile_enable(ap_convnext* m, int on);
+int ap_convnext_profile_read(ap_convnext* m, double* ms_by_kind, long long* launches_by_kind, int kinds);
+/* Same arguments and semantics as ap_resnet_forward_u8; out: device float32 [n, widths[3]]. */
+int ap_convnext_forward_u8(ap_convnext* m, const uint8_t* patches, int n, int h, int w,
+                           const float mean[3], const float stdv[3],
+                           float* out, void* workspace, size_t workspace_bytes, ap_stream_t stream);
+
+/* Single operators of the ConvNeXt forward (NHWC, T = dtype, device pointers 16-byte aligned):
+ * ap_conv2d_nhwc_ex: ap_conv2d_nhwc with cout % 32 == 0 and act 0 none / 1 ReLU / 2 GELU (erf), applied after the residual.
+ * ap_dwconv7_ln_nhwc: y = T(depthwise 7x7 conv (padding 3) of x T [n, h, w, c] + dw_bias), then out T [n, h, w, c] =
+ *   LayerNorm over the c channels of each pixel of y (f32 statistics, eps) * ln_weight + ln_bias; dw_weight f32 [49][c]
+ *   (tap-major: [(ky * 7 + kx) * c + ch]), the rest f32 [c]; c % 8 == 0; out must not alias x.
+ * ap_layernorm_rows: out T [rows, c] = LayerNorm of each row of x T [rows, c] (f32 statistics, eps) * weight + bias. */
+int ap_conv2d_nhwc_ex(int dtype, const void* x, int n, int h, int w, int cin, const void* weight, const float* bias, int cout,
+                      int ksize, int stride, int pad, const void* resid, int act, void* out, ap_stream_t stream);
+int ap_dwconv7_ln_nhwc(int dtype, const void* x, int n, int h, int w, int c, const float* dw_weight, const float* dw_bias,
+                       const float* ln_weight, const float* ln_bias, float eps, void* out, ap_stream_t stream);
+int ap_layernorm_rows(int dtype, const void* x, int rows, int c, const float* weight, const float* bias, float eps, void* out,
+                      ap_stream_t stream);
+
 /* ---- float32 operator set of the SAM2 (Hiera-T) tissue segmenter ------------------------
  * Replaces the torch modules behind SAM2ImagePredictor.set_image / predict as the reference drives them
  * (services/segmentation.py:120-140: one 1024 x 1024 thumbnail per slide, box prompt = whole image,
