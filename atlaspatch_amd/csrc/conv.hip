@@ -255,63 +255,54 @@ inline int grid_for(size_t work) {
     return (int)(b < 65536 ? (b > 0 ? b : 1) : 65536);
 }
 
-}  // namespace
-
-int launch_conv2d_nhwc(int dtype, const void* x, int n, int h, int w, int cin, const void* weight, const float* bias, int cout,
-                       int ksize, int stride, int pad, const void* resid, int relu, void* out, hipStream_t stream) {
-    AP_REQUIRE(x && weight && bias && out, "conv2d_nhwc: null pointer");
-    AP_REQUIRE(dtype == AP_F16 || dtype == AP_BF16 || dtype == AP_F32, "conv2d_nhwc: dtype %d", dtype);
-    AP_REQUIRE(n >= 0 && h > 0 && w > 0, "conv2d_nhwc: shape n %d h %d w %d", n, h, w);
-    AP_REQUIRE(cin > 0 && cin % 8 == 0, "conv2d_nhwc: Cin %d must be a multiple of 8 (pad the channels with zeros)", cin);
-    AP_REQUIRE(cout > 0 && cout % CBN == 0, "conv2d_nhwc: Cout %d must be a multiple of %d", cout, CBN);
+// The implicit GEMM's launcher.  EXT = false: ap_conv2d_nhwc (ResNet; Cout % 64, act = ReLU flag); EXT = true: ap_conv2d_nhwc_ex
+// (ConvNeXt; Cout % 32 through the masked N tail, act 0 none / 1 ReLU / 2 GELU).
+template <bool EXT>
+int launch_conv2d(int dtype, const void* x, int n, int h, int w, int cin, const void* weight, const float* bias, int cout, int ksize,
+                  int stride, int pad, const void* resid, int act, void* out, hipStream_t stream) {
+    const char* who = EXT ? "conv2d_nhwc_ex" : "conv2d_nhwc";
+    const int cout_step = EXT ? 32 : CBN;
+    AP_REQUIRE(x && weight && bias && out, "%s: null pointer", who);
+    AP_REQUIRE(dtype == AP_F16 || dtype == AP_BF16 || dtype == AP_F32, "%s: dtype %d", who, dtype);
+    AP_REQUIRE(n >= 0 && h > 0 && w > 0, "%s: shape n %d h %d w %d", who, n, h, w);
+    AP_REQUIRE(cin > 0 && cin % 8 == 0, "%s: Cin %d must be a multiple of 8 (pad the channels with zeros)", who, cin);
+    AP_REQUIRE(cout > 0 && cout % cout_step == 0, "%s: Cout %d must be a multiple of %d", who, cout, cout_step);
     AP_REQUIRE(ksize >= 1 && ksize <= 7 && stride >= 1 && stride <= 4 && pad >= 0 && pad < ksize,
-               "conv2d_nhwc: kernel %d stride %d pad %d", ksize, stride, pad);
-    AP_REQUIRE(h + 2 * pad >= ksize && w + 2 * pad >= ksize, "conv2d_nhwc: %dx%d input smaller than the %d kernel", h, w, ksize);
+               "%s: kernel %d stride %d pad %d", who, ksize, stride, pad);
+    AP_REQUIRE(h + 2 * pad >= ksize && w + 2 * pad >= ksize, "%s: %dx%d input smaller than the %d kernel", who, h, w, ksize);
     AP_REQUIRE((((uintptr_t)x | (uintptr_t)weight | (uintptr_t)out | (uintptr_t)resid) & 15) == 0,
-               "conv2d_nhwc: pointers must be 16-byte aligned");
+               "%s: pointers must be 16-byte aligned", who);
+    if (EXT) {
+        AP_REQUIRE(act == ACT_NONE || act == ACT_RELU || act == ACT_GELU, "%s: activation %d (0 none, 1 ReLU, 2 GELU)", who, act);
+    } else {
+        act = act ? ACT_RELU : ACT_NONE;
+    }
     const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (w + 2 * pad - ksize) / stride + 1;
     const size_t M = (size_t)n * ho * wo;
-    AP_REQUIRE(M < (size_t)1 << 31 && (size_t)ksize * ksize * cin < (size_t)1 << 24, "conv2d_nhwc: problem too large");
+    AP_REQUIRE(M < (size_t)1 << 31 && (size_t)ksize * ksize * cin < (size_t)1 << 24, "%s: problem too large", who);
     if (M == 0) return AP_OK;
-    ConvArgs a{x, weight, bias, resid, out, h, w, cin, ho, wo, cout, ksize, stride, pad, ksize * ksize * cin, (int)M, relu ? 1 : 0};
-    const size_t blocks = (M + CBM - 1) / CBM * (size_t)(cout / CBN);
-    AP_REQUIRE(blocks < (size_t)1 << 31, "conv2d_nhwc: grid too large");
+    ConvArgs a{x, weight, bias, resid, out, h, w, cin, ho, wo, cout, ksize, stride, pad, ksize * ksize * cin, (int)M, act};
+    const size_t blocks = (M + CBM - 1) / CBM * (size_t)((cout + CBN - 1) / CBN);
+    AP_REQUIRE(blocks < (size_t)1 << 31, "%s: grid too large", who);
     switch (dtype) {
-        case AP_F16: conv_implicit_gemm<f16, false><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
-        case AP_BF16: conv_implicit_gemm<bf16, false><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
-        default: conv_implicit_gemm<float, false><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
+        case AP_F16: conv_implicit_gemm<f16, EXT><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
+        case AP_BF16: conv_implicit_gemm<bf16, EXT><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
+        default: conv_implicit_gemm<float, EXT><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
     }
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }
 
+}  // namespace
+
+int launch_conv2d_nhwc(int dtype, const void* x, int n, int h, int w, int cin, const void* weight, const float* bias, int cout,
+                       int ksize, int stride, int pad, const void* resid, int relu, void* out, hipStream_t stream) {
+    return launch_conv2d<false>(dtype, x, n, h, w, cin, weight, bias, cout, ksize, stride, pad, resid, relu, out, stream);
+}
+
 int launch_conv2d_nhwc_ex(int dtype, const void* x, int n, int h, int w, int cin, const void* weight, const float* bias, int cout,
                           int ksize, int stride, int pad, const void* resid, int act, void* out, hipStream_t stream) {
-    AP_REQUIRE(x && weight && bias && out, "conv2d_nhwc_ex: null pointer");
-    AP_REQUIRE(dtype == AP_F16 || dtype == AP_BF16 || dtype == AP_F32, "conv2d_nhwc_ex: dtype %d", dtype);
-    AP_REQUIRE(n >= 0 && h > 0 && w > 0, "conv2d_nhwc_ex: shape n %d h %d w %d", n, h, w);
-    AP_REQUIRE(cin > 0 && cin % 8 == 0, "conv2d_nhwc_ex: Cin %d must be a multiple of 8 (pad the channels with zeros)", cin);
-    AP_REQUIRE(cout > 0 && cout % 32 == 0, "conv2d_nhwc_ex: Cout %d must be a multiple of 32", cout);
-    AP_REQUIRE(ksize >= 1 && ksize <= 7 && stride >= 1 && stride <= 4 && pad >= 0 && pad < ksize,
-               "conv2d_nhwc_ex: kernel %d stride %d pad %d", ksize, stride, pad);
-    AP_REQUIRE(h + 2 * pad >= ksize && w + 2 * pad >= ksize, "conv2d_nhwc_ex: %dx%d input smaller than the %d kernel", h, w, ksize);
-    AP_REQUIRE((((uintptr_t)x | (uintptr_t)weight | (uintptr_t)out | (uintptr_t)resid) & 15) == 0,
-               "conv2d_nhwc_ex: pointers must be 16-byte aligned");
-    AP_REQUIRE(act == ACT_NONE || act == ACT_RELU || act == ACT_GELU, "conv2d_nhwc_ex: activation %d (0 none, 1 ReLU, 2 GELU)", act);
-    const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (w + 2 * pad - ksize) / stride + 1;
-    const size_t M = (size_t)n * ho * wo;
-    AP_REQUIRE(M < (size_t)1 << 31 && (size_t)ksize * ksize * cin < (size_t)1 << 24, "conv2d_nhwc_ex: problem too large");
-    if (M == 0) return AP_OK;
-    ConvArgs a{x, weight, bias, resid, out, h, w, cin, ho, wo, cout, ksize, stride, pad, ksize * ksize * cin, (int)M, act};
-    const size_t blocks = (M + CBM - 1) / CBM * (size_t)((cout + CBN - 1) / CBN);
-    AP_REQUIRE(blocks < (size_t)1 << 31, "conv2d_nhwc_ex: grid too large");
-    switch (dtype) {
-        case AP_F16: conv_implicit_gemm<f16, true><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
-        case AP_BF16: conv_implicit_gemm<bf16, true><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
-        default: conv_implicit_gemm<float, true><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
-    }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return launch_conv2d<true>(dtype, x, n, h, w, cin, weight, bias, cout, ksize, stride, pad, resid, act, out, stream);
 }
 
 int launch_preproc_nhwc8(const uint8_t* src, int n, int h, int w, int top, int left, int S, const float mean[3],

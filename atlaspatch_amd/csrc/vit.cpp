@@ -15,7 +15,7 @@
 #include <map>
 #include <string>
 #include <vector>
-#include "ap_common.h"
+#include "engine_host.h"
 #include <cstdlib>
 
 namespace ap {
@@ -80,39 +80,16 @@ struct ap_vit {
     bool fold_dirty = false;                // a parameter the folded weights depend on was set after the last finalize
     std::vector<float*> pending_free;       // ap_vit_set_params: f32 uploads to release once its stream has drained
     int device = 0;
-    // optional per-launch HIP-event timing (ap_vit_profile_*): kind -> events of the last forwards
-    bool profile = false;
-    std::vector<hipEvent_t> ev_pool;
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> ev_used;
-    size_t ev_next = 0;
+    ap::LaunchProfiler prof;                // optional per-launch HIP-event timing (ap_vit_profile_*)
     // experimental two-half overlap (AP_VIT_OVERLAP=1): second stream + hand-off events
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 };
 
 namespace {
-hipEvent_t next_event(ap_vit* m) {
-    if (m->ev_next == m->ev_pool.size()) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return nullptr;
-        m->ev_pool.push_back(e);
-    }
-    return m->ev_pool[m->ev_next++];
-}
-struct ScopedTimer {      // records start/stop events around one launch when profiling is on
-    ap_vit* m; int kind; hipStream_t s; hipEvent_t a = nullptr, b = nullptr;
-    ScopedTimer(ap_vit* m_, int kind_, hipStream_t s_) : m(m_), kind(kind_), s(s_) {
-        if (m->profile) { a = next_event(m); b = next_event(m); if (a) (void)hipEventRecord(a, s); }
-    }
-    ~ScopedTimer() {
-        if (m->profile && a && b) { (void)hipEventRecord(b, s); m->ev_used.push_back({kind, {a, b}}); }
-    }
-};
-}  // namespace
-
-namespace {
 
 using ap::Param;
+using ap::ScopedTimer;
 
 int alloc_param(ap_vit* m, const std::string& name, int rows, int cols, bool matrix) {
     Param p;
@@ -198,7 +175,7 @@ int patch_embed(ap_vit* m, int n, const Workspace& w, hipStream_t stream) {
         g.bias = m->pe_b;
         g.pos = m->pos;
         g.out = w.tok; g.ldo = D; g.P = m->patches; g.R = m->prefix; g.pos_row0 = m->pos_row0;
-        { ScopedTimer t(m, AP_PROF_GEMM_PATCH_EMBED, stream);
+        { ScopedTimer t(m->prof, AP_PROF_GEMM_PATCH_EMBED, stream);
           if ((rc = ap::launch_gemm(dt, ap::EPI_PATCH_EMBED, g, stream)) != AP_OK) return rc; }
         if ((rc = ap::launch_cls_init(w.tok, m->prefix_dev, m->prefix, n, m->tokens, D, stream)) != AP_OK) return rc;
     }
@@ -216,9 +193,9 @@ int patch_embed_stream(ap_vit* m, int n, const Workspace& w, hipStream_t stream)
     g.M = n * m->patches; g.N = D; g.K = m->kpe;
     g.bias = m->pe_b; g.pos16 = m->pos16; g.P = m->patches; g.R = m->prefix; g.pos_row0 = m->pos_row0;
     g.out = w.x16; g.ldo = D; g.partial = w.partial;
-    { ScopedTimer t(m, AP_PROF_GEMM_PATCH_EMBED, stream);
+    { ScopedTimer t(m->prof, AP_PROF_GEMM_PATCH_EMBED, stream);
       if ((rc = ap::launch_gemm(dt, ap::EPI_PATCH_STREAM, g, stream)) != AP_OK) return rc; }
-    ScopedTimer t(m, AP_PROF_LAYERNORM, stream);
+    ScopedTimer t(m->prof, AP_PROF_LAYERNORM, stream);
     if ((rc = ap::launch_cls_stream(dt, m->prefix_dev, m->prefix, 0, n, m->tokens, D, w.x16, w.partial, stream)) != AP_OK) return rc;
     return ap::launch_rowstats_finalize(w.partial, n * m->tokens, D / 64, D, c.ln_eps, w.rowstats, stream);
 }
@@ -242,7 +219,7 @@ int blocks_f32_stream(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipS
     const float* pending_ls = nullptr;   // ... and its LayerScale vector (applied in f32 by the add)
     for (int i = 0; i < c.depth; ++i) {
         const ap::BlockParams& bp = m->blocks[i];
-        { ScopedTimer t(m, AP_PROF_LAYERNORM, stream);
+        { ScopedTimer t(m->prof, AP_PROF_LAYERNORM, stream);
           if ((rc = ap::launch_add2_layernorm(dt, dt, w.tok, D, pending, D, pending_ls, nullptr, 0, nullptr, /*store=*/0,
                                               M, D, bp.ln1_w, bp.ln1_b, c.ln_eps, w.xn,
                                               stream)) != AP_OK) return rc; }
@@ -260,13 +237,13 @@ int blocks_f32_stream(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipS
                 g.A = w.xn; g.lda = D; g.W = (const char*)wsel(m, wq) + (size_t)DA * wq->ld * es; g.split = use_split(m); g.ldw = wq->ld;
                 g.M = M; g.N = 2 * DA; g.K = D; g.bias = bp.qkv_b + DA;
                 g.out = (char*)w.qkv + (size_t)DA * es; g.ldo = 3 * DA;
-                ScopedTimer t(m, AP_PROF_GEMM_QKV, stream);
+                ScopedTimer t(m->prof, AP_PROF_GEMM_QKV, stream);
                 if ((rc = ap::launch_gemm(dt, ap::EPI_BIAS_STORE, g, stream)) != AP_OK) return rc;
                 if (c.rope && (rc = ap::launch_rope(dt, w.qkv, n, m->tokens, m->prefix, c.heads, m->hd, m->rope_cos, m->rope_sin, 2,
                                                     stream)) != AP_OK) return rc;     // the class rows' q is not rotated
             }
             // n-row GEMMs on the 128x128 kernel: more workgroups than 256x256 tiles would give, bit-identical results
-            ScopedTimer t(m, AP_PROF_CLS_TAIL, stream);
+            ScopedTimer t(m->prof, AP_PROF_CLS_TAIL, stream);
             {
                 ap::GemmArgs g{};                                          // q for the CLS rows
                 g.A = w.xn; g.lda = (int)cls_stride; g.W = wsel(m, wq); g.split = use_split(m); g.ldw = wq->ld;
@@ -307,12 +284,12 @@ int blocks_f32_stream(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipS
             ap::GemmArgs g{};
             g.A = w.xn; g.lda = D; g.W = wsel(m, bp.qkv); g.split = use_split(m); g.ldw = bp.qkv->ld;
             g.M = M; g.N = 3 * DA; g.K = D; g.bias = bp.qkv_b; g.out = w.qkv; g.ldo = 3 * DA;
-            ScopedTimer t(m, AP_PROF_GEMM_QKV, stream);
+            ScopedTimer t(m->prof, AP_PROF_GEMM_QKV, stream);
             if ((rc = ap::launch_gemm(dt, ap::EPI_BIAS_STORE, g, stream)) != AP_OK) return rc;
             if (c.rope && (rc = ap::launch_rope(dt, w.qkv, n, m->tokens, m->prefix, c.heads, m->hd, m->rope_cos, m->rope_sin, 3,
                                                 stream)) != AP_OK) return rc;
         }
-        { ScopedTimer t(m, AP_PROF_ATTENTION, stream);
+        { ScopedTimer t(m->prof, AP_PROF_ATTENTION, stream);
           if (use_split(m) && n <= 65535) {
               // float32, split-f16 products: the fused float32 attention of the SAM2 operator set in its split form (image = window,
               // q | k | v at column offsets of the packed rows) -- same arithmetic class as the GEMMs around it; 46 -> 27.5 ms of a
@@ -327,10 +304,10 @@ int blocks_f32_stream(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipS
             g.A = w.att; g.lda = DA; g.W = wsel(m, bp.proj); g.split = use_split(m); g.ldw = bp.proj->ld;
             g.M = M; g.N = D; g.K = DA; g.bias = bp.proj_b;
             g.out = w.delta2; g.ldo = D;
-            ScopedTimer t(m, AP_PROF_GEMM_PROJ, stream);
+            ScopedTimer t(m->prof, AP_PROF_GEMM_PROJ, stream);
             if ((rc = ap::launch_gemm(dt, ap::EPI_BIAS_STORE, g, stream)) != AP_OK) return rc;
         }
-        { ScopedTimer t(m, AP_PROF_LAYERNORM, stream);
+        { ScopedTimer t(m->prof, AP_PROF_LAYERNORM, stream);
           if ((rc = ap::launch_add2_layernorm(dt, dt, w.tok, D, pending, D, pending_ls, w.delta2, D,
                                               bp.ls1, /*store=*/1, M, D, bp.ln2_w,
                                               bp.ln2_b, c.ln_eps, w.xn, stream)) != AP_OK) return rc; }
@@ -338,7 +315,7 @@ int blocks_f32_stream(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipS
             ap::GemmArgs g{};
             g.A = w.xn; g.lda = D; g.W = wsel(m, bp.fc1); g.split = use_split(m); g.ldw = bp.fc1->ld;
             g.M = M; g.N = F1; g.K = D; g.bias = bp.fc1_b; g.out = w.hid; g.ldo = F1;
-            ScopedTimer t(m, AP_PROF_GEMM_FC1, stream);
+            ScopedTimer t(m->prof, AP_PROF_GEMM_FC1, stream);
             if ((rc = ap::launch_gemm(dt, swiglu ? ap::EPI_BIAS_STORE : (c.act == AP_ACT_QUICK_GELU ? ap::EPI_BIAS_QGELU : ap::EPI_BIAS_GELU), g, stream)) != AP_OK) return rc;
             if (swiglu && (rc = ap::launch_swiglu(dt, w.hid, M, H, w.hid2, stream)) != AP_OK) return rc;
         }
@@ -347,7 +324,7 @@ int blocks_f32_stream(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipS
             g.A = w.hid2; g.lda = H; g.W = wsel(m, bp.fc2); g.split = use_split(m); g.ldw = bp.fc2->ld;
             g.M = M; g.N = D; g.K = H; g.bias = bp.fc2_b;
             g.out = w.delta; g.ldo = D;
-            ScopedTimer t(m, AP_PROF_GEMM_FC2, stream);
+            ScopedTimer t(m->prof, AP_PROF_GEMM_FC2, stream);
             if ((rc = ap::launch_gemm(dt, ap::EPI_BIAS_STORE, g, stream)) != AP_OK) return rc;
         }
         pending = w.delta;
@@ -382,7 +359,7 @@ int blocks_fused(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipStream
     const bool exact_cls = m->exact_cls && (c.pool == AP_POOL_CLS || c.pool == AP_POOL_CLS_MEAN) && M < (1 << 24);
     const long cls_stride = (long)m->tokens;         // rows between two images' class rows
     if (exact_cls) {
-        ScopedTimer t(m, AP_PROF_CLS_TAIL, stream);
+        ScopedTimer t(m->prof, AP_PROF_CLS_TAIL, stream);
         // the class rows as the stream starts: the row the patch embedding (or CLIP's ln_pre) left in f32, or the shared prefix row
         if (c.pre_norm) {
             AP_HIP_CHECK(hipMemcpy2DAsync(w.cls32, (size_t)D * 4, w.tok, (size_t)cls_stride * D * 4, (size_t)D * 4, n,
@@ -391,13 +368,13 @@ int blocks_fused(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipStream
     }
     // cls32 += the branch the launch before left in cls_branch, then stream row <- T(cls32)
     auto exact_cls_update = [&]() -> int {
-        ScopedTimer t(m, AP_PROF_LAYERNORM, stream);
+        ScopedTimer t(m->prof, AP_PROF_LAYERNORM, stream);
         return ap::launch_cls_exact_update(dt, w.cls32, w.cls_branch, n, m->tokens, D, w.x16, w.partial, stream);
     };
     // statistics of the new rows; with the exact class rows the same launch folds the branch into cls32 and re-rounds the
     // stream's class rows (launch_rowstats_finalize_cls)
     auto finalize_stats = [&]() -> int {
-        ScopedTimer t(m, AP_PROF_LAYERNORM, stream);
+        ScopedTimer t(m->prof, AP_PROF_LAYERNORM, stream);
         return ap::launch_rowstats_finalize_cls(w.partial, M, G, D, c.ln_eps, w.rowstats, dt, exact_cls ? w.cls32 : nullptr,
                                                 w.cls_branch, w.x16, n, m->tokens, stream);
     };
@@ -413,12 +390,12 @@ int blocks_fused(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipStream
                 g.A = w.x16; g.lda = D; g.W = (const char*)fb.qkv_w + (size_t)DA * bp.qkv->ld * es; g.ldw = bp.qkv->ld;
                 g.M = M; g.N = 2 * DA; g.K = D; g.bias = fb.qkv_b + DA; g.colsum = fb.qkv_cs + DA; g.rowstats = w.rowstats;
                 g.out = (char*)w.qkv + (size_t)DA * es; g.ldo = 3 * DA;
-                ScopedTimer t(m, AP_PROF_GEMM_QKV, stream);
+                ScopedTimer t(m->prof, AP_PROF_GEMM_QKV, stream);
                 if ((rc = ap::launch_gemm(dt, ap::EPI_NORM_STORE, g, stream)) != AP_OK) return rc;
                 if (c.rope && (rc = ap::launch_rope(dt, w.qkv, n, m->tokens, m->prefix, c.heads, m->hd, m->rope_cos, m->rope_sin, 2,
                                                     stream)) != AP_OK) return rc;
             }
-            ScopedTimer t(m, AP_PROF_CLS_TAIL, stream);
+            ScopedTimer t(m->prof, AP_PROF_CLS_TAIL, stream);
             if (exact_cls) AP_HIP_CHECK(hipMemcpyAsync(w.tok, w.cls32, (size_t)n * D * 4, hipMemcpyDeviceToDevice, stream));
             else if ((rc = ap::launch_stream_to_f32(dt, w.x16, (long)m->tokens * D, n, D, w.tok, stream)) != AP_OK) return rc;
             if ((rc = ap::launch_add2_layernorm(dt, dt, w.tok, D, nullptr, 0, nullptr, nullptr, 0, nullptr, /*store=*/0,
@@ -462,19 +439,19 @@ int blocks_fused(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipStream
             g.A = w.x16; g.lda = D; g.W = fb.qkv_w; g.ldw = bp.qkv->ld;
             g.M = M; g.N = 3 * DA; g.K = D; g.bias = fb.qkv_b; g.colsum = fb.qkv_cs; g.rowstats = w.rowstats;
             g.out = w.qkv; g.ldo = 3 * DA;
-            ScopedTimer t(m, AP_PROF_GEMM_QKV, stream);
+            ScopedTimer t(m->prof, AP_PROF_GEMM_QKV, stream);
             if ((rc = ap::launch_gemm(dt, ap::EPI_NORM_STORE, g, stream)) != AP_OK) return rc;
             if (c.rope && (rc = ap::launch_rope(dt, w.qkv, n, m->tokens, m->prefix, c.heads, m->hd, m->rope_cos, m->rope_sin, 3,
                                                 stream)) != AP_OK) return rc;
         }
-        { ScopedTimer t(m, AP_PROF_ATTENTION, stream);
+        { ScopedTimer t(m->prof, AP_PROF_ATTENTION, stream);
           if ((rc = ap::launch_attention(dt, w.qkv, w.att, n, m->tokens, c.heads, m->hd, m->attn_scale, stream)) != AP_OK) return rc; }
         {
             ap::GemmArgs g{};
             g.A = w.att; g.lda = DA; g.W = fb.proj_w; g.ldw = bp.proj->ld;
             g.M = M; g.N = D; g.K = DA; g.bias = fb.proj_b; g.out = w.x16; g.ldo = D; g.partial = w.partial;
             if (exact_cls) { g.cls_branch = w.cls_branch; g.cls_tokens = m->tokens; }
-            ScopedTimer t(m, AP_PROF_GEMM_PROJ, stream);
+            ScopedTimer t(m->prof, AP_PROF_GEMM_PROJ, stream);
             if ((rc = ap::launch_gemm(dt, ap::EPI_RESID_STATS, g, stream)) != AP_OK) return rc;
         }
         if ((rc = finalize_stats()) != AP_OK) return rc;
@@ -485,7 +462,7 @@ int blocks_fused(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipStream
             // SwiGLU: the folded fc1 weights are row-interleaved (x1 | x2 of the same 32 output columns in one wave's tile), so
             // the gate runs in the epilogue on the f32 values: out = hid2 [M, H] directly, one rounding
             g.out = swiglu ? w.hid2 : w.hid; g.ldo = swiglu ? H : F1;
-            ScopedTimer t(m, AP_PROF_GEMM_FC1, stream);
+            ScopedTimer t(m->prof, AP_PROF_GEMM_FC1, stream);
             if ((rc = ap::launch_gemm(dt, swiglu ? ap::EPI_NORM_SWIGLU : (c.act == AP_ACT_QUICK_GELU ? ap::EPI_NORM_QGELU : ap::EPI_NORM_GELU), g, stream)) != AP_OK) return rc;
         }
         {
@@ -493,7 +470,7 @@ int blocks_fused(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipStream
             g.A = w.hid2; g.lda = H; g.W = fb.fc2_w; g.ldw = bp.fc2->ld;
             g.M = M; g.N = D; g.K = H; g.bias = fb.fc2_b; g.out = w.x16; g.ldo = D; g.partial = w.partial;
             if (exact_cls) { g.cls_branch = w.cls_branch; g.cls_tokens = m->tokens; }
-            ScopedTimer t(m, AP_PROF_GEMM_FC2, stream);
+            ScopedTimer t(m->prof, AP_PROF_GEMM_FC2, stream);
             if ((rc = ap::launch_gemm(dt, ap::EPI_RESID_STATS, g, stream)) != AP_OK) return rc;
         }
         if (i + 1 < c.depth) { if ((rc = finalize_stats()) != AP_OK) return rc; }
@@ -519,7 +496,7 @@ int run_blocks(ap_vit* m, int n, const Workspace& w, float* out, hipStream_t str
         // f32-stream dataflow, normalised in place (row-wise kernel: a row is read whole before it is written), and -- fused
         // dataflow -- rounded into the T stream together with its first row statistics (launch_stream_init)
         if ((rc = patch_embed(m, n, w, stream)) != AP_OK) return rc;
-        { ScopedTimer t(m, AP_PROF_LAYERNORM, stream);
+        { ScopedTimer t(m->prof, AP_PROF_LAYERNORM, stream);
           if ((rc = ap::launch_layernorm(AP_F32, w.tok, D, M, D, m->pre_w, m->pre_b, c.ln_eps, w.tok, stream)) != AP_OK) return rc;
           if (fused && (rc = ap::launch_stream_init(dt, w.tok, M, D, c.ln_eps, w.x16, w.rowstats, stream)) != AP_OK) return rc; }
     } else if ((rc = fused ? patch_embed_stream(m, n, w, stream) : patch_embed(m, n, w, stream)) != AP_OK) return rc;
@@ -600,21 +577,6 @@ int build_split(ap_vit* m) {
     return AP_OK;
 }
 
-int check_forward_args(const ap_vit* m, int n, const void* in, const float* out, const void* ws,
-                       size_t ws_bytes) {
-    AP_REQUIRE(m != nullptr, "vit: null handle");
-    if (!m->finalized) { ap::set_error("vit: ap_vit_finalize has not been called"); return AP_ERR_STATE; }
-    AP_REQUIRE(n >= 0, "vit: negative batch");
-    if (n == 0) return AP_OK;
-    AP_REQUIRE(in && out && ws, "vit: null buffer");
-    AP_REQUIRE(((uintptr_t)ws & 255) == 0, "vit: workspace must be 256-byte aligned");
-    if (ws_bytes < ap_vit_workspace_bytes(m, n)) {
-        ap::set_error("vit: workspace %zu bytes < required %zu", ws_bytes, ap_vit_workspace_bytes(m, n));
-        return AP_ERR_WORKSPACE;
-    }
-    return AP_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -622,38 +584,18 @@ extern "C" {
 size_t ap_sizeof_vit_config(void) { return sizeof(ap_vit_config); }
 
 int ap_vit_config_init(ap_vit_config* cfg, size_t sizeof_caller) {
-    AP_REQUIRE(cfg, "vit_config_init: null argument");
-    AP_REQUIRE(sizeof_caller >= AP_VIT_CONFIG_SIZE_V20 && sizeof_caller % 4 == 0 && sizeof_caller <= 4096,
-               "vit_config_init: %zu is not the size of an ap_vit_config (ABI v20: %u bytes, this library: %zu)", sizeof_caller,
-               AP_VIT_CONFIG_SIZE_V20, sizeof(ap_vit_config));
-    memset(cfg, 0, sizeof_caller);
-    cfg->struct_size = (uint32_t)sizeof_caller;
-    return AP_OK;
+    return ap::config_init("vit", cfg, sizeof_caller, AP_VIT_CONFIG_SIZE_V20);
 }
 
 int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
     AP_REQUIRE(cfg && out, "vit_create: null argument");
     static_assert(sizeof(ap_vit_config) == AP_VIT_CONFIG_SIZE_V20, "ap_vit_config grew: append only, keep AP_VIT_CONFIG_SIZE_V20, and drop this assert");
-    // ---- growth-safe hand-over (ABI v20): never read a byte the caller did not declare, and only sizes this structure has had.
-    // A binding written for ABI <= 19 (no size member, image_size first) presents 224 / 448 / 518 here: refused unread.
-    static const size_t known_sizes[] = {AP_VIT_CONFIG_SIZE_V20};          // append sizeof(ap_vit_config) of every later ABI
-    const size_t given = cfg->struct_size;
-    bool known = false;
-    for (size_t k : known_sizes) known = known || given == k;
-    if (!known && given > sizeof(ap_vit_config) && given % 4 == 0 && given <= 4096 && (given - sizeof(ap_vit_config)) <= 64) {
-        ap::set_error("vit_create: cfg->struct_size = %zu is larger than this library's ap_vit_config (%zu bytes, ABI %d): the binding was "
-                      "generated from a newer include/atlaspatch_hip.h than the library was built from", given, sizeof(ap_vit_config),
-                      AP_ABI_VERSION);
-        return AP_ERR_UNSUPPORTED;
-    }
-    AP_REQUIRE(known,
-               "vit_create: cfg->struct_size = %zu is not a size ap_vit_config has had (ABI v20: %u bytes; this library: %zu): fill the "
-               "structure with ap_vit_config_init(&cfg, sizeof cfg); a binding written for ABI <= 19 (no struct_size member, "
-               "image_size first) must be regenerated from include/atlaspatch_hip.h", given, AP_VIT_CONFIG_SIZE_V20, sizeof(ap_vit_config));
+    // A binding written for ABI <= 19 (no size member, image_size first) presents 224 / 448 / 518 here: only sizes up to 64 bytes
+    // past this library's count as a newer caller, so that one is refused as invalid, unread.
     ap_vit_config c;
-    memset(&c, 0, sizeof(c));
-    memcpy(&c, cfg, given < sizeof(c) ? given : sizeof(c));        // an older caller's missing tail stays zero = the old behaviour
-    c.struct_size = (uint32_t)sizeof(c);
+    int rc = ap::accept_config("vit", cfg, 64, "; a binding written for ABI <= 19 (no struct_size member, image_size first) "
+                               "must be regenerated from include/atlaspatch_hip.h", &c);
+    if (rc != AP_OK) return rc;
     AP_REQUIRE(c.image_size > 0 && c.patch_size > 0 && c.image_size % c.patch_size == 0,
                "vit_create: image %d / patch %d", c.image_size, c.patch_size);
     AP_REQUIRE(c.patch_size >= 4 && c.patch_size <= 32 && c.patch_size % 2 == 0,
@@ -700,7 +642,6 @@ int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
     m->f32_stream = getenv("AP_VIT_F32_STREAM") != nullptr;
     m->exact_cls = getenv("AP_VIT_NO_EXACT_CLS") == nullptr;
     m->split_f16 = c.compute_dtype == AP_F32 && getenv("AP_VIT_EXACT_F32") == nullptr;      // float32: split-f16 products unless asked otherwise
-    int rc = AP_OK;
     auto add = [&](const std::string& name, int rows, int cols, bool matrix) {
         if (rc == AP_OK) rc = alloc_param(m, name, rows, cols, matrix);
     };
@@ -756,7 +697,6 @@ void ap_vit_destroy(ap_vit* m) {
     for (void* p : m->fused_allocs) (void)hipFree(p);
     if (m->prefix_dev) (void)hipFree(m->prefix_dev);
     if (m->zero_bias) (void)hipFree(m->zero_bias);
-    for (hipEvent_t e : m->ev_pool) (void)hipEventDestroy(e);
     if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
     if (m->ev_join) (void)hipEventDestroy(m->ev_join);
     if (m->side) (void)hipStreamDestroy(m->side);
@@ -1007,48 +947,29 @@ int ap_vit_embed_dim(const ap_vit* m) {
     return m->cfg.pool == AP_POOL_ATTN ? m->cfg.pool_dim : (m->cfg.pool == AP_POOL_CLS_MEAN ? 2 * m->cfg.dim : m->cfg.dim);
 }
 
-int ap_vit_profile_enable(ap_vit* m, int on) {
-    AP_REQUIRE(m, "vit_profile_enable: null handle");
-    m->profile = on != 0;
-    m->ev_used.clear();
-    m->ev_next = 0;
-    return AP_OK;
-}
+int ap_vit_profile_enable(ap_vit* m, int on) { return ap::profile_enable(m ? &m->prof : nullptr, "vit", on); }
 
 int ap_vit_profile_read(ap_vit* m, double* ms_by_kind, long long* launches_by_kind, int kinds) {
-    AP_REQUIRE(m && ms_by_kind && launches_by_kind && kinds >= AP_PROF_KINDS, "vit_profile_read: bad arguments");
-    for (int k = 0; k < kinds; ++k) { ms_by_kind[k] = 0.0; launches_by_kind[k] = 0; }
-    for (auto& u : m->ev_used) {
-        AP_HIP_CHECK(hipEventSynchronize(u.second.second));
-        float ms = 0.f;
-        AP_HIP_CHECK(hipEventElapsedTime(&ms, u.second.first, u.second.second));
-        ms_by_kind[u.first] += ms;
-        launches_by_kind[u.first] += 1;
-    }
-    m->ev_used.clear();
-    m->ev_next = 0;
-    return AP_OK;
+    return ap::profile_read(m ? &m->prof : nullptr, "vit", AP_PROF_KINDS, ms_by_kind, launches_by_kind, kinds);
 }
 
 int ap_vit_forward_u8(ap_vit* m, const uint8_t* patches, int n, int h, int w, const float mean[3],
                       const float stdv[3], float* out, void* workspace, size_t workspace_bytes,
                       ap_stream_t stream) {
-    int rc = check_forward_args(m, n, patches, out, workspace, workspace_bytes);
+    int rc = ap::check_forward_args("vit", m, n, patches && out, workspace, workspace_bytes, ap_vit_workspace_bytes);
     if (rc != AP_OK || n == 0) return rc;
     const int S = m->cfg.image_size;
     AP_REQUIRE(h >= S && w >= S, "vit_forward_u8: %dx%d tiles smaller than the %d model input "
                "(resampling preprocess not in this build)", h, w, S);
-    // torchvision CenterCrop: top = int(round((h - S) / 2.0)) (banker's rounding)
-    auto crop_off = [](int full, int size) { int d = full - size; return (d / 2) + ((d & 1) && ((d / 2) & 1) ? 1 : 0); };
     hipStream_t s = (hipStream_t)stream;
     auto forward_part = [&](const uint8_t* tiles, int cnt, float* dst, char* base, hipStream_t st) -> int {
         const Workspace ws = carve(m, cnt, base);
         if (m->kpe != 3 * m->cfg.patch_size * m->cfg.patch_size)
             AP_HIP_CHECK(hipMemsetAsync(ws.hid, 0, (size_t)cnt * m->patches * m->kpe * ap::dtype_size(m->cfg.compute_dtype), st));
         int r;
-        { ScopedTimer t(m, AP_PROF_PREPROC, st);
-          r = ap::preproc_patchrows(tiles, cnt, h, w, crop_off(h, S), crop_off(w, S), S, S, m->cfg.patch_size,
-                                    mean, stdv, ws.hid, m->kpe, m->cfg.compute_dtype, st); }
+        { ScopedTimer t(m->prof, AP_PROF_PREPROC, st);
+          r = ap::preproc_patchrows(tiles, cnt, h, w, ap::center_crop_offset(h, S), ap::center_crop_offset(w, S), S, S,
+                                    m->cfg.patch_size, mean, stdv, ws.hid, m->kpe, m->cfg.compute_dtype, st); }
         if (r != AP_OK) return r;
         return run_blocks(m, cnt, ws, dst, st);
     };
@@ -1077,7 +998,7 @@ int ap_vit_forward_u8(ap_vit* m, const uint8_t* patches, int n, int h, int w, co
 
 int ap_vit_forward_chw(ap_vit* m, const void* x, int x_dtype, int n, float* out, void* workspace,
                        size_t workspace_bytes, ap_stream_t stream) {
-    int rc = check_forward_args(m, n, x, out, workspace, workspace_bytes);
+    int rc = ap::check_forward_args("vit", m, n, x && out, workspace, workspace_bytes, ap_vit_workspace_bytes);
     if (rc != AP_OK || n == 0) return rc;
     AP_REQUIRE(x_dtype == AP_F32 || x_dtype == m->cfg.compute_dtype,
                "vit_forward_chw: input dtype %d must be f32 or the compute dtype", x_dtype);

@@ -18,6 +18,7 @@
 from __future__ import annotations
 
 import abc
+import ctypes as C
 import logging
 from typing import Callable, Optional, Sequence
 
@@ -42,6 +43,96 @@ class FeatureExtractor(abc.ABC):
 
     @abc.abstractmethod
     def cleanup(self) -> None: ...
+
+
+class NativeEncoder:
+    """A device-resident encoder behind one object of the C ABI (``ap_<ABI>_*``): owns the handle and its grow-only HBM
+    workspace, and launches on torch's current stream.  ``HipViTFeatureExtractor`` drives it through ``forward_u8``,
+    ``embed_dim``, ``release`` and ``device``.  Subclasses set ``ABI`` (the symbol prefix) and ``PROF_KINDS`` (the kinds of
+    ``ap_<ABI>_profile_read``), and build the object with ``_bind`` + ``_open``."""
+
+    ABI = ""
+    PROF_KINDS: tuple = ()
+
+    def _bind(self, device, dtype) -> None:
+        if torch.device(device).type != "cuda":
+            raise _lib.HipLibraryError(f"{type(self).__name__} needs a HIP device ('cuda' on PyTorch-ROCm); "
+                                       "there is no CPU fallback")
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        self.dtype = dtype
+        self._handle = None
+        self._workspace: Optional[torch.Tensor] = None
+
+    def _fn(self, name: str):
+        return getattr(self.lib, f"ap_{self.ABI}_{name}")
+
+    def _open(self, cfg, params: dict) -> None:
+        """create -> upload every parameter (float32, torch layout) -> finalize.  hipMalloc / hipMemcpy on the legacy stream
+        must not fall into another thread's stream capture (the SAM2 hipGraph): both sides hold _lib.HIP_CAPTURE_LOCK for
+        their device section."""
+        arrs = {k: np.ascontiguousarray(v.detach().to(torch.float32).cpu().numpy()) for k, v in params.items()}
+        handle = C.c_void_p()
+        with _lib.HIP_CAPTURE_LOCK, torch.cuda.device(self.device):
+            _lib.check(self._fn("create")(C.byref(cfg), C.byref(handle)), f"ap_{self.ABI}_create")
+            self._handle = handle
+            self._upload(arrs)
+            del arrs
+            _lib.check(self._fn("finalize")(self._handle), f"ap_{self.ABI}_finalize")
+
+    def _upload(self, arrs: dict) -> None:
+        for k, a in arrs.items():
+            _lib.check(self._fn("set_param")(self._handle, k.encode(), a.ctypes.data, a.size), f"ap_{self.ABI}_set_param({k})")
+
+    def _live(self) -> None:
+        if self._handle is None:
+            raise _lib.HipLibraryError(f"{type(self).__name__} used after release()")
+
+    def _ws(self, n: int) -> torch.Tensor:
+        need = int(self._fn("workspace_bytes")(self._handle, n))
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = None
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._workspace
+
+    def forward_u8(self, tiles: torch.Tensor, mean, std, out: torch.Tensor) -> torch.Tensor:
+        """tiles: uint8 [n, H, W, 3] on the device; out: float32 [n, embed_dim] on the device (written)."""
+        self._live()
+        assert tiles.dtype == torch.uint8 and tiles.is_contiguous() and tiles.dim() == 4 and tiles.shape[3] == 3
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (tiles.shape[0], self.embed_dim)
+        n, h, w, _ = tiles.shape
+        if n == 0:
+            return out
+        ws = self._ws(n)
+        with torch.cuda.device(self.device):
+            _lib.check(self._fn("forward_u8")(self._handle, tiles.data_ptr(), n, h, w, _lib.f3(mean), _lib.f3(std),
+                                              out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr(self.device)),
+                       f"ap_{self.ABI}_forward_u8")
+        return out
+
+    def profile(self, on: bool) -> None:
+        _lib.check(self._fn("profile_enable")(self._handle, 1 if on else 0), f"ap_{self.ABI}_profile_enable")
+
+    def profile_read(self) -> dict:
+        """{kind: (milliseconds, launches)} accumulated since the last read (HIP events)."""
+        k = len(self.PROF_KINDS)
+        ms = (C.c_double * k)()
+        cnt = (C.c_longlong * k)()
+        _lib.check(self._fn("profile_read")(self._handle, ms, cnt, k), f"ap_{self.ABI}_profile_read")
+        return {name: (float(ms[i]), int(cnt[i])) for i, name in enumerate(self.PROF_KINDS)}
+
+    def release(self) -> None:
+        if getattr(self, "_handle", None) is not None:
+            torch.cuda.synchronize(self.device)
+            self._fn("destroy")(self._handle)
+            self._handle = None
+            self._workspace = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.release()
+        except Exception:
+            pass
 
 
 def _as_uint8_hwc(patch) -> np.ndarray:

@@ -18,7 +18,6 @@ These names are not in ``build_default_registry``: they are registered by ``regi
 from __future__ import annotations
 
 import ctypes as C
-import logging
 import re
 from typing import Optional
 
@@ -26,10 +25,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .base import HipViTFeatureExtractor
-from .vit import IMAGENET_MEAN, IMAGENET_STD, _env_seed, load_checkpoint, weights_path
-
-logger = logging.getLogger("atlaspatch_amd.encoders.convnext")
+from .base import HipViTFeatureExtractor, NativeEncoder
+from .vit import IMAGENET_MEAN, IMAGENET_STD, _env_seed, check_canonical, resolve_weights
 
 LN_EPS = 1e-6
 
@@ -132,16 +129,7 @@ def canonical_state_dict(sd: dict, *, arch, source: str = "auto") -> dict:
         if name.endswith("layer_scale") and t.dim() == 1:
             t = t.view(-1, 1, 1)                        # transformers keeps it as [C]
         out[name] = t.contiguous()
-    if unknown:
-        raise ValueError(f"ConvNeXt checkpoint ({source} layout): {len(unknown)} unknown key(s) for this architecture, e.g. "
-                         f"{unknown[:5]}")
-    missing = [k for k in want if k not in out]
-    if missing:
-        raise ValueError(f"ConvNeXt checkpoint ({source} layout): {len(missing)} missing key(s), e.g. {missing[:5]}")
-    for k, shape in want.items():
-        if tuple(out[k].shape) != shape:
-            raise ValueError(f"ConvNeXt checkpoint: {k} has shape {tuple(out[k].shape)}, expected {shape}")
-    return out
+    return check_canonical(out, want, unknown, family="ConvNeXt", source=source)
 
 
 def fold_layer_scale(canonical: dict, *, arch, dtype: torch.dtype = torch.float32) -> dict:
@@ -188,78 +176,18 @@ def random_canonical_state_dict(arch, seed: int = 0) -> dict:
 
 
 # ----------------------------------------------------------------------------- device object
-class HipConvNeXt:
-    """Device-resident ConvNeXt behind ``ap_convnext_*`` (the ``vit`` object ``HipViTFeatureExtractor`` drives:
-    ``forward_u8``, ``embed_dim``, ``release``, ``device``)."""
+class HipConvNeXt(NativeEncoder):
+    """Device-resident ConvNeXt behind ``ap_convnext_*``."""
+
+    ABI = "convnext"
+    PROF_KINDS = _lib.CONVNEXT_PROF_KINDS
 
     def __init__(self, arch, folded: dict, *, device: torch.device, dtype: torch.dtype) -> None:
-        if torch.device(device).type != "cuda":
-            raise _lib.HipLibraryError("HipConvNeXt needs a HIP device ('cuda' on PyTorch-ROCm); there is no CPU fallback")
+        self._bind(device, dtype)
         spec = _spec(arch)
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        self.dtype = dtype
-        cfg = _lib.ConvnextConfig((C.c_int * 4)(*spec["depths"]), (C.c_int * 4)(*spec["widths"]),
-                                  _lib.torch_dtype_code(dtype), int(spec["image_size"]))
-        handle = C.c_void_p()
-        arrs = {k: np.ascontiguousarray(v.detach().to(torch.float32).cpu().numpy()) for k, v in folded.items()}
-        # hipMalloc / hipMemcpy on the legacy stream must not fall into another thread's stream capture (the SAM2 hipGraph)
-        with _lib.HIP_CAPTURE_LOCK, torch.cuda.device(self.device):
-            _lib.check(self.lib.ap_convnext_create(C.byref(cfg), C.byref(handle)), "ap_convnext_create")
-            self._handle = handle
-            for k, a in arrs.items():
-                _lib.check(self.lib.ap_convnext_set_param(self._handle, k.encode(), a.ctypes.data, a.size),
-                           f"ap_convnext_set_param({k})")
-            _lib.check(self.lib.ap_convnext_finalize(self._handle), "ap_convnext_finalize")
+        self._open(_lib.ConvnextConfig((C.c_int * 4)(*spec["depths"]), (C.c_int * 4)(*spec["widths"]),
+                                       _lib.torch_dtype_code(dtype), int(spec["image_size"])), folded)
         self.embed_dim = int(self.lib.ap_convnext_embed_dim(self._handle))
-        self._workspace: Optional[torch.Tensor] = None
-
-    def _ws(self, n: int) -> torch.Tensor:
-        need = int(self.lib.ap_convnext_workspace_bytes(self._handle, n))
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = None
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._workspace
-
-    def forward_u8(self, tiles: torch.Tensor, mean, std, out: torch.Tensor) -> torch.Tensor:
-        """tiles: uint8 [n, H, W, 3] on the device; out: float32 [n, embed_dim] on the device (written)."""
-        if self._handle is None:
-            raise _lib.HipLibraryError("HipConvNeXt used after release()")
-        assert tiles.dtype == torch.uint8 and tiles.is_contiguous() and tiles.dim() == 4 and tiles.shape[3] == 3
-        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (tiles.shape[0], self.embed_dim)
-        n, h, w, _ = tiles.shape
-        if n == 0:
-            return out
-        ws = self._ws(n)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.ap_convnext_forward_u8(self._handle, tiles.data_ptr(), n, h, w, _lib.f3(mean), _lib.f3(std),
-                                                       out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                       _lib.current_stream_ptr(self.device)), "ap_convnext_forward_u8")
-        return out
-
-    def profile(self, on: bool) -> None:
-        _lib.check(self.lib.ap_convnext_profile_enable(self._handle, 1 if on else 0), "ap_convnext_profile_enable")
-
-    def profile_read(self) -> dict:
-        """{kind: (milliseconds, launches)} accumulated since the last read (HIP events)."""
-        k = len(_lib.CONVNEXT_PROF_KINDS)
-        ms = (C.c_double * k)()
-        cnt = (C.c_longlong * k)()
-        _lib.check(self.lib.ap_convnext_profile_read(self._handle, ms, cnt, k), "ap_convnext_profile_read")
-        return {name: (float(ms[i]), int(cnt[i])) for i, name in enumerate(_lib.CONVNEXT_PROF_KINDS)}
-
-    def release(self) -> None:
-        if getattr(self, "_handle", None) is not None:
-            torch.cuda.synchronize(self.device)
-            self.lib.ap_convnext_destroy(self._handle)
-            self._handle = None
-            self._workspace = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.release()
-        except Exception:
-            pass
 
 
 # ----------------------------------------------------------------------------- builders
@@ -270,20 +198,9 @@ def build_hip_convnext_extractor(*, name: str, arch, device, dtype, state_dict: 
     weights when ``random_init_seed`` is given) as an extractor on the HIP kernels, behind the same device front end as the
     ViTs: Pillow-exact device resize (shorter side -> the variant's resize size, bilinear), then centre crop 224."""
     spec = _spec(arch)
-    if state_dict is None:
-        path = weights_path(name)
-        if path is not None:
-            canonical = canonical_state_dict(load_checkpoint(path), arch=arch, source=source)
-        elif random_init_seed is not None:
-            logger.warning("%s: using seeded RANDOM weights (seed %d); features are not meaningful", name, random_init_seed)
-            canonical = random_canonical_state_dict(arch, random_init_seed)
-        else:
-            raise FileNotFoundError(
-                f"No weights for '{name}': set ATLASPATCH_WEIGHTS_DIR to a directory holding {name}.safetensors/.pt "
-                "(torchvision or transformers ConvNextModel key names), or set ATLASPATCH_RANDOM_INIT=<seed> for seeded "
-                "random weights (benchmarks/tests).")
-    else:
-        canonical = canonical_state_dict(state_dict, arch=arch, source=source)
+    sd, seeded = resolve_weights(name, state_dict, random_init_seed, lambda seed: random_canonical_state_dict(arch, seed),
+                                 "torchvision or transformers ConvNextModel")
+    canonical = sd if seeded else canonical_state_dict(sd, arch=arch, source=source)
     folded = fold_layer_scale(canonical, arch=arch, dtype=dtype)
     net = HipConvNeXt(arch, folded, device=torch.device(device), dtype=dtype)
     return HipViTFeatureExtractor(name=name, vit=net, mean=mean or IMAGENET_MEAN, std=std or IMAGENET_STD,

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .base import HipViTFeatureExtractor
+from .base import HipViTFeatureExtractor, NativeEncoder
 
 logger = logging.getLogger("atlaspatch_amd.encoders.vit")
 
@@ -603,16 +603,14 @@ def random_canonical_state_dict(arch: dict, seed: int = 0) -> dict:
 
 
 # ----------------------------------------------------------------------------- device object
-class HipViT:
+class HipViT(NativeEncoder):
     """Device-resident ViT encoder behind ``ap_vit_*``."""
 
+    ABI = "vit"
+    PROF_KINDS = _lib.PROF_KINDS
+
     def __init__(self, arch: dict, state: dict, *, device: torch.device, dtype: torch.dtype) -> None:
-        if device.type != "cuda":
-            raise _lib.HipLibraryError("HipViT needs a HIP device ('cuda' on PyTorch-ROCm); "
-                                       "there is no CPU fallback")
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        self.dtype = dtype
+        self._bind(device, dtype)
         self.arch = dict(arch)
         attn_pool = arch.get("pool") == "attn"
         cls_mean = arch.get("pool") == "cls_mean"          # [class token | mean of the patch tokens] (midnight.py:58-61)
@@ -633,51 +631,20 @@ class HipViT:
                              int(arch.get("proj_dim", 0)), 1 if arch.get("rope") else 0)
         state = pad_heads(state, dim=arch["dim"], heads=arch["heads"], depth=arch["depth"])
         state = pad_mlp(state, mlp_dim=arch["mlp_dim"], depth=arch["depth"], swiglu=arch.get("mlp") == "swiglu")
-        handle = C.c_void_p()
-        # hipMalloc / hipMemcpy on the legacy stream must not fall into another thread's stream capture (the SAM2 hipGraph):
-        # both sides hold _lib.HIP_CAPTURE_LOCK for their device section
-        with _lib.HIP_CAPTURE_LOCK, torch.cuda.device(self.device):
-            _lib.check(self.lib.ap_vit_create(C.byref(cfg), C.byref(handle)), "ap_vit_create")
-            self._handle = handle
-            # one native call for the whole checkpoint: the uploads run outside the interpreter lock (the encoder is built
-            # on a side thread while the CLI's phase 1 runs)
-            arrs = [np.ascontiguousarray(t.detach().to(torch.float32).cpu().numpy()) for t in state.values()]
-            n = len(arrs)
-            names = (C.c_char_p * n)(*[k.encode() for k in state])
-            ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
-            counts = (C.c_size_t * n)(*[a.size for a in arrs])
-            _lib.check(self.lib.ap_vit_set_params(self._handle, names, ptrs, counts, n), "ap_vit_set_params")
-            del arrs
-            _lib.check(self.lib.ap_vit_finalize(self._handle), "ap_vit_finalize")
-        self._workspace: Optional[torch.Tensor] = None
+        self._open(cfg, state)
 
-    def _ws(self, n: int) -> torch.Tensor:
-        need = int(self.lib.ap_vit_workspace_bytes(self._handle, n))
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = None
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._workspace
-
-    def forward_u8(self, tiles: torch.Tensor, mean, std, out: torch.Tensor) -> torch.Tensor:
-        """tiles: uint8 [n, H, W, 3] on the device; out: float32 [n, D] on the device (written)."""
-        if self._handle is None:
-            raise _lib.HipLibraryError("HipViT used after release()")
-        assert tiles.dtype == torch.uint8 and tiles.is_contiguous() and tiles.dim() == 4 and tiles.shape[3] == 3
-        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (tiles.shape[0], self.embed_dim)
-        n, h, w, _ = tiles.shape
-        if n == 0:
-            return out
-        ws = self._ws(n)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.ap_vit_forward_u8(self._handle, tiles.data_ptr(), n, h, w, _lib.f3(mean), _lib.f3(std),
-                                                  out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                  _lib.current_stream_ptr(self.device)), "ap_vit_forward_u8")
-        return out
+    def _upload(self, arrs: dict) -> None:
+        # one native call for the whole checkpoint: the uploads run outside the interpreter lock (the encoder is built on a
+        # side thread while the CLI's phase 1 runs)
+        n = len(arrs)
+        names = (C.c_char_p * n)(*[k.encode() for k in arrs])
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs.values()])
+        counts = (C.c_size_t * n)(*[a.size for a in arrs.values()])
+        _lib.check(self.lib.ap_vit_set_params(self._handle, names, ptrs, counts, n), "ap_vit_set_params")
 
     def forward_chw(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x: [n, 3, S, S] float32 or compute dtype, already normalised."""
-        if self._handle is None:
-            raise _lib.HipLibraryError("HipViT used after release()")
+        self._live()
         assert x.is_contiguous() and x.dim() == 4
         n = x.shape[0]
         if out is None:
@@ -705,30 +672,6 @@ class HipViT:
         value = int(on) if not isinstance(on, bool) else (1 if on else 0)
         _lib.check(self.lib.ap_vit_set_option(self._handle, self.OPTIONS[name], value), "ap_vit_set_option")
 
-    def profile(self, on: bool) -> None:
-        _lib.check(self.lib.ap_vit_profile_enable(self._handle, 1 if on else 0), "ap_vit_profile_enable")
-
-    def profile_read(self) -> dict:
-        """{kind: (milliseconds, launches)} accumulated since the last read (HIP events)."""
-        k = len(_lib.PROF_KINDS)
-        ms = (C.c_double * k)()
-        cnt = (C.c_longlong * k)()
-        _lib.check(self.lib.ap_vit_profile_read(self._handle, ms, cnt, k), "ap_vit_profile_read")
-        return {name: (float(ms[i]), int(cnt[i])) for i, name in enumerate(_lib.PROF_KINDS)}
-
-    def release(self) -> None:
-        if getattr(self, "_handle", None) is not None:
-            torch.cuda.synchronize(self.device)
-            self.lib.ap_vit_destroy(self._handle)
-            self._handle = None
-            self._workspace = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.release()
-        except Exception:
-            pass
-
 
 # ----------------------------------------------------------------------------- builders
 def weights_path(name: str) -> Optional[Path]:
@@ -754,26 +697,49 @@ def load_checkpoint(path: Path) -> dict:
     return obj
 
 
+def resolve_weights(name: str, state_dict: Optional[dict], random_init_seed: Optional[int], random_init,
+                    key_families: str) -> tuple[dict, bool]:
+    """(checkpoint, seeded) for the model ``name``: ``state_dict`` if given, else ``$ATLASPATCH_WEIGHTS_DIR/<name>.*``, else
+    ``random_init(random_init_seed)`` -- seeded random weights in canonical form (``seeded`` True) -- when a seed is given.
+    ``key_families``: the checkpoint layouts the model takes, named in the error when there is none of the three."""
+    if state_dict is not None:
+        return state_dict, False
+    path = weights_path(name)
+    if path is not None:
+        return load_checkpoint(path), False
+    if random_init_seed is not None:
+        logger.warning("%s: using seeded RANDOM weights (seed %d); features are not meaningful", name, random_init_seed)
+        return random_init(random_init_seed), True
+    raise FileNotFoundError(
+        f"No weights for '{name}': set ATLASPATCH_WEIGHTS_DIR to a directory holding {name}.safetensors/.pt "
+        f"({key_families} key names), or set ATLASPATCH_RANDOM_INIT=<seed> for seeded random weights (benchmarks/tests).")
+
+
+def check_canonical(out: dict, want: dict, unknown: list, *, family: str, source: str) -> dict:
+    """``out`` (canonical key -> tensor) against ``want`` (canonical key -> shape): a ``ValueError`` for checkpoint keys that
+    mapped to no canonical key (``unknown``), then for missing keys, then for wrong shapes; else ``out``."""
+    if unknown:
+        raise ValueError(f"{family} checkpoint ({source} layout): {len(unknown)} unknown key(s) for this architecture, e.g. "
+                         f"{unknown[:5]}")
+    missing = [k for k in want if k not in out]
+    if missing:
+        raise ValueError(f"{family} checkpoint ({source} layout): {len(missing)} missing key(s), e.g. {missing[:5]}")
+    for k, shape in want.items():
+        if tuple(out[k].shape) != shape:
+            raise ValueError(f"{family} checkpoint: {k} has shape {tuple(out[k].shape)}, expected {shape}")
+    return out
+
+
 def build_hip_vit_extractor(*, name: str, arch, device, dtype, state_dict: Optional[dict] = None,
                             mean=None, std=None, source: str = "auto", max_batch: int = 1024,
                             random_init_seed: Optional[int] = None, resize=None,
                             expect_size: Optional[int] = 256, **arch_overrides) -> HipViTFeatureExtractor:
     spec = dict(ARCHS[arch]) if isinstance(arch, str) else dict(arch)
     spec.update(arch_overrides)
-    if state_dict is None:
-        path = weights_path(name)
-        if path is not None:
-            state_dict = load_checkpoint(path)
-        elif random_init_seed is not None:
-            logger.warning("%s: using seeded RANDOM weights (seed %d); features are not meaningful",
-                           name, random_init_seed)
-            state_dict = random_canonical_state_dict(spec, random_init_seed)
-            source = "canonical"
-        else:
-            raise FileNotFoundError(
-                f"No weights for '{name}': set ATLASPATCH_WEIGHTS_DIR to a directory holding "
-                f"{name}.safetensors/.pt (torchvision, timm or HF ViT key names), or set "
-                "ATLASPATCH_RANDOM_INIT=<seed> for seeded random weights (benchmarks/tests).")
+    state_dict, seeded = resolve_weights(name, state_dict, random_init_seed, lambda seed: random_canonical_state_dict(spec, seed),
+                                         "torchvision, timm or HF ViT")
+    if seeded:
+        source = "canonical"
     pool_state = None
     if spec.get("pool") == "attn" and source != "canonical":
         if any(k.startswith("visual.trunk.") for k in state_dict):          # a CONCH checkpoint

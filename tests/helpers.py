@@ -1,8 +1,10 @@
-"""Shared test helpers (inputs that reproduce the golden generator's seeds)."""
+"""Shared test helpers (inputs that reproduce the golden generator's seeds; the convolutional encoders' GPU tests)."""
+import functools
 import json
 import os
 
 import numpy as np
+import torch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -67,3 +69,39 @@ def canonical_to_hf(sd, depth):
                    p + "mlp.fc1.weight": sd[b + "fc1.weight"], p + "mlp.fc1.bias": sd[b + "fc1.bias"],
                    p + "mlp.fc2.weight": sd[b + "fc2.weight"], p + "mlp.fc2.bias": sd[b + "fc2.bias"]})
     return hf
+
+
+# ----------------------------------------------------------------------------- convolutional encoders (GPU tests)
+DT = {"float32": (torch.float32, 0), "float16": (torch.float16, 1), "bfloat16": (torch.bfloat16, 2)}
+
+
+def _record(env, key, value):
+    """Record a measured error under ``key`` in the JSON file named by the environment variable ``env`` (bound updates)."""
+    path = os.environ.get(env)
+    if path:
+        data = json.load(open(path)) if os.path.exists(path) else {}
+        data[key] = value
+        json.dump(data, open(path, "w"), indent=1, sort_keys=True)
+
+
+def _rel(got, want):
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    return float(np.linalg.norm(got - want) / max(np.linalg.norm(want), 1e-30))
+
+
+def _lib():
+    from atlaspatch_amd import _lib as lib
+    return lib, lib.load()
+
+
+def _tiles(count, size=256, seed=0):
+    from atlaspatch_amd.core.wsi.synth_pixels import SynthSpec, render_region
+    spec = SynthSpec(width=20000, height=20000, seed=seed)
+    rng = np.random.default_rng(seed)
+    xs = rng.integers(0, 20000 - size, (count, 2))
+    return [render_region(spec, int(x), int(y), size, size, 0) for x, y in xs]
+
+
+@functools.lru_cache(maxsize=None)
+def _tiles33():
+    return _tiles(33)

@@ -5,7 +5,6 @@ batch-cut invariance, the device resize of a 512-px tile, and `process` with the
 Bounds: float32 products are exact f32 MFMA chains / f32 FMAs (bound 1e-5 everywhere).  float16 / bfloat16 network bounds are
 the first MI355X run's measured error x 1.2 (the measured value is next to each bound)."""
 import json
-import os
 
 import numpy as np
 import pytest
@@ -13,10 +12,10 @@ import torch
 import torch.nn.functional as F
 
 from tests import convnext_reference as ref
+from tests.helpers import DT, _lib, _record, _rel, _tiles, _tiles33
 
 pytestmark = pytest.mark.gpu
 
-DT = {"float32": (torch.float32, 0), "float16": (torch.float16, 1), "bfloat16": (torch.bfloat16, 2)}
 # one operator: the output's rounding to T (and a 1-ulp different rounding of an intermediate) is the error
 OP_TOL = {"float32": 1e-5, "float16": 1e-3, "bfloat16": 8e-3}
 # network features against the CPU float32 restatement (measured on the first MI355X run; bound = measured x 1.2)
@@ -24,25 +23,8 @@ NET_TOL = {("convnext_tiny", "float32"): 1e-5,                                  
            ("convnext_tiny", "float16"): 6.7e-4, ("convnext_tiny", "bfloat16"): 5.5e-3,       # measured 5.58e-4 / 4.62e-3
            ("convnext_small", "float16"): 7.2e-4, ("convnext_base", "float16"): 7.3e-4,       # measured 5.99e-4 / 6.11e-4
            ("convnext_large", "float16"): 7.2e-4}                                             # measured 5.97e-4
-MEASURED = os.environ.get("ATLASPATCH_CONVNEXT_MEASURED")      # optional path: record the measured errors (bound updates)
+MEASURED = "ATLASPATCH_CONVNEXT_MEASURED"      # optional: names the path to record the measured errors in (bound updates)
 EPS = 1e-6
-
-
-def _record(key, value):
-    if MEASURED:
-        data = json.load(open(MEASURED)) if os.path.exists(MEASURED) else {}
-        data[key] = value
-        json.dump(data, open(MEASURED, "w"), indent=1, sort_keys=True)
-
-
-def _rel(got, want):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    return float(np.linalg.norm(got - want) / max(np.linalg.norm(want), 1e-30))
-
-
-def _lib():
-    from atlaspatch_amd import _lib as lib
-    return lib, lib.load()
 
 
 def _dw_shapes():
@@ -154,14 +136,6 @@ def test_conv2d_ex_refuses_bad_arguments():
 
 
 # ----------------------------------------------------------------------------- full networks
-def _tiles(count, size=256, seed=0):
-    from atlaspatch_amd.core.wsi.synth_pixels import SynthSpec, render_region
-    spec = SynthSpec(width=20000, height=20000, seed=seed)
-    rng = np.random.default_rng(seed)
-    xs = rng.integers(0, 20000 - size, (count, 2))
-    return [render_region(spec, int(x), int(y), size, size, 0) for x, y in xs]
-
-
 _REF_CACHE = {}
 
 
@@ -188,16 +162,6 @@ def _extractor(arch, dtype_name, **kw):
                                         state_dict=_canonical(arch), **kw)
 
 
-TILES33 = None
-
-
-def _tiles33():
-    global TILES33
-    if TILES33 is None:
-        TILES33 = _tiles(33)
-    return TILES33
-
-
 @pytest.mark.parametrize("dtype_name", ["float32", "float16", "bfloat16"])
 def test_convnext_tiny_against_the_restatement(dtype_name):
     arch = "convnext_tiny"
@@ -214,7 +178,7 @@ def test_convnext_tiny_against_the_restatement(dtype_name):
             rel = _rel(got, want_all[:n])
             worst = max(worst, rel)
             assert rel <= NET_TOL[(arch, dtype_name)], (n, rel)
-        _record(f"{arch}/{dtype_name}", worst)
+        _record(MEASURED, f"{arch}/{dtype_name}", worst)
         # the same rows whatever the batch cut: 33 tiles in one call == three calls, bit for bit
         whole = ex.extract_batch(tiles)
         parts = np.concatenate([ex.extract_batch(tiles[i:i + 11]) for i in (0, 11, 22)])
@@ -233,7 +197,7 @@ def test_deep_convnexts_float16(arch):
     finally:
         ex.cleanup()
     rel = _rel(got, want)
-    _record(f"{arch}/float16", rel)
+    _record(MEASURED, f"{arch}/float16", rel)
     from atlaspatch_amd.encoders.convnext import ARCHS
     assert got.shape == (5, ARCHS[arch]["embed_dim"]) and rel <= NET_TOL[(arch, "float16")], rel
 

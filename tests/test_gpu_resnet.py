@@ -5,7 +5,6 @@ full networks against the CPU restatement (tests/resnet_reference.py), batch-cut
 Bounds: float32 products are exact f32 MFMA chains (bound 1e-5 everywhere).  float16 / bfloat16 network bounds are the
 first MI355X run's measured error x 1.2 (the measured value is next to each bound)."""
 import json
-import os
 
 import numpy as np
 import pytest
@@ -13,10 +12,10 @@ import torch
 import torch.nn.functional as F
 
 from tests import resnet_reference as ref
+from tests.helpers import DT, _lib, _record, _rel, _tiles, _tiles33
 
 pytestmark = pytest.mark.gpu
 
-DT = {"float32": (torch.float32, 0), "float16": (torch.float16, 1), "bfloat16": (torch.bfloat16, 2)}
 # element-type rounding of the stored output is the only error of one convolution besides f32 summation order
 CONV_TOL = {"float32": 1e-5, "float16": 1e-3, "bfloat16": 8e-3}
 # network features against the CPU float32 restatement (measured on the first MI355X run; bound = measured x 1.2)
@@ -24,19 +23,7 @@ NET_TOL = {("resnet18", "float32"): 1e-5, ("resnet50", "float32"): 1e-5,        
            ("resnet18", "float16"): 1.05e-3, ("resnet50", "float16"): 9.8e-4,             # measured 8.76e-4 / 8.20e-4
            ("resnet18", "bfloat16"): 1.34e-2, ("resnet50", "bfloat16"): 9.0e-3,           # measured 1.115e-2 / 7.50e-3
            ("resnet101", "float16"): 1.1e-3, ("resnet152", "float16"): 6.3e-4}            # measured 9.16e-4 / 5.23e-4
-MEASURED = os.environ.get("ATLASPATCH_RESNET_MEASURED")      # optional path: record the measured errors (bound updates)
-
-
-def _record(key, value):
-    if MEASURED:
-        data = json.load(open(MEASURED)) if os.path.exists(MEASURED) else {}
-        data[key] = value
-        json.dump(data, open(MEASURED, "w"), indent=1, sort_keys=True)
-
-
-def _rel(got, want):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    return float(np.linalg.norm(got - want) / max(np.linalg.norm(want), 1e-30))
+MEASURED = "ATLASPATCH_RESNET_MEASURED"      # optional: names the path to record the measured errors in (bound updates)
 
 
 def _layer_shapes():
@@ -67,11 +54,6 @@ def _layer_shapes():
 
 
 SHAPES = _layer_shapes()
-
-
-def _lib():
-    from atlaspatch_amd import _lib as lib
-    return lib, lib.load()
 
 
 def _conv(dtype_name, x, w, b, stride, pad, resid=None, relu=False):
@@ -151,14 +133,6 @@ def test_maxpool_and_avgpool(hw, c, n, dtype_name):
 
 
 # ----------------------------------------------------------------------------- full networks
-def _tiles(count, size=256, seed=0):
-    from atlaspatch_amd.core.wsi.synth_pixels import SynthSpec, render_region
-    spec = SynthSpec(width=20000, height=20000, seed=seed)
-    rng = np.random.default_rng(seed)
-    xs = rng.integers(0, 20000 - size, (count, 2))
-    return [render_region(spec, int(x), int(y), size, size, 0) for x, y in xs]
-
-
 _REF_CACHE = {}
 
 
@@ -185,16 +159,6 @@ def _extractor(arch, dtype_name, **kw):
                                       state_dict=_canonical(arch), **kw)
 
 
-TILES33 = None
-
-
-def _tiles33():
-    global TILES33
-    if TILES33 is None:
-        TILES33 = _tiles(33)
-    return TILES33
-
-
 @pytest.mark.parametrize("dtype_name", ["float32", "float16", "bfloat16"])
 @pytest.mark.parametrize("arch", ["resnet18", "resnet50"])
 def test_extract_batch_full_depth_against_the_restatement(arch, dtype_name):
@@ -212,7 +176,7 @@ def test_extract_batch_full_depth_against_the_restatement(arch, dtype_name):
             rel = _rel(got, want_all[:n])
             worst = max(worst, rel)
             assert rel <= NET_TOL[(arch, dtype_name)], (n, rel)
-        _record(f"{arch}/{dtype_name}", worst)
+        _record(MEASURED, f"{arch}/{dtype_name}", worst)
         # the same rows whatever the batch cut: 33 tiles in one call == three calls, bit for bit
         whole = ex.extract_batch(tiles)
         parts = np.concatenate([ex.extract_batch(tiles[i:i + 11]) for i in (0, 11, 22)])
@@ -231,7 +195,7 @@ def test_extract_batch_deep_bottlenecks_float16(arch):
     finally:
         ex.cleanup()
     rel = _rel(got, want)
-    _record(f"{arch}/float16", rel)
+    _record(MEASURED, f"{arch}/float16", rel)
     assert got.shape == (5, 2048) and rel <= NET_TOL[(arch, "float16")], rel
 
 

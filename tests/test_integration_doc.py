@@ -216,6 +216,38 @@ def test_vit_create_never_reads_past_the_declared_size(lib):
     assert lib.ap_vit_config_init(None, full) == _lib.AP_ERR_INVALID
 
 
+def test_conv_engines_take_only_sizes_their_config_has_had(lib):
+    """ap_resnet_create / ap_convnext_create and their *_config_init: the same hand-over as ap_vit_create, except that any
+    multiple of 4 past the library's size (up to 4096 bytes) counts as a newer caller.  Each buffer below is exactly as long
+    as a v20 structure, and every refusal comes before any HIP call."""
+    from atlaspatch_amd import _lib
+    for family, config, v20 in (("resnet", _lib.ResnetConfig, 36), ("convnext", _lib.ConvnextConfig, 44)):
+        full = getattr(lib, f"ap_sizeof_{family}_config")()
+        assert full == C.sizeof(config) == v20
+        raw = bytes(config())
+
+        def create(size):
+            buf = C.create_string_buffer(int(size).to_bytes(4, "little") + raw[4:], len(raw))
+            h = C.c_void_p()
+            rc = getattr(lib, f"ap_{family}_create")(C.cast(buf, C.POINTER(config)), C.byref(h))
+            assert rc != 0 and not h.value, (family, size, rc)
+            return rc, lib.ap_last_error().decode()
+
+        for bad in (0, 4, v20 - 4, v20 - 1, v20 + 2, v20 + 6, 4097, 4100, 8192, 1 << 20):
+            rc, msg = create(bad)
+            assert rc == _lib.AP_ERR_INVALID and "struct_size" in msg, (family, bad, rc, msg)
+        for newer in (v20 + 8, v20 + 400, 4096):
+            rc, msg = create(newer)
+            assert rc == _lib.AP_ERR_UNSUPPORTED and "newer" in msg, (family, newer, rc, msg)
+        init = getattr(lib, f"ap_{family}_config_init")
+        cfg = config()
+        cfg.compute_dtype = 2
+        assert init(C.byref(cfg), C.sizeof(cfg)) == 0 and cfg.struct_size == full and cfg.compute_dtype == 0
+        for bad in (0, 4, v20 - 4, v20 + 2):
+            assert init(C.byref(cfg), bad) == _lib.AP_ERR_INVALID, (family, bad)
+        assert init(None, full) == _lib.AP_ERR_INVALID
+
+
 # ----------------------------------------------------------------------------- GPU: the plugin of section 2.1, as written
 def _plugin_source():
     for block in doc_blocks():
