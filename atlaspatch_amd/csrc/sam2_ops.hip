@@ -82,10 +82,14 @@ __global__ __launch_bounds__(256) void sgemm_mfma_kernel(SgemmArgs g) {
             int gr = row0 + r;
             gr = gr < rows ? gr : rows - 1;
             const float* p = base + (size_t)gr * ld;
-            if constexpr (VEC) {                      // K % 4 == 0: a float4 is wholly inside or wholly outside [kbeg, kend)
-                const bool ok = k < kend;
+            if constexpr (VEC) {                      // ld % 4 == 0: the float4 at k < kend lies inside the row's ld elements.
+                // K % 4 == 0 (always, for NT weights): it is wholly inside or wholly outside [kbeg, kend).  The A of an NN
+                // product may have K % 4 != 0: the elements of the last float4 at and past kend (row padding, possibly
+                // NaN) are masked one by one.
+                const int rem = kend - k;
+                const bool ok = rem > 0;
                 dst[j] = *(const f32x4*)(p + (ok ? k : kbeg));
-                msk[j] = ok ? 15u : 0u;
+                msk[j] = rem >= 4 ? 15u : (ok ? (1u << rem) - 1u : 0u);
             } else {
                 unsigned m = 0;
 #pragma unroll

@@ -105,3 +105,26 @@ def _tiles(count, size=256, seed=0):
 @functools.lru_cache(maxsize=None)
 def _tiles33():
     return _tiles(33)
+
+
+U_T = {"float32": 2.0 ** -24, "float16": 2.0 ** -11, "bfloat16": 2.0 ** -8}      # unit roundoff of the stored type
+
+
+def _conv_bound_ratio(got, x, w, b, stride, pad, resid, act, dtype_name):
+    """max over the elements of |got - ref| / bound; got [n, cout, ho, wo]; x, w, resid are the T-rounded CPU operands (NCHW)."""
+    import torch.nn.functional as F
+    x64, w64, b64 = x.double(), w.double(), b.double()
+    ref = F.conv2d(x64, w64, b64, stride=stride, padding=pad)
+    mag = F.conv2d(x64.abs(), w64.abs(), b64.abs(), stride=stride, padding=pad)
+    if resid is not None:
+        ref = ref + resid.double()
+        mag = mag + resid.double().abs()
+    extra = 0.0
+    if act == 1:
+        ref = F.relu(ref)
+    elif act == 2:
+        ref = F.gelu(ref)
+        extra = 3e-5
+    K = w[0].numel()
+    bound = (K + 4) * 2.0 ** -24 * mag + U_T[dtype_name] * ref.abs() * 1.001 + extra
+    return float(((got.double() - ref).abs() / bound.clamp_min(1e-300)).max())

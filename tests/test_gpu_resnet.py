@@ -12,7 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import resnet_reference as ref
-from tests.helpers import DT, _lib, _record, _rel, _tiles, _tiles33
+from tests.helpers import DT, _conv_bound_ratio, _lib, _record, _rel, _tiles, _tiles33
 
 pytestmark = pytest.mark.gpu
 
@@ -70,7 +70,7 @@ def _conv(dtype_name, x, w, b, stride, pad, resid=None, relu=False):
     return out
 
 
-def _conv_case(dtype_name, k, stride, cin, cout, h, n, resid, relu, seed=0):
+def _conv_case(dtype_name, k, stride, cin, cout, h, n, resid, relu, seed=0, elementwise=False):
     dt = DT[dtype_name][0]
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(n, cin, h, h, generator=g).to(dt)
@@ -87,14 +87,18 @@ def _conv_case(dtype_name, k, stride, cin, cout, h, n, resid, relu, seed=0):
     dev = torch.device("cuda")
     got = _conv(dtype_name, x.permute(0, 2, 3, 1).contiguous().to(dev), w.permute(0, 2, 3, 1).contiguous().to(dev), b.to(dev),
                 stride, pad, r.permute(0, 2, 3, 1).contiguous().to(dev) if r is not None else None, relu)
-    return _rel(got.float().cpu().permute(0, 3, 1, 2), want)
+    got = got.float().cpu().permute(0, 3, 1, 2)
+    if elementwise:                 # the sharper check: every element inside the derived bound (tests/helpers.py::_conv_bound_ratio)
+        ratio = _conv_bound_ratio(got, x, w, b, stride, pad, r, 1 if relu else 0, dtype_name)
+        assert ratio <= 1.0, ratio
+    return _rel(got, want)
 
 
 @pytest.mark.parametrize("dtype_name", ["float32", "float16", "bfloat16"])
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "k%d_s%d_cin%d_cout%d_h%d" % s)
 def test_conv2d_every_layer_shape(shape, dtype_name):
     k, stride, cin, cout, h = shape
-    rel = _conv_case(dtype_name, k, stride, cin, cout, h, n=1, resid=False, relu=False)
+    rel = _conv_case(dtype_name, k, stride, cin, cout, h, n=1, resid=False, relu=False, elementwise=True)
     assert rel <= CONV_TOL[dtype_name], rel
 
 

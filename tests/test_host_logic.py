@@ -833,3 +833,34 @@ def test_env_flag_zero_never_switches_a_feature_on(monkeypatch):
         src = inspect.getsource(mod)
         assert 'env_flag("ATLASPATCH_GATHER_FEATURES")' in src and 'os.environ.get("ATLASPATCH_GATHER_FEATURES")' not in src
 
+
+
+# ----------------------------------------------------------------------------- every exported kernel has a GPU test
+# Exported `int ap_*(` names that need no mention in a GPU test source, each with its reason (full-match patterns).
+_NO_OPERATOR_TEST = [
+    (r"ap_abi_version", "library lifecycle: _lib.load() refuses a library that reports another ABI"),
+    (r"ap_device_info", "host query of the runtime, no kernel"),
+    (r"ap_host_\w+", "host-only entry points (tile ring, passports, OpenSlide): no device work; CPU tests call them"),
+    (r"ap_(vit|resnet|convnext)_\w+", "engine object lifecycle / forward: driven through the Python engines by the network tests"),
+    (r"ap_gemm_trace", "diagnostic switch of the instrumented GEMM twin, which is not in the product library"),
+    (r"ap_pillow_reduce_u8", "called through utils.resample.pillow_reduce_device, which test_segmentation_device.py checks against Pillow"),
+    (r"ap_tile_content_counts", "called through utils.image, which test_gpu_ops.py checks against the cv2 restatement"),
+    (r"ap_contours_\w+|ap_grid_coords", "called through utils.contours by services.extraction.coords_from_mask (test_gpu_parity.py)"),
+]
+
+
+def test_every_exported_kernel_is_named_in_a_gpu_test():
+    """A new `int ap_*(` in include/atlaspatch_hip.h must occur in a tests/test_gpu*.py or tests/test_*device*.py source (an
+    operator-level test through the C ABI) or be listed above with its reason."""
+    import glob
+    header = open(os.path.join(ROOT, "include", "atlaspatch_hip.h")).read()
+    names = sorted(set(re.findall(r"^int\s+(ap_\w+)\s*\(", header, re.M)))
+    assert len(names) >= 80 and "ap_sgemm" in names and "ap_gather2d_f32" in names, len(names)
+    paths = sorted(set(glob.glob(os.path.join(ROOT, "tests", "test_gpu*.py")) + glob.glob(os.path.join(ROOT, "tests", "test_*device*.py"))))
+    assert len(paths) >= 5
+    text = "\n".join(open(p).read() for p in paths)
+    used = set(re.findall(r"\bap_\w+", text))
+    missing = [n for n in names if n not in used and not any(re.fullmatch(p, n) for p, _ in _NO_OPERATOR_TEST)]
+    assert not missing, f"exported without a GPU operator test: {missing}"
+    for pattern, reason in _NO_OPERATOR_TEST:
+        assert reason and any(re.fullmatch(pattern, n) for n in names), f"stale allow-list entry {pattern}"
