@@ -6,19 +6,24 @@
 // never drains: while a tile's epilogue runs, the LDS-DMA for the next tile's first K-tiles is
 // already in flight.
 //
-//  * waves: 8 = 2 (wr, along m) x 4 (wc, along n); a wave owns 128 m x 64 n = 4 x 2 MFMA tiles of
-//    32x32 (v_mfma_f32_32x32x16_{f16,bf16}; 128 accumulator registers).  The MFMA "A" operand is the
-//    weight fragment so a lane ends up with 4 consecutive n of one m.
+//  * waves: 8 = 2 (wr, along m) x 4 (wc, along n); a wave owns 128 m x 64 n = 8 x 4 MFMA blocks of
+//    16x16 (v_mfma_f32_16x16x32_{f16,bf16}; 128 accumulator registers).  The MFMA "A" operand is the
+//    weight fragment so a lane ends up with 4 consecutive n of one m (AccMap, gemm_mma.h).  The shape is
+//    chosen for the clock, not for cycles: on MI355X this power-capped loop holds a higher shader clock on
+//    16x16x32 than on 32x32x16 at the same pipe cycles per FLOP (tools/isa_probes/mfma_shape_probe.hip:
+//    1.14x in the bare fragment-read + MFMA loop; 1.03-1.07x on the four ViT-B shapes here), and the f32 accumulators
+//    of the two shapes are bit-identical in ascending k, so the 128x128 kernel (gemm.hip, 32x32x16) still
+//    agrees with this one bit for bit.
 //  * LDS (160 KiB): two K-tile buffers of 64 KiB + 8 x 4 KiB per-wave epilogue scratch.  A buffer
 //    holds four 16-KiB staging UNITS of 128 rows x 128 B, cut along the waves' output QUADRANTS
 //    rather than along the tile:  X0 / X1 = the first / second 64 m-rows of both wr groups,
 //    Y0 / Y1 = the first / second 32 n-rows of all four wc groups.  A K-tile is consumed in four
-//    phases  (X0,Y0) (X0,Y1) (X1,Y1) (X1,Y0)  of 8 MFMAs per wave, so every unit has ONE reading
+//    phases  (X0,Y0) (X0,Y1) (X1,Y1) (X1,Y0)  of 16 MFMAs per wave (64 m x 32 n x 64 k), so every unit has ONE reading
 //    phase (Y0's fragment stays in registers for phase 3).  That makes a unit free two phases
 //    after it was read and lets a plain double buffer run ~4 phases (a whole K-tile) of prefetch:
 //        phase 0: read X0,Y0   stage Y1 of K-tile v+1      phase 2: read X1   stage X0 of v+2
 //        phase 1: read Y1      stage X1 of K-tile v+1      phase 3: -         stage Y0 of v+2
-//    A phase is  s_waitcnt vmcnt(6); s_barrier; [8 MFMAs with the phase's unit staged between them: 2 x
+//    A phase is  s_waitcnt vmcnt(6); s_barrier; [16 MFMAs with the phase's unit staged between them: 2 x
 //    global_load_lds_dwordx4 per lane -- and, since round 5, the NEXT phase's fragment reads].  vmcnt(6) = "everything staged four
 //    phases ago has landed"; data is read no earlier than behind the barrier that follows the wait that retires it
 //    (round 2-4's loop: one phase later) and a unit is restaged no earlier than one barrier after its reading phase (raw s_barrier,
@@ -45,7 +50,9 @@
 //    statistics.  RESID_STATS / PATCH_STREAM fetch their operands (bias, the 128 x 64 stream window) with plain loads +
 //    __builtin_amdgcn_s_waitcnt before the epilogue body; the NORM epilogues' operands arrive in the wave's idle scratch by
 //    LDS-DMA during the tile's K loop and the drain sits in front of the tile's first store (round 5, see kLdsOps below).
-//  * round 5: the fragment reads of a phase are issued between the MFMAs of the phase BEFORE it (ktile_p below); 16-bit
+//  * round 5: the fragment reads of a phase are issued between the MFMAs of the phase BEFORE it (ktile_p below; every
+//    instantiation, EPI_PATCH_STREAM included: with two 32-deep k-steps per K-tile the loop keeps 8 fragment addresses
+//    instead of 16 and no instantiation spills); 16-bit
 //    plain-store epilogues write their rows with the non-temporal hint (out_store16).
 //  * XCD-aware tile order: block b runs on XCD b % 8; each XCD owns a contiguous range of tile ids
 //    (n fastest), its 32 workgroups take consecutive ids, so concurrently running tiles share
@@ -142,7 +149,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wr = wave >> 2, wc = wave & 3;
-    const int hi = lane >> 5, l31 = lane & 31;
+    const AccMap am(lane);
     using Frag = typename Mma<T>::Frag;
 
     // ---- tile list (XCD-aware, see header)
@@ -223,24 +230,26 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
     set_tile(cb, 1, 0);
 
     // ---- fragment read addresses (byte offsets into a buffer)
-    const int xr = (l31 >> 1) & 7;
-    int pa[4], pb[4];
+    //      operand map of the 16x16x32 MFMA: lane l holds row l & 15, k = 32 kk + 8 (l >> 4) + j, j = 0..7 = 16-byte chunk
+    //      4 kk + (l >> 4) of the 128-byte row; block bases are multiples of 16 rows, so the swizzle depends on l & 15 alone
+    const int xr = (am.l15 >> 1) & 7;
+    int pa[2], pb[2];
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-        const int co = ((kk * 2 + hi) ^ xr) << 4;
-        pa[kk] = (wr * 64 + l31) * kRowBytes + co;          // + unit * 16K + rb * 32 rows
-        pb[kk] = (wc * 32 + l31) * kRowBytes + co;
+    for (int kk = 0; kk < 2; ++kk) {
+        const int co = ((kk * 4 + am.q) ^ xr) << 4;
+        pa[kk] = (wr * 64 + am.l15) * kRowBytes + co;       // + unit * 16K + block * 16 rows
+        pb[kk] = (wc * 32 + am.l15) * kRowBytes + co;
     }
 
-    // Accumulators start from the bias (lane's 32 n values, the same for its four m blocks), so the
+    // Accumulators start from the bias (lane's 16 n values, the same for its eight m rows), so the
     // epilogue has no bias pass; the next tile's bias is fetched while the current epilogue runs.
-    f32x16 acc[2][4];         // [n block of 32][m block of 32]
-    f32x4 nbias[2][4];
+    f32x4 acc[2][4][4];       // [n block of 32][m block of 32][16 x 16 block nh * 2 + mh], lane -> (m, n): AccMap (gemm_mma.h)
+    f32x4 nbias[2][2];        // [n block of 32][nh]: the lane's 4 consecutive n of that block
     // fused-LayerNorm epilogues (EPI_NORM_*): the accumulators start from zero, and the CURRENT tile's bias (in nbias),
     // column sums and row statistics are requested before the drain that opens its epilogue
-    f32x4 ncs[2][4];
+    f32x4 ncs[2][2];
     typedef float f32x2 __attribute__((ext_vector_type(2)));
-    f32x2 rst[4];
+    f32x2 rst[4][2];          // [m block of 32][mh]
     u32x4 res[16];            // EPI_RESID_STATS: the wave's 128 x 64 window of the stream, row-major 16 B per lane
     u32x2 pk[2][4][4];        //   and the accumulators rounded to T ([n block][m block][group of 4 n])
     // The bias loads are inline asm with hand-placed waits.  A load hipcc tracks that is still pending at the
@@ -251,35 +260,35 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
     // epilogue's stores let a late bias load slip through about once in 10^5 tiles: one or two wrong images per
     // few hundred forwards).  The next tile's bias is therefore requested just before the drain that opens the
     // epilogue (the main loop's 64 fragment registers are free by then) and is complete when the drain returns.
-    auto bias_ptr = [&](int ti, int hi_) {
+    auto bias_ptr = [&](int ti, int q_) {
         int tr, tc;
         tw.rc(tw.first + ti * tw.stride, tr, tc);
-        return g.bias + tc * kBN + wc * 64 + hi_ * 4;
+        return g.bias + tc * kBN + wc * 64 + q_ * 4;
     };
-#define AP_BIAS_LD(P, NB, G4) \
-    asm volatile("global_load_dwordx4 %0, %1, off offset:" #NB "*128+" #G4 "*32" : "=&v"(nbias[NB][G4]) : "v"(P) : "memory")
-#define AP_BIAS_LD8(P)                                                                  \
-    AP_BIAS_LD(P, 0, 0); AP_BIAS_LD(P, 0, 1); AP_BIAS_LD(P, 0, 2); AP_BIAS_LD(P, 0, 3); \
-    AP_BIAS_LD(P, 1, 0); AP_BIAS_LD(P, 1, 1); AP_BIAS_LD(P, 1, 2); AP_BIAS_LD(P, 1, 3)
-#define AP_BIAS_WAIT(N)                                                                                           \
-    asm volatile("s_waitcnt vmcnt(" #N ")"                                                                        \
-                 : "+v"(nbias[0][0]), "+v"(nbias[0][1]), "+v"(nbias[0][2]), "+v"(nbias[0][3]), "+v"(nbias[1][0]), \
-                   "+v"(nbias[1][1]), "+v"(nbias[1][2]), "+v"(nbias[1][3])::"memory")
+#define AP_BIAS_LD(P, NB, NH) \
+    asm volatile("global_load_dwordx4 %0, %1, off offset:" #NB "*128+" #NH "*64" : "=&v"(nbias[NB][NH]) : "v"(P) : "memory")
+#define AP_BIAS_LD4(P) \
+    AP_BIAS_LD(P, 0, 0); AP_BIAS_LD(P, 0, 1); AP_BIAS_LD(P, 1, 0); AP_BIAS_LD(P, 1, 1)
+#define AP_BIAS_WAIT(N)                    \
+    asm volatile("s_waitcnt vmcnt(" #N ")" \
+                 : "+v"(nbias[0][0]), "+v"(nbias[0][1]), "+v"(nbias[1][0]), "+v"(nbias[1][1])::"memory")
     auto init_acc = [&]() {
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
-                for (int e = 0; e < 16; ++e) acc[nb][mb][e] = kNorm ? 0.0f : nbias[nb][e >> 2][e & 3];
+                for (int g4 = 0; g4 < 4; ++g4)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[nb][mb][g4][e] = kNorm ? 0.0f : nbias[nb][AccMap::nh(g4)][e];
     };
     if constexpr (!kNorm) {
-        const float* bp0 = bias_ptr(0, hi);
-        AP_BIAS_LD8(bp0);
+        const float* bp0 = bias_ptr(0, am.q);
+        AP_BIAS_LD4(bp0);
         AP_BIAS_WAIT(0);
     }
 
-    Frag fa[2][4], fb0[4], fb1[4];
+    Frag fa[4][2], fb0[2][2], fb1[2][2];      // [16-row block of the unit's 64 m / 32 n rows][32-deep k-step]
 
     // ---- prologue: K-tile 0 complete, X0 / Y0 of K-tile 1
     stage(ca, true, 0, U_X0); stage(ca, false, 0, U_Y0); advance(ca, 0);
@@ -308,61 +317,18 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
     if (!(kDiag && abl_nobar)) __builtin_amdgcn_s_barrier();  \
     __builtin_amdgcn_sched_barrier(0)
 #define AP_MMA(ACC, B, A) ACC = Mma<T>::run(B, A, ACC)
+    // A phase = 64 m x 32 n x 64 k per wave = 16 MFMAs.  AP_MMA2: activation block J (16 rows) of X-unit half H against both weight
+    // blocks of the phase's Y unit (fragments FB, accumulator column block NB), k-step KK; AP_MMA8: the four blocks J of one k-step.
+#define AP_MMA2(NB, H, FB, J, KK)                                                      \
+    AP_MMA(acc[NB][(H) * 2 + ((J) >> 1)][(J) & 1], FB[0][KK], fa[J][KK]);              \
+    AP_MMA(acc[NB][(H) * 2 + ((J) >> 1)][2 + ((J) & 1)], FB[1][KK], fa[J][KK])
+#define AP_MMA8(NB, H, FB, KK) \
+    AP_MMA2(NB, H, FB, 0, KK); AP_MMA2(NB, H, FB, 1, KK); AP_MMA2(NB, H, FB, 2, KK); AP_MMA2(NB, H, FB, 3, KK)
+    constexpr int kBlk = 16 * kRowBytes;      // one 16-row operand block
 
-    // (the loop of rounds 2-4: still what EPI_PATCH_STREAM runs -- its epilogue keeps more registers live across the K loop and
-    //  the pipelined form below would spill 5-11 of them)
     // wait = false only for the first K-tile after an epilogue: everything staged before the epilogue
     // was drained there (vmcnt(0)), so its four phases need no counted wait and the epilogue's own
     // stores keep draining under them.
-    [[maybe_unused]] auto ktile = [&](auto bufc, const bool wait) {
-        constexpr int BUF = decltype(bufc)::value;
-        const char* buf = smem + BUF * kBufBytes;
-        // ---------------- phase 0: (X0, Y0), stage Y1 of the next K-tile
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            fb0[kk] = *(const Frag*)(buf + U_Y0 * kUnitBytes + pb[kk]);
-            fa[0][kk] = *(const Frag*)(buf + U_X0 * kUnitBytes + pa[kk]);
-            fa[1][kk] = *(const Frag*)(buf + U_X0 * kUnitBytes + 32 * kRowBytes + pa[kk]);
-        }
-        AP_PHASE_SYNC();
-        AP_MMA(acc[0][0], fb0[0], fa[0][0]); AP_MMA(acc[0][1], fb0[0], fa[1][0]);
-        stage(cb, false, BUF ^ 1, U_Y1);
-        AP_MMA(acc[0][0], fb0[1], fa[0][1]); AP_MMA(acc[0][1], fb0[1], fa[1][1]);
-        AP_MMA(acc[0][0], fb0[2], fa[0][2]); AP_MMA(acc[0][1], fb0[2], fa[1][2]);
-        AP_MMA(acc[0][0], fb0[3], fa[0][3]); AP_MMA(acc[0][1], fb0[3], fa[1][3]);
-        // ---------------- phase 1: (X0, Y1), stage X1 of the next K-tile
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) fb1[kk] = *(const Frag*)(buf + U_Y1 * kUnitBytes + pb[kk]);
-        AP_PHASE_SYNC();
-        AP_MMA(acc[1][0], fb1[0], fa[0][0]); AP_MMA(acc[1][1], fb1[0], fa[1][0]);
-        stage(cb, true, BUF ^ 1, U_X1);
-        advance(cb, 1);
-        AP_MMA(acc[1][0], fb1[1], fa[0][1]); AP_MMA(acc[1][1], fb1[1], fa[1][1]);
-        AP_MMA(acc[1][0], fb1[2], fa[0][2]); AP_MMA(acc[1][1], fb1[2], fa[1][2]);
-        AP_MMA(acc[1][0], fb1[3], fa[0][3]); AP_MMA(acc[1][1], fb1[3], fa[1][3]);
-        // ---------------- phase 2: (X1, Y1), stage X0 of the K-tile after next
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            fa[0][kk] = *(const Frag*)(buf + U_X1 * kUnitBytes + pa[kk]);
-            fa[1][kk] = *(const Frag*)(buf + U_X1 * kUnitBytes + 32 * kRowBytes + pa[kk]);
-        }
-        AP_PHASE_SYNC();
-        AP_MMA(acc[1][2], fb1[0], fa[0][0]); AP_MMA(acc[1][3], fb1[0], fa[1][0]);
-        stage(ca, true, BUF, U_X0);
-        AP_MMA(acc[1][2], fb1[1], fa[0][1]); AP_MMA(acc[1][3], fb1[1], fa[1][1]);
-        AP_MMA(acc[1][2], fb1[2], fa[0][2]); AP_MMA(acc[1][3], fb1[2], fa[1][2]);
-        AP_MMA(acc[1][2], fb1[3], fa[0][3]); AP_MMA(acc[1][3], fb1[3], fa[1][3]);
-        // ---------------- phase 3: (X1, Y0)   (Y0 fragment still in registers), stage Y0 likewise
-        AP_PHASE_SYNC();
-        AP_MMA(acc[0][2], fb0[0], fa[0][0]); AP_MMA(acc[0][3], fb0[0], fa[1][0]);
-        stage(ca, false, BUF, U_Y0);
-        advance(ca, 0);
-        AP_MMA(acc[0][2], fb0[1], fa[0][1]); AP_MMA(acc[0][3], fb0[1], fa[1][1]);
-        AP_MMA(acc[0][2], fb0[2], fa[0][2]); AP_MMA(acc[0][3], fb0[2], fa[1][2]);
-        AP_MMA(acc[0][2], fb0[3], fa[0][3]); AP_MMA(acc[0][3], fb0[3], fa[1][3]);
-    };
-
-    constexpr bool kOldLoop = kPatch;
     // Software-pipelined fragment reads (round 5): the reads of a phase are issued BETWEEN the MFMAs of the phase before it, each as soon
     // as the last MFMA that uses its destination register has been issued (program order pinned with sched_barrier), so every
     // phase opens with MFMAs whose operands arrived long ago instead of with all eight waves' ds_read burst and the
@@ -377,73 +343,106 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
     // SLOWER than the product), and the two waves of a SIMD issuing a phase's LDS-DMA two MFMA pairs apart (+1 ... +3 %).
     // fragment addresses of both K-tile buffers in registers (the second buffer starts past ds_read's 16-bit offset field:
     // without these every read of it is preceded by a v_add / v_or in the MFMA stream)
-    int pa1[4], pb1[4];
+    int pa1[2], pb1[2];
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) { pa1[kk] = pa[kk] + kBufBytes; pb1[kk] = pb[kk] + kBufBytes; }
+    for (int kk = 0; kk < 2; ++kk) { pa1[kk] = pa[kk] + kBufBytes; pb1[kk] = pb[kk] + kBufBytes; }
 #define AP_PA(B, kk) ((B) ? pa1[kk] : pa[kk])
 #define AP_PB(B, kk) ((B) ? pb1[kk] : pb[kk])
 #define AP_FRAG(UNIT_OFF, P) (*(const Frag*)(smem + (UNIT_OFF) + (P)))
     [[maybe_unused]] auto ktile_p = [&](auto bufc, auto firstc, auto prefc, const bool wait) {
         constexpr int BUF = decltype(bufc)::value, NBUF = BUF ^ 1;
         constexpr bool FIRST = decltype(firstc)::value, PREFETCH = decltype(prefc)::value;
+        // (every read sits behind the last MFMA that uses its destination register: one read per MFMA pair, i.e. per 32 pipe cycles)
         // ---------------- phase 0: (X0, Y0), stage Y1 of the next K-tile; read Y1 of this one
         if constexpr (FIRST) {
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                fb0[kk] = AP_FRAG(U_Y0 * kUnitBytes, AP_PB(BUF, kk));
-                fa[0][kk] = AP_FRAG(U_X0 * kUnitBytes, AP_PA(BUF, kk));
-                fa[1][kk] = AP_FRAG(U_X0 * kUnitBytes + 32 * kRowBytes, AP_PA(BUF, kk));
+            for (int kk = 0; kk < 2; ++kk) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) fb0[j][kk] = AP_FRAG(U_Y0 * kUnitBytes + j * kBlk, AP_PB(BUF, kk));
+#pragma unroll
+                for (int j = 0; j < 4; ++j) fa[j][kk] = AP_FRAG(U_X0 * kUnitBytes + j * kBlk, AP_PA(BUF, kk));
             }
         }
         AP_PHASE_SYNC();
-        AP_MMA(acc[0][0], fb0[0], fa[0][0]); AP_MMA(acc[0][1], fb0[0], fa[1][0]);
+        AP_MMA2(0, 0, fb0, 0, 0); AP_MMA2(0, 0, fb0, 1, 0);
         stage(cb, false, NBUF, U_Y1);
         AP_SB();
-        fb1[0] = AP_FRAG(U_Y1 * kUnitBytes, AP_PB(BUF, 0));
-        fb1[1] = AP_FRAG(U_Y1 * kUnitBytes, AP_PB(BUF, 1));
+        fb1[0][0] = AP_FRAG(U_Y1 * kUnitBytes, AP_PB(BUF, 0));
+        fb1[1][0] = AP_FRAG(U_Y1 * kUnitBytes + kBlk, AP_PB(BUF, 0));
         AP_SB();
-        AP_MMA(acc[0][0], fb0[1], fa[0][1]); AP_MMA(acc[0][1], fb0[1], fa[1][1]);
+        AP_MMA2(0, 0, fb0, 2, 0); AP_MMA2(0, 0, fb0, 3, 0);
         AP_SB();
-        fb1[2] = AP_FRAG(U_Y1 * kUnitBytes, AP_PB(BUF, 2));
-        fb1[3] = AP_FRAG(U_Y1 * kUnitBytes, AP_PB(BUF, 3));
+        fb1[0][1] = AP_FRAG(U_Y1 * kUnitBytes, AP_PB(BUF, 1));
+        fb1[1][1] = AP_FRAG(U_Y1 * kUnitBytes + kBlk, AP_PB(BUF, 1));
         AP_SB();
-        AP_MMA(acc[0][0], fb0[2], fa[0][2]); AP_MMA(acc[0][1], fb0[2], fa[1][2]);
-        AP_MMA(acc[0][0], fb0[3], fa[0][3]); AP_MMA(acc[0][1], fb0[3], fa[1][3]);
+        AP_MMA8(0, 0, fb0, 1);
         // ---------------- phase 1: (X0, Y1), stage X1 of the next K-tile; read X1 of this one into fa as its registers free up
         AP_PHASE_SYNC();
-        AP_MMA(acc[1][0], fb1[0], fa[0][0]); AP_MMA(acc[1][1], fb1[0], fa[1][0]);
+        AP_MMA2(1, 0, fb1, 0, 0); AP_MMA2(1, 0, fb1, 1, 0);
         stage(cb, true, NBUF, U_X1); advance(cb, 1);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            AP_SB();
-            fa[0][kk] = AP_FRAG(U_X1 * kUnitBytes, AP_PA(BUF, kk));
-            fa[1][kk] = AP_FRAG(U_X1 * kUnitBytes + 32 * kRowBytes, AP_PA(BUF, kk));
-            AP_SB();
-            if (kk < 3) { AP_MMA(acc[1][0], fb1[kk + 1], fa[0][kk + 1]); AP_MMA(acc[1][1], fb1[kk + 1], fa[1][kk + 1]); }
-        }
+        AP_SB();
+        fa[0][0] = AP_FRAG(U_X1 * kUnitBytes, AP_PA(BUF, 0));
+        fa[1][0] = AP_FRAG(U_X1 * kUnitBytes + kBlk, AP_PA(BUF, 0));
+        AP_SB();
+        AP_MMA2(1, 0, fb1, 2, 0);
+        AP_SB();
+        fa[2][0] = AP_FRAG(U_X1 * kUnitBytes + 2 * kBlk, AP_PA(BUF, 0));
+        AP_SB();
+        AP_MMA2(1, 0, fb1, 3, 0);
+        AP_SB();
+        fa[3][0] = AP_FRAG(U_X1 * kUnitBytes + 3 * kBlk, AP_PA(BUF, 0));
+        AP_SB();
+#define AP_P1(J)                                                      \
+        AP_MMA2(1, 0, fb1, J, 1);                                     \
+        AP_SB();                                                      \
+        fa[J][1] = AP_FRAG(U_X1 * kUnitBytes + (J) * kBlk, AP_PA(BUF, 1)); \
+        AP_SB()
+        AP_P1(0); AP_P1(1); AP_P1(2); AP_P1(3);
+#undef AP_P1
         // ---------------- phase 2: (X1, Y1), stage X0 of the K-tile after next
         AP_PHASE_SYNC();
-        AP_MMA(acc[1][2], fb1[0], fa[0][0]); AP_MMA(acc[1][3], fb1[0], fa[1][0]);
+        AP_MMA2(1, 1, fb1, 0, 0); AP_MMA2(1, 1, fb1, 1, 0);
         stage(ca, true, BUF, U_X0);
         AP_SB();
-        AP_MMA(acc[1][2], fb1[1], fa[0][1]); AP_MMA(acc[1][3], fb1[1], fa[1][1]);
-        AP_MMA(acc[1][2], fb1[2], fa[0][2]); AP_MMA(acc[1][3], fb1[2], fa[1][2]);
-        AP_MMA(acc[1][2], fb1[3], fa[0][3]); AP_MMA(acc[1][3], fb1[3], fa[1][3]);
+        AP_MMA2(1, 1, fb1, 2, 0); AP_MMA2(1, 1, fb1, 3, 0);
+        AP_MMA8(1, 1, fb1, 1);
         // ---------------- phase 3: (X1, Y0), stage Y0 likewise; read X0 / Y0 of the NEXT K-tile (other buffer)
         AP_PHASE_SYNC();
-        AP_MMA(acc[0][2], fb0[0], fa[0][0]); AP_MMA(acc[0][3], fb0[0], fa[1][0]);
+        AP_MMA2(0, 1, fb0, 0, 0); AP_MMA2(0, 1, fb0, 1, 0);
         stage(ca, false, BUF, U_Y0); advance(ca, 0);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            if constexpr (PREFETCH) {
-                AP_SB();
-                fb0[kk] = AP_FRAG(U_Y0 * kUnitBytes, AP_PB(NBUF, kk));
-                fa[0][kk] = AP_FRAG(U_X0 * kUnitBytes, AP_PA(NBUF, kk));
-                fa[1][kk] = AP_FRAG(U_X0 * kUnitBytes + 32 * kRowBytes, AP_PA(NBUF, kk));
-                AP_SB();
-            }
-            if (kk < 3) { AP_MMA(acc[0][2], fb0[kk + 1], fa[0][kk + 1]); AP_MMA(acc[0][3], fb0[kk + 1], fa[1][kk + 1]); }
+        if constexpr (PREFETCH) {
+            AP_SB();
+            fa[0][0] = AP_FRAG(U_X0 * kUnitBytes, AP_PA(NBUF, 0));
+            fa[1][0] = AP_FRAG(U_X0 * kUnitBytes + kBlk, AP_PA(NBUF, 0));
+            AP_SB();
         }
+        AP_MMA2(0, 1, fb0, 2, 0);
+        if constexpr (PREFETCH) {
+            AP_SB();
+            fa[2][0] = AP_FRAG(U_X0 * kUnitBytes + 2 * kBlk, AP_PA(NBUF, 0));
+            AP_SB();
+        }
+        AP_MMA2(0, 1, fb0, 3, 0);
+        if constexpr (PREFETCH) {
+            AP_SB();
+            fa[3][0] = AP_FRAG(U_X0 * kUnitBytes + 3 * kBlk, AP_PA(NBUF, 0));
+            fb0[0][0] = AP_FRAG(U_Y0 * kUnitBytes, AP_PB(NBUF, 0));
+            AP_SB();
+        }
+#define AP_P3(J)                                                                \
+        AP_MMA2(0, 1, fb0, J, 1);                                               \
+        if constexpr (PREFETCH) {                                               \
+            AP_SB();                                                            \
+            fa[J][1] = AP_FRAG(U_X0 * kUnitBytes + (J) * kBlk, AP_PA(NBUF, 1)); \
+            if ((J) == 0) fb0[1][0] = AP_FRAG(U_Y0 * kUnitBytes + kBlk, AP_PB(NBUF, 0)); \
+            if ((J) == 3) {                                                     \
+                fb0[0][1] = AP_FRAG(U_Y0 * kUnitBytes, AP_PB(NBUF, 1));         \
+                fb0[1][1] = AP_FRAG(U_Y0 * kUnitBytes + kBlk, AP_PB(NBUF, 1));  \
+            }                                                                   \
+            AP_SB();                                                            \
+        }
+        AP_P3(0) AP_P3(1) AP_P3(2) AP_P3(3)
+#undef AP_P3
     };
 
     char* scr = smem + kScratchOff + wave * 4096;
@@ -506,7 +505,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
         stamp(ti, 0);
         stamp_clk(ti, 5);
         if constexpr (kLdsOps) { if (ti > 0) stage_ops(ti); }
-        if constexpr (!kOldLoop) {
+        {
             using B0 = std::integral_constant<int, 0>; using B1 = std::integral_constant<int, 1>;
             using Y = std::true_type; using N = std::false_type;
             ktile_p(B0{}, Y{}, Y{}, ti == 0);
@@ -515,17 +514,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
                 ktile_p(B0{}, N{}, Y{}, true);
             }
             ktile_p(B1{}, N{}, N{}, true);
-        } else {
-            for (int kt = 0; kt < nk; kt += 2) {
-                if constexpr (kDiag) {
-                    // fine timeline (twin only): start of every K-tile pair, in a second [workgroups, tiles, 8] block of the buffer
-                    if (g.trace && ti < g.trace_tiles && threadIdx.x == 0 && (kt >> 1) < 8)
-                        g.trace[((size_t)(gridDim.x + blockIdx.x) * g.trace_tiles + ti) * 8 + (kt >> 1)] =
-                            (long long)__builtin_amdgcn_s_memrealtime();
-                }
-                ktile(std::integral_constant<int, 0>{}, ti == 0 || kt != 0);
-                ktile(std::integral_constant<int, 1>{}, true);
-            }
         }
         // ---------------- epilogue
         stamp_clk(ti, 6);
@@ -536,7 +524,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
         // BIAS_QGELU instantiation and spilled THAT register)
         int lane_e;
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
-        const int hi = lane_e >> 5, l31 = lane_e & 31;
+        const AccMap am(lane_e);               // lane -> (m, n) of its accumulators
+        const int l15 = am.l15, q4 = am.q;
         const int id = tw.first + ti * tw.stride;
         int tr, tc;
         tw.rc(id, tr, tc);
@@ -554,31 +543,35 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    nbias[nb][g4] = *(const f32x4*)(scr + 1024 + (nb * 32 + g4 * 8 + hi * 4) * 4);
-                    ncs[nb][g4] = *(const f32x4*)(scr + 1280 + (nb * 32 + g4 * 8 + hi * 4) * 4);
+                for (int nh = 0; nh < 2; ++nh) {
+                    nbias[nb][nh] = *(const f32x4*)(scr + 1024 + (nb * 32 + nh * 16 + q4 * 4) * 4);
+                    ncs[nb][nh] = *(const f32x4*)(scr + 1280 + (nb * 32 + nh * 16 + q4 * 4) * 4);
                 }
 #pragma unroll
-            for (int mb = 0; mb < 4; ++mb) rst[mb] = *(const f32x2*)(scr + (mb * 32 + l31) * 8);
+            for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+                for (int mh = 0; mh < 2; ++mh) rst[mb][mh] = *(const f32x2*)(scr + (mb * 32 + mh * 16 + l15) * 8);
             __builtin_amdgcn_sched_barrier(0);
         } else if constexpr (kNorm) {
             // THIS tile's bias, column sums and row statistics
             __builtin_amdgcn_sched_barrier(0);
-            const float* bp = bias_ptr(ti, hi);
+            const float* bp = bias_ptr(ti, q4);
             const float* cp = g.colsum + (bp - g.bias);
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    nbias[nb][g4] = *(const f32x4*)(bp + nb * 32 + g4 * 8);
-                    ncs[nb][g4] = *(const f32x4*)(cp + nb * 32 + g4 * 8);
+                for (int nh = 0; nh < 2; ++nh) {
+                    nbias[nb][nh] = *(const f32x4*)(bp + nb * 32 + nh * 16);
+                    ncs[nb][nh] = *(const f32x4*)(cp + nb * 32 + nh * 16);
                 }
 #pragma unroll
-            for (int mb = 0; mb < 4; ++mb) {
-                int m = m0 + mb * 32 + l31;
-                m = m < g.M ? m : g.M - 1;
-                rst[mb] = *(const f32x2*)(g.rowstats + 2 * (size_t)m);
-            }
+            for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+                for (int mh = 0; mh < 2; ++mh) {
+                    int m = m0 + mb * 32 + mh * 16 + l15;
+                    m = m < g.M ? m : g.M - 1;
+                    rst[mb][mh] = *(const f32x2*)(g.rowstats + 2 * (size_t)m);
+                }
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_waitcnt(0x0F70);
             __builtin_amdgcn_sched_barrier(0);
@@ -586,11 +579,11 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
             // next tile's bias and this tile's window of the stream (16 B per lane and row: the layout the transposed
             // stores use)
             __builtin_amdgcn_sched_barrier(0);
-            const float* nbp = bias_ptr(ti + 1 < tw.count ? ti + 1 : ti, hi);
+            const float* nbp = bias_ptr(ti + 1 < tw.count ? ti + 1 : ti, q4);
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) nbias[nb][g4] = *(const f32x4*)(nbp + nb * 32 + g4 * 8);
+                for (int nh = 0; nh < 2; ++nh) nbias[nb][nh] = *(const f32x4*)(nbp + nb * 32 + nh * 16);
             auto res_ld = [&](int j) {
                 int m = m0 + (j >> 2) * 32 + (j & 3) * 8 + rrow;
                 m = m < g.M ? m : g.M - 1;
@@ -612,22 +605,19 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
                 if (g.cls_tokens > 0) {
                     const float inv_t = 1.0f / (float)g.cls_tokens;
 #pragma unroll
-                    for (int mb = 0; mb < 4; ++mb) {
-                        const int m = m0 + mb * 32 + l31;
+                    for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+                    for (int mh = 0; mh < 2; ++mh) {
+                        const int m = m0 + mb * 32 + mh * 16 + l15;
                         int q = (int)((float)m * inv_t);
                         const int r = m - q * g.cls_tokens;
                         q = r < 0 ? q - 1 : (r >= g.cls_tokens ? q + 1 : q);
                         if (m == q * g.cls_tokens && m < g.M) {
-                            float* cbr = g.cls_branch + (size_t)q * g.N + n0 + hi * 4;
+                            float* cbr = g.cls_branch + (size_t)q * g.N + n0 + q4 * 4;
 #pragma unroll
                             for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-                                for (int g4 = 0; g4 < 4; ++g4) {
-                                    f32x4 v;
-#pragma unroll
-                                    for (int e = 0; e < 4; ++e) v[e] = acc[nb][mb][g4 * 4 + e];
-                                    *(f32x4*)(cbr + nb * 32 + g4 * 8) = v;
-                                }
+                                for (int nh = 0; nh < 2; ++nh) *(f32x4*)(cbr + nb * 32 + nh * 16) = acc[nb][mb][nh * 2 + mh];
                         }
                     }
                 }
@@ -639,12 +629,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        f32x4 v;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = acc[nb][mb][g4 * 4 + e];
-                        pk[nb][mb][g4] = pack4<T>(v);
-                    }
+                    for (int g4 = 0; g4 < 4; ++g4) pk[nb][mb][g4] = pack4<T>(acc[nb][mb][g4]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 8; j < 16; ++j) res_ld(j);
@@ -657,23 +642,25 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
         } else {
             // next tile's bias (its accumulators start from it), then ONE drain: the stream staged so far (next
             // tile's first K-tiles) and the bias have landed; only loads are outstanding here
-            const float* nbp = bias_ptr(ti + 1 < tw.count ? ti + 1 : ti, hi);
-            AP_BIAS_LD8(nbp);
+            const float* nbp = bias_ptr(ti + 1 < tw.count ? ti + 1 : ti, q4);
+            AP_BIAS_LD4(nbp);
             AP_BIAS_WAIT(0);
         }
         stamp(ti, 2);
         if constexpr (EPI == EPI_NORM_GELU) {
             // the GELU routine takes y * kGeluS (its clamp is the packed multiply's CLAMP bit, ap_common.h): scale the tile's bias
-            // registers and the rows' (rstd, -mean rstd) once -- 24 packed multiplies per tile and wave instead of 128 v_min
+            // registers and the rows' (rstd, -mean rstd) once -- 16 packed multiplies per tile and wave instead of 128 v_min
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) nbias[nb][g4] *= kGeluS;
+                for (int nh = 0; nh < 2; ++nh) nbias[nb][nh] *= kGeluS;
 #pragma unroll
-            for (int mb = 0; mb < 4; ++mb) rst[mb] *= kGeluS;
+            for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+                for (int mh = 0; mh < 2; ++mh) rst[mb][mh] *= kGeluS;
         }
         const bool has_gamma = (EPI == EPI_BIAS_STORE || EPI == EPI_BIAS_RESID) && g.gamma != nullptr;
-        const float* gp = g.gamma + n0 + hi * 4;
+        const float* gp = g.gamma + n0 + q4 * 4;
         if constexpr (kDiag) { if (g.trace) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(ti, 3); } }
         // ablation bit 8 (twin, timing only): no epilogue body at all (drain and accumulator restart stay) = the bound on what
         // hiding the epilogue behind another tile's MFMAs could return
@@ -681,7 +668,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-                for (int mb = 0; mb < 4; ++mb) asm volatile("" ::"v"(acc[nb][mb]));
+                for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+                    for (int g4 = 0; g4 < 4; ++g4) asm volatile("" ::"v"(acc[nb][mb][g4]));
         } else
 #pragma unroll
         for (int mb = 0; mb < 4; ++mb) {
@@ -690,15 +679,13 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
                 for (int nb = 0; nb < 2; ++nb) {
 #pragma unroll
                     for (int g4 = 0; g4 < 4; ++g4) {
-                        f32x4 v;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = acc[nb][mb][g4 * 4 + e];
+                        f32x4 v = acc[nb][mb][g4];
                         if (has_gamma) {
-                            const f32x4 ga = *(const f32x4*)(gp + nb * 32 + g4 * 8);
+                            const f32x4 ga = *(const f32x4*)(gp + nb * 32 + AccMap::nh(g4) * 16);
 #pragma unroll
                             for (int e = 0; e < 4; ++e) v[e] *= ga[e];
                         }
-                        *(f32x4*)(scr + l31 * 128 + (((g4 * 2 + hi) ^ (l31 & 7)) << 4)) = v;
+                        *(f32x4*)(scr + am.m(g4) * 128 + (((am.n(g4) >> 2) ^ (l15 & 7)) << 4)) = v;       // 16-byte chunk = n / 4
                     }
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
@@ -717,21 +704,23 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
             } else if constexpr (kSwiglu) {
                 // out[m][32 q + j] = silu(norm(x1)) * norm(x2): the lane holds both in acc[0] / acc[1] (interleaved weight rows).
                 // The wave's block is 32 rows x 32 columns = 64 bytes per row: four 16-byte chunks, XOR-swizzled by row & 3
-                const f32x2_t rs2 = {rst[mb][0], rst[mb][0]}, nm2 = {rst[mb][1], rst[mb][1]};
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
+                    const int nh = AccMap::nh(g4), mh = AccMap::mh(g4);
+                    const f32x2_t rs2 = {rst[mb][mh][0], rst[mb][mh][0]}, nm2 = {rst[mb][mh][1], rst[mb][mh][1]};
                     f32x4 y[2];
 #pragma unroll
                     for (int nb = 0; nb < 2; ++nb) {
-                        const f32x2_t lo = __builtin_elementwise_fma(rs2, f32x2_t{acc[nb][mb][g4 * 4 + 0], acc[nb][mb][g4 * 4 + 1]},
-                            __builtin_elementwise_fma(nm2, f32x2_t{ncs[nb][g4][0], ncs[nb][g4][1]}, f32x2_t{nbias[nb][g4][0], nbias[nb][g4][1]}));
-                        const f32x2_t hi2 = __builtin_elementwise_fma(rs2, f32x2_t{acc[nb][mb][g4 * 4 + 2], acc[nb][mb][g4 * 4 + 3]},
-                            __builtin_elementwise_fma(nm2, f32x2_t{ncs[nb][g4][2], ncs[nb][g4][3]}, f32x2_t{nbias[nb][g4][2], nbias[nb][g4][3]}));
+                        const f32x2_t lo = __builtin_elementwise_fma(rs2, f32x2_t{acc[nb][mb][g4][0], acc[nb][mb][g4][1]},
+                            __builtin_elementwise_fma(nm2, f32x2_t{ncs[nb][nh][0], ncs[nb][nh][1]}, f32x2_t{nbias[nb][nh][0], nbias[nb][nh][1]}));
+                        const f32x2_t hi2 = __builtin_elementwise_fma(rs2, f32x2_t{acc[nb][mb][g4][2], acc[nb][mb][g4][3]},
+                            __builtin_elementwise_fma(nm2, f32x2_t{ncs[nb][nh][2], ncs[nb][nh][3]}, f32x2_t{nbias[nb][nh][2], nbias[nb][nh][3]}));
                         y[nb] = f32x4{lo[0], lo[1], hi2[0], hi2[1]};
                     }
                     const f32x2_t a = swiglu2(f32x2_t{y[0][0], y[0][1]}, f32x2_t{y[1][0], y[1][1]});
                     const f32x2_t b = swiglu2(f32x2_t{y[0][2], y[0][3]}, f32x2_t{y[1][2], y[1][3]});
-                    *(u32x2*)(scr + l31 * 64 + ((g4 ^ (l31 & 3)) << 4) + hi * 8) = pack4<T>(f32x4{a[0], a[1], b[0], b[1]});
+                    // row m of the 32-row block, 8 bytes at output column n: 16-byte chunk n / 8 (XOR row & 3), half (n / 4) & 1
+                    *(u32x2*)(scr + am.m(g4) * 64 + (((am.n(g4) >> 3) ^ (l15 & 3)) << 4) + (q4 & 1) * 8) = pack4<T>(f32x4{a[0], a[1], b[0], b[1]});
                 }
                 if (mb == 0 && drain_late) AP_VMCNT(0);        // (the drain that used to open the epilogue)
 #pragma unroll
@@ -746,17 +735,16 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
                 for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
                     for (int g4 = 0; g4 < 4; ++g4) {
-                        f32x4 v;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = acc[nb][mb][g4 * 4 + e];
+                        const int nh = AccMap::nh(g4), mh = AccMap::mh(g4);
+                        f32x4 v = acc[nb][mb][g4];
                         if constexpr (kNorm) {
                             // two values per instruction (v_pk_fma_f32): y = rstd * acc + (nmr * colsum + bias)
                             // (EPI_NORM_GELU: rst and nbias were multiplied by kGeluS above -> y * kGeluS, what the GELU routine takes)
-                            const f32x2_t rs2 = {rst[mb][0], rst[mb][0]}, nm2 = {rst[mb][1], rst[mb][1]};
+                            const f32x2_t rs2 = {rst[mb][mh][0], rst[mb][mh][0]}, nm2 = {rst[mb][mh][1], rst[mb][mh][1]};
                             const f32x2_t lo = __builtin_elementwise_fma(rs2, f32x2_t{v[0], v[1]},
-                                __builtin_elementwise_fma(nm2, f32x2_t{ncs[nb][g4][0], ncs[nb][g4][1]}, f32x2_t{nbias[nb][g4][0], nbias[nb][g4][1]}));
+                                __builtin_elementwise_fma(nm2, f32x2_t{ncs[nb][nh][0], ncs[nb][nh][1]}, f32x2_t{nbias[nb][nh][0], nbias[nb][nh][1]}));
                             const f32x2_t hi2 = __builtin_elementwise_fma(rs2, f32x2_t{v[2], v[3]},
-                                __builtin_elementwise_fma(nm2, f32x2_t{ncs[nb][g4][2], ncs[nb][g4][3]}, f32x2_t{nbias[nb][g4][2], nbias[nb][g4][3]}));
+                                __builtin_elementwise_fma(nm2, f32x2_t{ncs[nb][nh][2], ncs[nb][nh][3]}, f32x2_t{nbias[nb][nh][2], nbias[nb][nh][3]}));
                             v = f32x4{lo[0], lo[1], hi2[0], hi2[1]};
                         }
                         if constexpr (EPI == EPI_BIAS_GELU) {
@@ -772,12 +760,15 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
                             v = f32x4{lo[0], lo[1], hi2[0], hi2[1]};
                         }
                         if (has_gamma) {
-                            const f32x4 ga = *(const f32x4*)(gp + nb * 32 + g4 * 8);
+                            const f32x4 ga = *(const f32x4*)(gp + nb * 32 + nh * 16);
 #pragma unroll
                             for (int e = 0; e < 4; ++e) v[e] *= ga[e];
                         }
-                        if constexpr (kRes) *(u32x2*)(scr + l31 * 128 + (((nb * 4 + g4) ^ (l31 & 7)) << 4) + hi * 8) = pk[nb][mb][g4];
-                        else *(u32x2*)(scr + l31 * 128 + (((nb * 4 + g4) ^ (l31 & 7)) << 4) + hi * 8) = pack4<T>(v);
+                        // row m of the 32-row block, 8 bytes at column nb * 32 + n: 16-byte chunk column / 8 (XOR row & 7: rows l and
+                        // l + 8 of a 32-lane half share a chunk, which is ds_write_b64's minimum of two passes), half (n / 4) & 1
+                        char* dst = scr + am.m(g4) * 128 + (((nb * 4 + (am.n(g4) >> 3)) ^ (l15 & 7)) << 4) + (q4 & 1) * 8;
+                        if constexpr (kRes) *(u32x2*)dst = pk[nb][mb][g4];
+                        else *(u32x2*)dst = pack4<T>(v);
                     }
                 if (mb == 0 && drain_late) AP_VMCNT(0);        // (the drain that used to open the epilogue)
 #pragma unroll
@@ -813,7 +804,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
 #undef AP_PHASE_SYNC
 #undef AP_MMA
 #undef AP_BIAS_LD
-#undef AP_BIAS_LD8
+#undef AP_BIAS_LD4
+#undef AP_MMA2
+#undef AP_MMA8
 #undef AP_BIAS_WAIT
 }
 

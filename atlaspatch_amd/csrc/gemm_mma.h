@@ -1,4 +1,9 @@
-// MFMA fragment / packing / row-statistics helpers shared by the persistent GEMM kernels (gemm256.hip, gemm_duo.hip).
+// MFMA fragment / packing / row-statistics helpers of the persistent GEMM kernel (gemm256.hip).
+//
+// The 16-bit product is v_mfma_f32_16x16x32_{f16,bf16}: on MI355X the chip holds a higher clock on this shape than on
+// 32x32x16 at equal cycles per FLOP (tools/isa_probes/mfma_shape_probe.hip, profiles/mfma_shape_probe.txt), and the f32
+// accumulators of the two shapes are bit-identical for the same operands in ascending k (same probe), which is why the
+// 128 x 128 kernel (gemm.hip) can stay on 32x32x16 and still agree with this one bit for bit.
 #pragma once
 #include "ap_common.h"
 
@@ -8,15 +13,30 @@ namespace {
 template <typename T> struct Mma;
 template <> struct Mma<f16> {
     using Frag = f16x8;
-    static __device__ __forceinline__ f32x16 run(Frag a, Frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+    static __device__ __forceinline__ f32x4 run(Frag a, Frag b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
     }
 };
 template <> struct Mma<bf16> {
     using Frag = bf16x8;
-    static __device__ __forceinline__ f32x16 run(Frag a, Frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+    static __device__ __forceinline__ f32x4 run(Frag a, Frag b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
     }
+};
+
+// Operand map of Mma<T>::run(a, b, c): lane l supplies row l & 15 of either operand, k = 8 (l >> 4) + j (j = 0..7 of the Frag), and
+// receives c[e] = C[first-operand row 4 (l >> 4) + e][second-operand row l & 15].
+// AccMap: the kernels give the WEIGHT fragment as the first operand and cover a 32 (n) x 32 (m) region of the output with 2 x 2
+// blocks, block g = nh * 2 + mh.  Element e of block g in lane l is
+//     m = mh * 16 + (l & 15),    n = nh * 16 + 4 (l >> 4) + e       -- four consecutive n of one m (what pack4 and the
+// 16-byte transposed stores rely on).  m(g) / n(g): the lane's row and first column of block g inside the region.
+struct AccMap {
+    int l15, q;
+    __device__ __forceinline__ explicit AccMap(int lane) : l15(lane & 15), q(lane >> 4) {}
+    static __device__ __forceinline__ constexpr int nh(int g) { return g >> 1; }
+    static __device__ __forceinline__ constexpr int mh(int g) { return g & 1; }
+    __device__ __forceinline__ int m(int g) const { return mh(g) * 16 + l15; }
+    __device__ __forceinline__ int n(int g) const { return nh(g) * 16 + q * 4; }
 };
 
 template <typename T> __device__ __forceinline__ u32x2 pack4(f32x4 v);
