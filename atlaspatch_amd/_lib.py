@@ -71,6 +71,18 @@ class ConvnextConfig(C.Structure):
 CONVNEXT_PROF_KINDS = ("stem", "dwconv_ln", "fc1", "fc2", "downsample", "pool")
 
 
+class SwinConfig(C.Structure):
+    """``ap_swin_config`` (additive to ABI v20); ``struct_size`` is filled in here."""
+    _fields_ = [("struct_size", C.c_uint32), ("depths", C.c_int * 4), ("heads", C.c_int * 4), ("embed_dim", C.c_int),
+                ("window", C.c_int), ("compute_dtype", C.c_int), ("image_size", C.c_int)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(C.sizeof(type(self)), *args, **kw)
+
+
+SWIN_PROF_KINDS = ("stem", "ln", "qkv", "window_attn", "proj", "fc1", "fc2", "merge", "pool")
+
+
 # name -> (restype, argtypes); every symbol include/atlaspatch_hip.h declares
 SIGNATURES = {
     "ap_abi_version": (C.c_int, []),
@@ -144,6 +156,22 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "ap_layernorm_rows": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                     C.c_void_p]),
+    "ap_sizeof_swin_config": (C.c_size_t, []),
+    "ap_swin_config_init": (C.c_int, [C.POINTER(SwinConfig), C.c_size_t]),
+    "ap_swin_create": (C.c_int, [C.POINTER(SwinConfig), C.POINTER(C.c_void_p)]),
+    "ap_swin_destroy": (None, [C.c_void_p]),
+    "ap_swin_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]),
+    "ap_swin_finalize": (C.c_int, [C.c_void_p]),
+    "ap_swin_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "ap_swin_embed_dim": (C.c_int, [C.c_void_p]),
+    "ap_swin_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "ap_swin_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_int]),
+    "ap_swin_forward_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ap_swin_window_attention": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "ap_patch_merge_ln": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                    C.c_void_p, C.c_void_p]),
     "ap_gemm": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ap_gemm_fused": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -277,6 +277,11 @@ int launch_dwconv7_ln_nhwc(int dtype, const void* x, int n, int h, int w, int c,
                            const float* ln_weight, const float* ln_bias, float eps, void* out, hipStream_t stream);
 int launch_layernorm_rows(int dtype, const void* x, int rows, int c, const float* weight, const float* bias, float eps, void* out,
                           hipStream_t stream);
+// swin.hip: shifted-window attention (7x7 windows, head dimension 32) and patch merging fused with its LayerNorm
+int launch_swin_window_attention(int dtype, const void* qkv, int n, int h, int w, int heads, int shift, const float* rel_bias,
+                                 void* out, hipStream_t stream);
+int launch_patch_merge_ln(int dtype, const void* x, int n, int h, int w, int c, const float* ln_weight, const float* ln_bias,
+                          float eps, void* out, hipStream_t stream);
 
 int tile_content_counts(const uint8_t* tiles, int n, int h, int w, int black_thresh, int sat_thresh,
                         int value_thresh, unsigned* counts, hipStream_t stream);

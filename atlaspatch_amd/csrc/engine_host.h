@@ -1,6 +1,6 @@
-// Host plumbing shared by the encoder objects behind the C ABI (vit.cpp, resnet.cpp, convnext.cpp): per-kind launch timing,
-// the config size hand-over, the forward argument check, the centre-crop offset and the parameter store of the two
-// convolutional engines.  Host C++ only; no kernel source includes it.
+// Host plumbing shared by the encoder objects behind the C ABI (vit.cpp, resnet.cpp, convnext.cpp, swin.cpp): per-kind launch timing,
+// the config size hand-over, the forward argument check, the centre-crop offset and the parameter store of the
+// convolutional and Swin engines.  Host C++ only; no kernel source includes it.
 #pragma once
 #include <cstring>
 #include <map>

@@ -559,6 +559,83 @@ int ap_dwconv7_ln_nhwc(int dtype, const void* x, int n, int h, int w, int c, con
 int ap_layernorm_rows(int dtype, const void* x, int rows, int c, const float* weight, const float* bias, float eps, void* out,
                       ap_stream_t stream);
 
+/* ---- Swin encoder: CHIEF-CTransPath (additive to ABI v20) --------------------------------
+ * Replaces the timm swin_tiny_patch4_window7_224 forward with the convolutional stem of models/patch/chief_ctranspath.py
+ * (head = Identity: the mean over the 49 tokens of the final LayerNorm's output) with the kernels of swin.hip, convnext.hip
+ * and conv.hip.  Activations are token-major NHWC in the compute type; accumulation, softmax and LayerNorm statistics are
+ * f32; every LayerNorm has eps 1e-5 and the GELU is the erf form.  Block j of a stage shifts its windows by 0 (j even, or
+ * the stage's map is a single window) or window / 2.  Same structure rules as ap_resnet_config. */
+typedef struct ap_swin ap_swin;
+typedef struct ap_swin_config {
+    uint32_t struct_size; /* sizeof(ap_swin_config) as the caller sees it; written by ap_swin_config_init */
+    int depths[4];        /* blocks per stage: 2 2 6 2 */
+    int heads[4];         /* attention heads per stage: 3 6 12 24 (embed_dim * 2^s / heads[s] must be 32) */
+    int embed_dim;        /* 96: the first stage's width (a multiple of 32); stage s has embed_dim * 2^s channels */
+    int window;           /* 7 */
+    int compute_dtype;    /* AP_F16 / AP_BF16 / AP_F32 (exact f32 products) */
+    int image_size;       /* 224: the centre crop the network sees (a multiple of 224) */
+} ap_swin_config;
+#define AP_SWIN_CONFIG_SIZE_V20 52u   /* the smallest size ap_swin_create accepts */
+size_t ap_sizeof_swin_config(void);
+int ap_swin_config_init(ap_swin_config* cfg, size_t sizeof_caller);
+/* AP_ERR_INVALID for a window other than 7, a head dimension other than 32 in any stage, or an image size that is not a
+ * multiple of 224. */
+int ap_swin_create(const ap_swin_config* cfg, ap_swin** out);
+void ap_swin_destroy(ap_swin* m);
+/* Upload one parameter (host float32, torch layout, `count` elements); synchronous.  Names (timm's, BatchNorm folded into
+ * the stem's convolutions by the caller; E = embed_dim, C = E * 2^s, s = 0..3, d = 1..3):
+ *   patch_embed.proj.0.weight [E/8, 3, 3, 3] | .bias [E/8]          stem convolution 1 (stride 2, padding 1; ReLU follows)
+ *   patch_embed.proj.3.weight [E/4, E/8, 3, 3] | .bias [E/4]        stem convolution 2 (stride 2, padding 1; ReLU follows)
+ *   patch_embed.proj.6.weight [E, E/4, 1, 1] | .bias [E]            stem projection
+ *   patch_embed.norm.weight [E] | .bias [E]
+ *   layers.<d>.downsample.norm.weight [2C] | .bias [2C]              patch merging in front of stage d: LayerNorm(4 C_{d-1})
+ *   layers.<d>.downsample.reduction.weight [C, 2C]                   ... and its bias-free linear layer
+ *   layers.<s>.blocks.<j>.norm1.weight [C] | .bias [C]
+ *   layers.<s>.blocks.<j>.attn.qkv.weight [3C, C] | .bias [3C]       rows q | k | v, head-major inside each
+ *   layers.<s>.blocks.<j>.attn.relative_position_bias_table [169, heads[s]]
+ *   layers.<s>.blocks.<j>.attn.proj.weight [C, C] | .bias [C]
+ *   layers.<s>.blocks.<j>.norm2.weight [C] | .bias [C]
+ *   layers.<s>.blocks.<j>.mlp.fc1.weight [4C, C] | .bias [4C]        (GELU follows)
+ *   layers.<s>.blocks.<j>.mlp.fc2.weight [C, 4C] | .bias [C]
+ *   norm.weight [8E] | .bias [8E]                                    final LayerNorm
+ * The library pads the stem's channels to the implicit GEMM's granularity with zeros and expands each bias table to
+ * f32 [heads][49][49].  Setting a parameter un-finalises the object. */
+int ap_swin_set_param(ap_swin* m, const char* name, const float* host, size_t count);
+int ap_swin_finalize(ap_swin* m);          /* AP_ERR_STATE if a parameter was never set */
+size_t ap_swin_workspace_bytes(const ap_swin* m, int n);
+int ap_swin_embed_dim(const ap_swin* m);   /* 8 x embed_dim */
+#define AP_SWIN_PROF_STEM 0            /* preprocess + the three stem convolutions + patch_embed.norm */
+#define AP_SWIN_PROF_LN 1              /* norm1, norm2 and the final LayerNorm */
+#define AP_SWIN_PROF_QKV 2
+#define AP_SWIN_PROF_WINDOW_ATTN 3
+#define AP_SWIN_PROF_PROJ 4            /* + residual */
+#define AP_SWIN_PROF_FC1 5             /* + GELU */
+#define AP_SWIN_PROF_FC2 6             /* + residual */
+#define AP_SWIN_PROF_MERGE 7           /* 2x2 gather + LayerNorm, and the reduction */
+#define AP_SWIN_PROF_POOL 8
+#define AP_SWIN_PROF_KINDS 9
+int ap_swin_profile_enable(ap_swin* m, int on);
+int ap_swin_profile_read(ap_swin* m, double* ms_by_kind, long long* launches_by_kind, int kinds);
+/* Same arguments and semantics as ap_convnext_forward_u8; out: device float32 [n, 8 x embed_dim]. */
+int ap_swin_forward_u8(ap_swin* m, const uint8_t* patches, int n, int h, int w,
+                       const float mean[3], const float stdv[3],
+                       float* out, void* workspace, size_t workspace_bytes, ap_stream_t stream);
+
+/* Single operators of the Swin forward (token-major NHWC, T = dtype, device pointers 16-byte aligned):
+ * ap_swin_window_attention: qkv T [n, h, w, 3 * heads * 32] (q | k | v, head-major) -> out T [n, h, w, heads * 32]: roll the
+ *   map by (-shift, -shift), cut it into 7x7 windows, per window and head softmax(q k^T 32^-0.5 + rel_bias[head] + M) v, reverse
+ *   the windows and roll back -- all as index arithmetic inside one kernel.  rel_bias f32 [heads][49][49] (token i = 7 yi + xi).
+ *   M (shift > 0 only) is -100 where the two tokens lie in different regions of the rolled map, the regions being the slices
+ *   [0, h-7) | [h-7, h-shift) | [h-shift, h) per axis.  h % 7 == 0, w % 7 == 0, h, w <= 4096, 0 <= shift < 7, 1 <= heads <= 1024; out must not alias
+ *   qkv.  f32 accumulation and softmax; no atomics: a token's result does not depend on n.
+ * ap_patch_merge_ln: x T [n, h, w, c] (h, w even, c % 8 == 0) -> out T [n, h/2, w/2, 4c] = LayerNorm over the 4c channels
+ *   (f32 statistics, eps; ln_weight / ln_bias f32 [4c]) of x[0::2,0::2] | x[1::2,0::2] | x[0::2,1::2] | x[1::2,1::2]
+ *   (rows, columns) concatenated along the channels; out must not alias x. */
+int ap_swin_window_attention(int dtype, const void* qkv, int n, int h, int w, int heads, int shift, const float* rel_bias,
+                             void* out, ap_stream_t stream);
+int ap_patch_merge_ln(int dtype, const void* x, int n, int h, int w, int c, const float* ln_weight, const float* ln_bias, float eps,
+                      void* out, ap_stream_t stream);
+
 /* ---- float32 operator set of the SAM2 (Hiera-T) tissue segmenter ------------------------
  * Replaces the torch modules behind SAM2ImagePredictor.set_image / predict as the reference drives them
  * (services/segmentation.py:120-140: one 1024 x 1024 thumbnail per slide, box prompt = whole image,
