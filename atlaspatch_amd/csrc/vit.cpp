@@ -11,12 +11,12 @@
 //   hid   T   [M, mlp]    GELU(fc1) ; the patch-row matrix [n*P, Kpe] aliases it
 // Weights are converted once to T, K-contiguous ([out, in], exactly the checkpoint layout).
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
 #include <vector>
 #include "engine_host.h"
-#include <cstdlib>
 
 namespace ap {
 
@@ -30,9 +30,6 @@ struct Param {
     bool set = false;
 };
 
-}  // namespace ap
-
-namespace ap {
 // parameter pointers of one block, resolved once by ap_vit_finalize (no name lookups on the launch path)
 struct BlockParams {
     const float *ln1_w, *ln1_b, *qkv_b, *proj_b, *ln2_w, *ln2_b, *fc1_b, *fc2_b, *ls1, *ls2;
@@ -84,6 +81,20 @@ struct ap_vit {
     // experimental two-half overlap (AP_VIT_OVERLAP=1): second stream + hand-off events
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+
+    ~ap_vit() {
+        for (auto& kv : params) {
+            if (kv.second.dev) (void)hipFree(kv.second.dev);
+            if (kv.second.dev32) (void)hipFree(kv.second.dev32);
+            if (kv.second.split) (void)hipFree(kv.second.split);
+        }
+        for (void* p : fused_allocs) (void)hipFree(p);
+        if (prefix_dev) (void)hipFree(prefix_dev);
+        if (zero_bias) (void)hipFree(zero_bias);
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (ev_join) (void)hipEventDestroy(ev_join);
+        if (side) (void)hipStreamDestroy(side);
+    }
 };
 
 namespace {
@@ -110,9 +121,26 @@ const Param* find(const ap_vit* m, const std::string& name) {
     return it == m->params.end() ? nullptr : &it->second;
 }
 
-// weight operand of a GEMM on the float32 path: the f32 matrix, or its split rows when AP_VIT_OPT_SPLIT_F16 is on
+// float32 compute type with AP_VIT_OPT_SPLIT_F16 on: split-f16 products in the GEMMs and in the blocks' attention
 inline bool use_split(const ap_vit* m) { return m->split_f16 && m->cfg.compute_dtype == AP_F32; }
-inline const void* wsel(const ap_vit* m, const Param* p) { return use_split(m) ? p->split : p->dev; }
+
+// The weight operand of a GEMM (W, ldw, split): rows row0 .. of parameter p.  The one place that knows which buffer a GEMM
+// reads: the matrix in the compute type; its split rows when use_split (same row stride in bytes); or `folded`, the fused
+// dataflow's copy of p with the LayerNorm gain / LayerScale folded in (FusedBlock: shape and ld of p, 16-bit types, so never split).
+void set_weight(const ap_vit* m, ap::GemmArgs& g, const Param* p, int row0 = 0, const void* folded = nullptr) {
+    const bool split = !folded && use_split(m);
+    const void* base = folded ? folded : (split ? p->split : p->dev);
+    g.W = (const char*)base + (size_t)row0 * p->ld * ap::dtype_size(m->cfg.compute_dtype);
+    g.split = split; g.ldw = p->ld;
+}
+
+// The epilogue of an fc1 GEMM.  folded: the fused dataflow's GEMM on the stream (EPI_NORM_*: row statistics applied, SwiGLU
+// gated in the epilogue); otherwise the plain one (EPI_BIAS_*: SwiGLU stores both halves and launch_swiglu follows).
+int fc1_epilogue(const ap_vit_config& c, bool folded) {
+    if (c.mlp_type == AP_MLP_SWIGLU) return folded ? ap::EPI_NORM_SWIGLU : ap::EPI_BIAS_STORE;
+    if (c.act == AP_ACT_QUICK_GELU) return folded ? ap::EPI_NORM_QGELU : ap::EPI_BIAS_QGELU;
+    return folded ? ap::EPI_NORM_GELU : ap::EPI_BIAS_GELU;
+}
 
 struct Workspace {
     float* tok; void* xn; void* qkv; void* att; void* hid; void* hid2; void* delta; void* delta2;
@@ -167,19 +195,15 @@ int patch_embed(ap_vit* m, int n, const Workspace& w, hipStream_t stream) {
     const int dt = c.compute_dtype, D = c.dim;
     int rc;
     // patch embedding: tok[img][1 + p] = pe_row @ W^T + b + pos[1 + p]
-    {
-        const Param* wpe = m->pe_w;
-        ap::GemmArgs g{};
-        g.A = w.hid; g.lda = m->kpe; g.W = wsel(m, wpe); g.split = use_split(m); g.ldw = wpe->ld;
-        g.M = n * m->patches; g.N = D; g.K = m->kpe;
-        g.bias = m->pe_b;
-        g.pos = m->pos;
-        g.out = w.tok; g.ldo = D; g.P = m->patches; g.R = m->prefix; g.pos_row0 = m->pos_row0;
-        { ScopedTimer t(m->prof, AP_PROF_GEMM_PATCH_EMBED, stream);
-          if ((rc = ap::launch_gemm(dt, ap::EPI_PATCH_EMBED, g, stream)) != AP_OK) return rc; }
-        if ((rc = ap::launch_cls_init(w.tok, m->prefix_dev, m->prefix, n, m->tokens, D, stream)) != AP_OK) return rc;
-    }
-    return AP_OK;
+    ap::GemmArgs g{};
+    g.A = w.hid; g.lda = m->kpe; set_weight(m, g, m->pe_w);
+    g.M = n * m->patches; g.N = D; g.K = m->kpe;
+    g.bias = m->pe_b;
+    g.pos = m->pos;
+    g.out = w.tok; g.ldo = D; g.P = m->patches; g.R = m->prefix; g.pos_row0 = m->pos_row0;
+    { ScopedTimer t(m->prof, AP_PROF_GEMM_PATCH_EMBED, stream);
+      if ((rc = ap::launch_gemm(dt, ap::EPI_PATCH_EMBED, g, stream)) != AP_OK) return rc; }
+    return ap::launch_cls_init(w.tok, m->prefix_dev, m->prefix, n, m->tokens, D, stream);
 }
 
 // fused path: the patch embedding writes the T stream and its partial sums directly (EPI_PATCH_STREAM), the class-token
@@ -189,7 +213,7 @@ int patch_embed_stream(ap_vit* m, int n, const Workspace& w, hipStream_t stream)
     const int dt = c.compute_dtype, D = c.dim;
     int rc;
     ap::GemmArgs g{};
-    g.A = w.hid; g.lda = m->kpe; g.W = m->pe_w->dev; g.ldw = m->pe_w->ld;
+    g.A = w.hid; g.lda = m->kpe; set_weight(m, g, m->pe_w);
     g.M = n * m->patches; g.N = D; g.K = m->kpe;
     g.bias = m->pe_b; g.pos16 = m->pos16; g.P = m->patches; g.R = m->prefix; g.pos_row0 = m->pos_row0;
     g.out = w.x16; g.ldo = D; g.partial = w.partial;
@@ -198,6 +222,72 @@ int patch_embed_stream(ap_vit* m, int n, const Workspace& w, hipStream_t stream)
     ScopedTimer t(m->prof, AP_PROF_LAYERNORM, stream);
     if ((rc = ap::launch_cls_stream(dt, m->prefix_dev, m->prefix, 0, n, m->tokens, D, w.x16, w.partial, stream)) != AP_OK) return rc;
     return ap::launch_rowstats_finalize(w.partial, n * m->tokens, D / 64, D, c.ln_eps, w.rowstats, stream);
+}
+
+// ---- attention of one block on the packed q | k | v rows -> att
+int block_attention(ap_vit* m, int n, const Workspace& w, hipStream_t stream) {
+    const ap_vit_config& c = m->cfg;
+    const int DA = m->dattn;
+    ScopedTimer t(m->prof, AP_PROF_ATTENTION, stream);
+    if (use_split(m) && n <= 65535) {
+        // float32, split-f16 products: the fused float32 attention of the SAM2 operator set in its split form (image = window,
+        // q | k | v at column offsets of the packed rows) -- same arithmetic class as the GEMMs around it; 46 -> 27.5 ms of a
+        // 2048-tile ViT-B/16 step against the exact-f32 strip kernel (profiles/r06e_split_f16_attention.txt)
+        const float* qp = (const float*)w.qkv;
+        return ap::launch_sattention(qp, 3 * DA, qp + DA, 3 * DA, qp + 2 * DA, 3 * DA, n, c.heads, m->tokens, m->tokens, m->hd,
+                                     m->attn_scale, (float*)w.att, DA, stream, /*exact=*/false);
+    }
+    return ap::launch_attention(c.compute_dtype, w.qkv, w.att, n, m->tokens, c.heads, m->hd, m->attn_scale, stream);
+}
+
+// ---- Last block, CLS readout (class-token pooling unless AP_VIT_OPT_FULL_LAST_BLOCK): nothing reads this block's output for
+// the patch tokens, so only what the CLS row depends on is computed: K and V of every token, then the CLS row alone through
+// q-projection, attention, proj, ln2, fc1, fc2.  Same operators, same operation order per row -> same features.
+// The block loops run what their dataflow does differently -- the k | v GEMM into qkv (rope on k only: the class rows' q is
+// not rotated) and LayerNorm-1 of the class rows -- and this is the rest, on the plain weights in both dataflows:
+//   in   xn    LayerNorm-1 of the class rows, row stride xn_stride
+//        tok   their f32 residual stream, row stride tok_stride, with `pending` (LayerScale pending_ls, row stride
+//              pending_stride; null: none) still to be added
+//   out  tok   + pending + proj branch (stored by ln2)
+//        delta fc2 output [n, D], left for the final LayerNorm to fold in with bp.ls2
+// xn [n, D], att, hid, delta2 are scratch.
+int cls_tail_rows(ap_vit* m, int n, const Workspace& w, const ap::BlockParams& bp, long xn_stride, long tok_stride,
+                  const void* pending, const float* pending_ls, long pending_stride, hipStream_t stream) {
+    const ap_vit_config& c = m->cfg;
+    const int dt = c.compute_dtype, D = c.dim, DA = m->dattn, H = c.mlp_dim, F1 = m->fc1_rows;
+    const bool swiglu = c.mlp_type == AP_MLP_SWIGLU;
+    int rc;
+    char* q_cls = (char*)w.att;                                              // T [n, DA]
+    char* a_cls = (char*)w.att + (size_t)n * DA * ap::dtype_size(dt);        // T [n, DA]
+    // n-row GEMMs on the 128x128 kernel: more workgroups than 256x256 tiles would give, bit-identical results
+    {
+        ap::GemmArgs g{};                                                    // q for the CLS rows
+        g.A = w.xn; g.lda = (int)xn_stride; set_weight(m, g, bp.qkv);
+        g.M = n; g.N = DA; g.K = D; g.bias = bp.qkv_b; g.out = q_cls; g.ldo = DA;
+        if ((rc = ap::launch_gemm_impl(dt, ap::EPI_BIAS_STORE, g, 128, 0, stream)) != AP_OK) return rc;
+    }
+    if ((rc = ap::launch_attention_cls(dt, q_cls, w.qkv, 3 * DA, DA, 2 * DA, a_cls, n, m->tokens, c.heads,
+                                       m->hd, m->attn_scale, stream)) != AP_OK) return rc;
+    {
+        ap::GemmArgs g{};
+        g.A = a_cls; g.lda = DA; set_weight(m, g, bp.proj);
+        g.M = n; g.N = D; g.K = DA; g.bias = bp.proj_b; g.out = w.delta2; g.ldo = D;
+        if ((rc = ap::launch_gemm_impl(dt, ap::EPI_BIAS_STORE, g, 128, 0, stream)) != AP_OK) return rc;
+    }
+    if ((rc = ap::launch_add2_layernorm(dt, dt, w.tok, tok_stride, pending, pending_stride, pending_ls, w.delta2, D,
+                                        bp.ls1, /*store=*/1, n, D, bp.ln2_w, bp.ln2_b, c.ln_eps, w.xn, stream)) != AP_OK)
+        return rc;
+    {
+        ap::GemmArgs g{};
+        g.A = w.xn; g.lda = D; set_weight(m, g, bp.fc1);
+        g.M = n; g.N = F1; g.K = D; g.bias = bp.fc1_b; g.out = w.hid; g.ldo = F1;
+        if ((rc = ap::launch_gemm_impl(dt, fc1_epilogue(c, /*folded=*/false), g, 128, 0, stream)) != AP_OK) return rc;
+        if (swiglu && (rc = ap::launch_swiglu(dt, w.hid, n, H, w.hid2, stream)) != AP_OK) return rc;
+    }
+    ap::GemmArgs g{};
+    g.A = w.hid2; g.lda = H; set_weight(m, g, bp.fc2);
+    g.M = n; g.N = D; g.K = H; g.bias = bp.fc2_b; g.out = w.delta; g.ldo = D;
+    return ap::launch_gemm_impl(dt, ap::EPI_BIAS_STORE, g, 128, 0, stream);
 }
 
 // ---- block loop, f32 residual stream (float32 mode; AP_VIT_OPT_F32_STREAM for f16 / bf16)
@@ -223,85 +313,33 @@ int blocks_f32_stream(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipS
           if ((rc = ap::launch_add2_layernorm(dt, dt, w.tok, D, pending, D, pending_ls, nullptr, 0, nullptr, /*store=*/0,
                                               M, D, bp.ln1_w, bp.ln1_b, c.ln_eps, w.xn,
                                               stream)) != AP_OK) return rc; }
-        if (i == c.depth - 1 && cls_tail) {
-            // ---- last block, CLS readout: nothing reads this block's output for the patch tokens, so only what the
-            // CLS row depends on is computed: K and V of every token, then the CLS row alone through q-projection,
-            // attention, proj, ln2, fc1, fc2.  Same operators, same operation order per row -> same features.
-            const size_t es = ap::dtype_size(dt);
-            const Param* wq = bp.qkv;
+        // last block of a CLS readout (cls_tail_rows): K and V of every token, then the class rows alone
+        const bool tail = i == c.depth - 1 && cls_tail;
+        {
+            const int col0 = tail ? DA : 0;                                // q | k | v, or k | v only
+            ap::GemmArgs g{};
+            g.A = w.xn; g.lda = D; set_weight(m, g, bp.qkv, col0);
+            g.M = M; g.N = 3 * DA - col0; g.K = D; g.bias = bp.qkv_b + col0;
+            g.out = (char*)w.qkv + (size_t)col0 * ap::dtype_size(dt); g.ldo = 3 * DA;
+            ScopedTimer t(m->prof, AP_PROF_GEMM_QKV, stream);
+            if ((rc = ap::launch_gemm(dt, ap::EPI_BIAS_STORE, g, stream)) != AP_OK) return rc;
+            if (c.rope && (rc = ap::launch_rope(dt, w.qkv, n, m->tokens, m->prefix, c.heads, m->hd, m->rope_cos, m->rope_sin,
+                                                tail ? 2 : 3, stream)) != AP_OK) return rc;     // the class rows' q is not rotated
+        }
+        if (tail) {
+            // the class rows where they lie: in xn and tok among their image's tokens, the pending branch likewise
             const long cls_stride = (long)m->tokens * D;
-            char* q_cls = (char*)w.att;                                   // T [n, DA]
-            char* a_cls = (char*)w.att + (size_t)n * DA * es;             // T [n, DA]
-            {
-                ap::GemmArgs g{};                                          // k | v for all rows
-                g.A = w.xn; g.lda = D; g.W = (const char*)wsel(m, wq) + (size_t)DA * wq->ld * es; g.split = use_split(m); g.ldw = wq->ld;
-                g.M = M; g.N = 2 * DA; g.K = D; g.bias = bp.qkv_b + DA;
-                g.out = (char*)w.qkv + (size_t)DA * es; g.ldo = 3 * DA;
-                ScopedTimer t(m->prof, AP_PROF_GEMM_QKV, stream);
-                if ((rc = ap::launch_gemm(dt, ap::EPI_BIAS_STORE, g, stream)) != AP_OK) return rc;
-                if (c.rope && (rc = ap::launch_rope(dt, w.qkv, n, m->tokens, m->prefix, c.heads, m->hd, m->rope_cos, m->rope_sin, 2,
-                                                    stream)) != AP_OK) return rc;     // the class rows' q is not rotated
-            }
-            // n-row GEMMs on the 128x128 kernel: more workgroups than 256x256 tiles would give, bit-identical results
             ScopedTimer t(m->prof, AP_PROF_CLS_TAIL, stream);
-            {
-                ap::GemmArgs g{};                                          // q for the CLS rows
-                g.A = w.xn; g.lda = (int)cls_stride; g.W = wsel(m, wq); g.split = use_split(m); g.ldw = wq->ld;
-                g.M = n; g.N = DA; g.K = D; g.bias = bp.qkv_b; g.out = q_cls; g.ldo = DA;
-                if ((rc = ap::launch_gemm_impl(dt, ap::EPI_BIAS_STORE, g, 128, 0, stream)) != AP_OK) return rc;
-            }
-            if ((rc = ap::launch_attention_cls(dt, q_cls, w.qkv, 3 * DA, DA, 2 * DA, a_cls, n, m->tokens, c.heads,
-                                               m->hd, m->attn_scale, stream)) != AP_OK) return rc;
-            {
-                ap::GemmArgs g{};
-                g.A = a_cls; g.lda = DA; g.W = wsel(m, bp.proj); g.split = use_split(m); g.ldw = bp.proj->ld;
-                g.M = n; g.N = D; g.K = DA; g.bias = bp.proj_b; g.out = w.delta2; g.ldo = D;
-                if ((rc = ap::launch_gemm_impl(dt, ap::EPI_BIAS_STORE, g, 128, 0, stream)) != AP_OK) return rc;
-            }
-            if ((rc = ap::launch_add2_layernorm(dt, dt, w.tok, cls_stride, pending, cls_stride, pending_ls, w.delta2, D,
-                                                bp.ls1, /*store=*/1, n, D,
-                                                bp.ln2_w, bp.ln2_b, c.ln_eps, w.xn, stream)) != AP_OK)
-                return rc;
-            {
-                ap::GemmArgs g{};
-                g.A = w.xn; g.lda = D; g.W = wsel(m, bp.fc1); g.split = use_split(m); g.ldw = bp.fc1->ld;
-                g.M = n; g.N = F1; g.K = D; g.bias = bp.fc1_b; g.out = w.hid; g.ldo = F1;
-                if ((rc = ap::launch_gemm_impl(dt, swiglu ? ap::EPI_BIAS_STORE : (c.act == AP_ACT_QUICK_GELU ? ap::EPI_BIAS_QGELU : ap::EPI_BIAS_GELU), g, 128, 0, stream)) != AP_OK) return rc;
-                if (swiglu && (rc = ap::launch_swiglu(dt, w.hid, n, H, w.hid2, stream)) != AP_OK) return rc;
-            }
-            {
-                ap::GemmArgs g{};
-                g.A = w.hid2; g.lda = H; g.W = wsel(m, bp.fc2); g.split = use_split(m); g.ldw = bp.fc2->ld;
-                g.M = n; g.N = D; g.K = H; g.bias = bp.fc2_b; g.out = w.delta; g.ldo = D;
-                if ((rc = ap::launch_gemm_impl(dt, ap::EPI_BIAS_STORE, g, 128, 0, stream)) != AP_OK) return rc;
-            }
+            if ((rc = cls_tail_rows(m, n, w, bp, cls_stride, cls_stride, pending, pending_ls, cls_stride, stream)) != AP_OK) return rc;
             pending = w.delta;
             pending_ls = bp.ls2;
             pending_stride = D;
             break;
         }
+        if ((rc = block_attention(m, n, w, stream)) != AP_OK) return rc;
         {
             ap::GemmArgs g{};
-            g.A = w.xn; g.lda = D; g.W = wsel(m, bp.qkv); g.split = use_split(m); g.ldw = bp.qkv->ld;
-            g.M = M; g.N = 3 * DA; g.K = D; g.bias = bp.qkv_b; g.out = w.qkv; g.ldo = 3 * DA;
-            ScopedTimer t(m->prof, AP_PROF_GEMM_QKV, stream);
-            if ((rc = ap::launch_gemm(dt, ap::EPI_BIAS_STORE, g, stream)) != AP_OK) return rc;
-            if (c.rope && (rc = ap::launch_rope(dt, w.qkv, n, m->tokens, m->prefix, c.heads, m->hd, m->rope_cos, m->rope_sin, 3,
-                                                stream)) != AP_OK) return rc;
-        }
-        { ScopedTimer t(m->prof, AP_PROF_ATTENTION, stream);
-          if (use_split(m) && n <= 65535) {
-              // float32, split-f16 products: the fused float32 attention of the SAM2 operator set in its split form (image = window,
-              // q | k | v at column offsets of the packed rows) -- same arithmetic class as the GEMMs around it; 46 -> 27.5 ms of a
-              // 2048-tile ViT-B/16 step against the exact-f32 strip kernel (profiles/r06e_split_f16_attention.txt)
-              const float* qp = (const float*)w.qkv;
-              if ((rc = ap::launch_sattention(qp, 3 * DA, qp + DA, 3 * DA, qp + 2 * DA, 3 * DA, n, c.heads, m->tokens, m->tokens, m->hd,
-                                              m->attn_scale, (float*)w.att, DA, stream, /*exact=*/false)) != AP_OK) return rc;
-          } else if ((rc = ap::launch_attention(dt, w.qkv, w.att, n, m->tokens, c.heads, m->hd, m->attn_scale,
-                                                stream)) != AP_OK) return rc; }
-        {
-            ap::GemmArgs g{};
-            g.A = w.att; g.lda = DA; g.W = wsel(m, bp.proj); g.split = use_split(m); g.ldw = bp.proj->ld;
+            g.A = w.att; g.lda = DA; set_weight(m, g, bp.proj);
             g.M = M; g.N = D; g.K = DA; g.bias = bp.proj_b;
             g.out = w.delta2; g.ldo = D;
             ScopedTimer t(m->prof, AP_PROF_GEMM_PROJ, stream);
@@ -313,15 +351,15 @@ int blocks_f32_stream(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipS
                                               bp.ln2_b, c.ln_eps, w.xn, stream)) != AP_OK) return rc; }
         {
             ap::GemmArgs g{};
-            g.A = w.xn; g.lda = D; g.W = wsel(m, bp.fc1); g.split = use_split(m); g.ldw = bp.fc1->ld;
+            g.A = w.xn; g.lda = D; set_weight(m, g, bp.fc1);
             g.M = M; g.N = F1; g.K = D; g.bias = bp.fc1_b; g.out = w.hid; g.ldo = F1;
             ScopedTimer t(m->prof, AP_PROF_GEMM_FC1, stream);
-            if ((rc = ap::launch_gemm(dt, swiglu ? ap::EPI_BIAS_STORE : (c.act == AP_ACT_QUICK_GELU ? ap::EPI_BIAS_QGELU : ap::EPI_BIAS_GELU), g, stream)) != AP_OK) return rc;
+            if ((rc = ap::launch_gemm(dt, fc1_epilogue(c, /*folded=*/false), g, stream)) != AP_OK) return rc;
             if (swiglu && (rc = ap::launch_swiglu(dt, w.hid, M, H, w.hid2, stream)) != AP_OK) return rc;
         }
         {
             ap::GemmArgs g{};
-            g.A = w.hid2; g.lda = H; g.W = wsel(m, bp.fc2); g.split = use_split(m); g.ldw = bp.fc2->ld;
+            g.A = w.hid2; g.lda = H; set_weight(m, g, bp.fc2);
             g.M = M; g.N = D; g.K = H; g.bias = bp.fc2_b;
             g.out = w.delta; g.ldo = D;
             ScopedTimer t(m->prof, AP_PROF_GEMM_FC2, stream);
@@ -346,7 +384,6 @@ int blocks_fused(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipStream
     const int dt = c.compute_dtype, D = c.dim, M = n * m->tokens, G = D / 64;
     const int DA = m->dattn, H = c.mlp_dim, F1 = m->fc1_rows;
     const bool swiglu = c.mlp_type == AP_MLP_SWIGLU;
-    const size_t es = ap::dtype_size(dt);
     int rc;
     const bool cls_tail = c.pool == AP_POOL_CLS && !m->full_last_block;
     // Exact class rows (default for the class-token poolings; AP_VIT_OPT_EXACT_CLS): the features ARE the class row of the
@@ -381,74 +418,35 @@ int blocks_fused(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipStream
     for (int i = 0; i < c.depth; ++i) {
         const ap::BlockParams& bp = m->blocks[i];
         const ap::FusedBlock& fb = m->fused[i];
-        if (i == c.depth - 1 && cls_tail) {
-            // ---- last block, CLS readout (see blocks_f32_stream): K and V of every token from the stream, then the CLS
-            // rows alone continue on the f32 path (their stream rows widened to f32, plain LayerNorm launches, unfolded
-            // weights on the 128x128 kernel).
-            {
-                ap::GemmArgs g{};
-                g.A = w.x16; g.lda = D; g.W = (const char*)fb.qkv_w + (size_t)DA * bp.qkv->ld * es; g.ldw = bp.qkv->ld;
-                g.M = M; g.N = 2 * DA; g.K = D; g.bias = fb.qkv_b + DA; g.colsum = fb.qkv_cs + DA; g.rowstats = w.rowstats;
-                g.out = (char*)w.qkv + (size_t)DA * es; g.ldo = 3 * DA;
-                ScopedTimer t(m->prof, AP_PROF_GEMM_QKV, stream);
-                if ((rc = ap::launch_gemm(dt, ap::EPI_NORM_STORE, g, stream)) != AP_OK) return rc;
-                if (c.rope && (rc = ap::launch_rope(dt, w.qkv, n, m->tokens, m->prefix, c.heads, m->hd, m->rope_cos, m->rope_sin, 2,
-                                                    stream)) != AP_OK) return rc;
-            }
+        // last block of a CLS readout (cls_tail_rows): K and V of every token from the stream, then the CLS rows alone
+        // continue on the f32 path (their stream rows widened to f32, plain LayerNorm launches, unfolded weights)
+        const bool tail = i == c.depth - 1 && cls_tail;
+        {
+            const int col0 = tail ? DA : 0;                                // q | k | v, or k | v only
+            ap::GemmArgs g{};
+            g.A = w.x16; g.lda = D; set_weight(m, g, bp.qkv, col0, fb.qkv_w);
+            g.M = M; g.N = 3 * DA - col0; g.K = D; g.bias = fb.qkv_b + col0; g.colsum = fb.qkv_cs + col0; g.rowstats = w.rowstats;
+            g.out = (char*)w.qkv + (size_t)col0 * ap::dtype_size(dt); g.ldo = 3 * DA;
+            ScopedTimer t(m->prof, AP_PROF_GEMM_QKV, stream);
+            if ((rc = ap::launch_gemm(dt, ap::EPI_NORM_STORE, g, stream)) != AP_OK) return rc;
+            if (c.rope && (rc = ap::launch_rope(dt, w.qkv, n, m->tokens, m->prefix, c.heads, m->hd, m->rope_cos, m->rope_sin,
+                                                tail ? 2 : 3, stream)) != AP_OK) return rc;
+        }
+        if (tail) {
             ScopedTimer t(m->prof, AP_PROF_CLS_TAIL, stream);
             if (exact_cls) AP_HIP_CHECK(hipMemcpyAsync(w.tok, w.cls32, (size_t)n * D * 4, hipMemcpyDeviceToDevice, stream));
             else if ((rc = ap::launch_stream_to_f32(dt, w.x16, (long)m->tokens * D, n, D, w.tok, stream)) != AP_OK) return rc;
             if ((rc = ap::launch_add2_layernorm(dt, dt, w.tok, D, nullptr, 0, nullptr, nullptr, 0, nullptr, /*store=*/0,
                                                 n, D, bp.ln1_w, bp.ln1_b, c.ln_eps, w.xn, stream)) != AP_OK) return rc;
-            char* q_cls = (char*)w.att;                                   // T [n, DA]
-            char* a_cls = (char*)w.att + (size_t)n * DA * es;             // T [n, DA]
-            {
-                ap::GemmArgs g{};                                          // q for the CLS rows
-                g.A = w.xn; g.lda = D; g.W = bp.qkv->dev; g.ldw = bp.qkv->ld;
-                g.M = n; g.N = DA; g.K = D; g.bias = bp.qkv_b; g.out = q_cls; g.ldo = DA;
-                if ((rc = ap::launch_gemm_impl(dt, ap::EPI_BIAS_STORE, g, 128, 0, stream)) != AP_OK) return rc;
-            }
-            if ((rc = ap::launch_attention_cls(dt, q_cls, w.qkv, 3 * DA, DA, 2 * DA, a_cls, n, m->tokens, c.heads,
-                                               m->hd, m->attn_scale, stream)) != AP_OK) return rc;
-            {
-                ap::GemmArgs g{};
-                g.A = a_cls; g.lda = DA; g.W = bp.proj->dev; g.ldw = bp.proj->ld;
-                g.M = n; g.N = D; g.K = DA; g.bias = bp.proj_b; g.out = w.delta2; g.ldo = D;
-                if ((rc = ap::launch_gemm_impl(dt, ap::EPI_BIAS_STORE, g, 128, 0, stream)) != AP_OK) return rc;
-            }
-            if ((rc = ap::launch_add2_layernorm(dt, dt, w.tok, D, nullptr, 0, nullptr, w.delta2, D, bp.ls1, /*store=*/1, n, D,
-                                                bp.ln2_w, bp.ln2_b, c.ln_eps, w.xn, stream)) != AP_OK) return rc;
-            {
-                ap::GemmArgs g{};
-                g.A = w.xn; g.lda = D; g.W = bp.fc1->dev; g.ldw = bp.fc1->ld;
-                g.M = n; g.N = F1; g.K = D; g.bias = bp.fc1_b; g.out = w.hid; g.ldo = F1;
-                if ((rc = ap::launch_gemm_impl(dt, swiglu ? ap::EPI_BIAS_STORE : (c.act == AP_ACT_QUICK_GELU ? ap::EPI_BIAS_QGELU : ap::EPI_BIAS_GELU), g, 128, 0, stream)) != AP_OK) return rc;
-                if (swiglu && (rc = ap::launch_swiglu(dt, w.hid, n, H, w.hid2, stream)) != AP_OK) return rc;
-            }
-            {
-                ap::GemmArgs g{};
-                g.A = w.hid2; g.lda = H; g.W = bp.fc2->dev; g.ldw = bp.fc2->ld;
-                g.M = n; g.N = D; g.K = H; g.bias = bp.fc2_b; g.out = w.delta; g.ldo = D;
-                if ((rc = ap::launch_gemm_impl(dt, ap::EPI_BIAS_STORE, g, 128, 0, stream)) != AP_OK) return rc;
-            }
+            // the class rows packed: tok and xn are [n, D] here, and the stream has no branch pending
+            if ((rc = cls_tail_rows(m, n, w, bp, D, D, nullptr, nullptr, 0, stream)) != AP_OK) return rc;
             st.pending = w.delta; st.pending_ls = bp.ls2; st.pending_stride = D; st.tok_stride = D;
             return AP_OK;
         }
+        if ((rc = block_attention(m, n, w, stream)) != AP_OK) return rc;
         {
             ap::GemmArgs g{};
-            g.A = w.x16; g.lda = D; g.W = fb.qkv_w; g.ldw = bp.qkv->ld;
-            g.M = M; g.N = 3 * DA; g.K = D; g.bias = fb.qkv_b; g.colsum = fb.qkv_cs; g.rowstats = w.rowstats;
-            g.out = w.qkv; g.ldo = 3 * DA;
-            ScopedTimer t(m->prof, AP_PROF_GEMM_QKV, stream);
-            if ((rc = ap::launch_gemm(dt, ap::EPI_NORM_STORE, g, stream)) != AP_OK) return rc;
-            if (c.rope && (rc = ap::launch_rope(dt, w.qkv, n, m->tokens, m->prefix, c.heads, m->hd, m->rope_cos, m->rope_sin, 3,
-                                                stream)) != AP_OK) return rc;
-        }
-        { ScopedTimer t(m->prof, AP_PROF_ATTENTION, stream);
-          if ((rc = ap::launch_attention(dt, w.qkv, w.att, n, m->tokens, c.heads, m->hd, m->attn_scale, stream)) != AP_OK) return rc; }
-        {
-            ap::GemmArgs g{};
-            g.A = w.att; g.lda = DA; g.W = fb.proj_w; g.ldw = bp.proj->ld;
+            g.A = w.att; g.lda = DA; set_weight(m, g, bp.proj, 0, fb.proj_w);
             g.M = M; g.N = D; g.K = DA; g.bias = fb.proj_b; g.out = w.x16; g.ldo = D; g.partial = w.partial;
             if (exact_cls) { g.cls_branch = w.cls_branch; g.cls_tokens = m->tokens; }
             ScopedTimer t(m->prof, AP_PROF_GEMM_PROJ, stream);
@@ -457,17 +455,17 @@ int blocks_fused(ap_vit* m, int n, const Workspace& w, StreamTail& st, hipStream
         if ((rc = finalize_stats()) != AP_OK) return rc;
         {
             ap::GemmArgs g{};
-            g.A = w.x16; g.lda = D; g.W = fb.fc1_w; g.ldw = bp.fc1->ld;
+            g.A = w.x16; g.lda = D; set_weight(m, g, bp.fc1, 0, fb.fc1_w);
             g.M = M; g.N = F1; g.K = D; g.bias = fb.fc1_b; g.colsum = fb.fc1_cs; g.rowstats = w.rowstats;
             // SwiGLU: the folded fc1 weights are row-interleaved (x1 | x2 of the same 32 output columns in one wave's tile), so
             // the gate runs in the epilogue on the f32 values: out = hid2 [M, H] directly, one rounding
             g.out = swiglu ? w.hid2 : w.hid; g.ldo = swiglu ? H : F1;
             ScopedTimer t(m->prof, AP_PROF_GEMM_FC1, stream);
-            if ((rc = ap::launch_gemm(dt, swiglu ? ap::EPI_NORM_SWIGLU : (c.act == AP_ACT_QUICK_GELU ? ap::EPI_NORM_QGELU : ap::EPI_NORM_GELU), g, stream)) != AP_OK) return rc;
+            if ((rc = ap::launch_gemm(dt, fc1_epilogue(c, /*folded=*/true), g, stream)) != AP_OK) return rc;
         }
         {
             ap::GemmArgs g{};
-            g.A = w.hid2; g.lda = H; g.W = fb.fc2_w; g.ldw = bp.fc2->ld;
+            g.A = w.hid2; g.lda = H; set_weight(m, g, bp.fc2, 0, fb.fc2_w);
             g.M = M; g.N = D; g.K = H; g.bias = fb.fc2_b; g.out = w.x16; g.ldo = D; g.partial = w.partial;
             if (exact_cls) { g.cls_branch = w.cls_branch; g.cls_tokens = m->tokens; }
             ScopedTimer t(m->prof, AP_PROF_GEMM_FC2, stream);
@@ -511,7 +509,7 @@ int run_blocks(ap_vit* m, int n, const Workspace& w, float* out, hipStream_t str
         if ((rc = ap::launch_add_layernorm(dt, dt, w.tok, st.tok_stride, pending, st.pending_stride, pending_ls, n, D, m->norm_w,
                                            m->norm_b, c.ln_eps, w.xn, stream)) != AP_OK) return rc;
         ap::GemmArgs g{};
-        g.A = w.xn; g.lda = D; g.W = wsel(m, m->head_proj); g.split = use_split(m); g.ldw = m->head_proj->ld; g.M = n; g.N = P; g.K = D;
+        g.A = w.xn; g.lda = D; set_weight(m, g, m->head_proj); g.M = n; g.N = P; g.K = D;
         g.bias = m->zero_bias; g.out = dt == AP_F32 ? (void*)out : w.att; g.ldo = P;
         if ((rc = ap::launch_gemm_impl(dt, ap::EPI_BIAS_STORE, g, 128, 0, stream)) != AP_OK) return rc;
         return dt == AP_F32 ? AP_OK : ap::launch_stream_to_f32(dt, w.att, P, n, P, out, stream);
@@ -522,29 +520,22 @@ int run_blocks(ap_vit* m, int n, const Workspace& w, float* out, hipStream_t str
                                         n, D, m->norm_w,
                                         m->norm_b, c.ln_eps, out, stream);
 
-    if (c.pool == AP_POOL_CLS_MEAN) {
-        // final LN on ALL tokens (f32 [M, D], reuses qkv), then [class token | mean of the patch tokens] -> out f32 [n, 2 D]
-        float* y = (float*)w.qkv;
-        if ((rc = ap::launch_add_layernorm(dt, AP_F32, w.tok, D, pending, D, pending_ls, M, D, m->norm_w, m->norm_b, c.ln_eps, y,
-                                           stream)) != AP_OK) return rc;
+    // the other poolings: final LN on ALL tokens (y f32 [M, D], reuses qkv)
+    float* y = (float*)w.qkv;
+    if ((rc = ap::launch_add_layernorm(dt, AP_F32, w.tok, D, pending, D, pending_ls, M, D, m->norm_w, m->norm_b, c.ln_eps, y,
+                                       stream)) != AP_OK) return rc;
+    if (c.pool == AP_POOL_CLS_MEAN)      // [class token | mean of the patch tokens] -> out f32 [n, 2 D]
         return ap::launch_cls_mean_pool(y, n, m->tokens, m->prefix, D, out, stream);
-    }
 
-    // ---- AP_POOL_ATTN (CONCH visual tower): final LN on ALL tokens, then the one-query attentional pooler.
-    // Buffers: y f32 [M, D] reuses qkv, xk T [M, D] = xn, kv T [M, 2P] reuses hid, pooled T [n, P] = att,
-    // o32 f32 [n, P] reuses delta.
+    // ---- AP_POOL_ATTN (CONCH visual tower): the one-query attentional pooler on the normalised tokens.
+    // Buffers: xk T [M, D] = xn, kv T [M, 2P] reuses hid, pooled T [n, P] = att, o32 f32 [n, P] reuses delta.
     const int P = c.pool_dim;
     const ap::PoolParams& pp = m->pool;
-    float* y = (float*)w.qkv;
-    if ((rc = ap::launch_add_layernorm(dt, AP_F32, w.tok, D, pending, D, pending_ls, M, D,
-                                       m->norm_w,
-                                       m->norm_b, c.ln_eps, y, stream)) != AP_OK) return rc;
     if ((rc = ap::launch_layernorm(dt, y, D, M, D, pp.ln_k_w, pp.ln_k_b, c.pool_ln_eps, w.xn,
                                    stream)) != AP_OK) return rc;
     {
-        const Param* wkv = pp.kv;
         ap::GemmArgs g{};
-        g.A = w.xn; g.lda = D; g.W = wkv->dev; g.ldw = wkv->ld; g.M = M; g.N = 2 * P; g.K = D;
+        g.A = w.xn; g.lda = D; set_weight(m, g, pp.kv); g.M = M; g.N = 2 * P; g.K = D;
         g.bias = pp.kv_b; g.out = w.hid; g.ldo = 2 * P;
         if ((rc = ap::launch_gemm(dt, ap::EPI_BIAS_STORE, g, stream)) != AP_OK) return rc;
     }
@@ -552,9 +543,8 @@ int run_blocks(ap_vit* m, int n, const Workspace& w, float* out, hipStream_t str
     float* o32 = (float*)w.delta;
     AP_HIP_CHECK(hipMemsetAsync(o32, 0, (size_t)n * P * sizeof(float), stream));
     {
-        const Param* wo = pp.out;
         ap::GemmArgs g{};
-        g.A = w.att; g.lda = P; g.W = wo->dev; g.ldw = wo->ld; g.M = n; g.N = P; g.K = P;
+        g.A = w.att; g.lda = P; set_weight(m, g, pp.out); g.M = n; g.N = P; g.K = P;
         g.bias = pp.out_b; g.out = o32; g.ldo = P;
         if ((rc = ap::launch_gemm(dt, ap::EPI_BIAS_RESID, g, stream)) != AP_OK) return rc;    // 0 + (acc + bias), f32
     }
@@ -575,6 +565,39 @@ int build_split(ap_vit* m) {
     }
     AP_HIP_CHECK(hipDeviceSynchronize());
     return AP_OK;
+}
+
+// ---- parameter bookkeeping shared by ap_vit_set_param and ap_vit_set_params (their upload mechanisms differ)
+int lookup_param(ap_vit* m, const char* name, size_t count, Param** out) {
+    auto it = m->params.find(name);
+    AP_REQUIRE(it != m->params.end(), "vit_set_param: unknown parameter '%s'", name);
+    AP_REQUIRE(count == it->second.count, "vit_set_param: '%s' expects %zu values, got %zu", name, it->second.count, count);
+    *out = &it->second;
+    return AP_OK;
+}
+
+// A matrix was uploaded again: its earlier f32 upload goes, and the new one (upload32, f32 [rows, ld]) is kept if
+// ap_vit_finalize needs it -- 16-bit compute types fold the LayerNorm gains / LayerScale into the block weights from the f32
+// values (one rounding).  False: not kept, the caller releases it once the device is done with it.
+bool keep_upload(ap_vit* m, const char* name, Param& p, float* upload32) {
+    if (p.dev32) { (void)hipFree(p.dev32); p.dev32 = nullptr; }      // (hipFree waits for the device: a re-upload is rare)
+    if (m->cfg.compute_dtype == AP_F32 || strncmp(name, "blocks.", 7) != 0) return false;
+    p.dev32 = upload32;
+    return true;
+}
+
+// `name` has new values: what was derived from the old ones no longer stands
+void mark_set(ap_vit* m, const char* name, Param& p) {
+    p.set = true;
+    const bool was_finalized = m->finalized;
+    if (strcmp(name, "cls_token") == 0 || strcmp(name, "reg_tokens") == 0 || strcmp(name, "pos_embed") == 0)
+        m->finalized = false;              // the prefix rows (class / register tokens + position rows) are rebuilt by finalize
+    if (was_finalized && m->cfg.compute_dtype != AP_F32 &&
+        (strncmp(name, "blocks.", 7) == 0 || strcmp(name, "pos_embed") == 0)) {
+        // the folded weights / the T copy of the position embedding are stale now: a forward needs a new ap_vit_finalize
+        m->fold_dirty = true;
+        m->finalized = false;
+    }
 }
 
 }  // namespace
@@ -627,8 +650,11 @@ int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
     AP_REQUIRE(c.compute_dtype != AP_F32 || (prefix + g * g <= 288 && hd == 64),
                "vit_create: %d tokens / head width %d exceed the float32 attention kernel's limits (288 tokens, 64 wide); use "
                "float16 / bfloat16", prefix + g * g, hd);
+    int device = 0;
+    AP_HIP_CHECK(hipGetDevice(&device));
     ap_vit* m = new ap_vit();
     m->cfg = c;
+    m->device = device;
     m->grid = g; m->patches = g * g; m->prefix = prefix; m->tokens = prefix + g * g;
     m->pos_rows = c.no_embed_class ? g * g : m->tokens;
     m->pos_row0 = c.no_embed_class ? 0 : prefix;
@@ -636,7 +662,6 @@ int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
     m->attn_scale = c.attn_scale > 0.f ? c.attn_scale : 1.0f / sqrtf((float)hd);
     m->fc1_rows = c.mlp_type == AP_MLP_SWIGLU ? 2 * c.mlp_dim : c.mlp_dim;
     m->kpe = (int)ap::align_up(3 * c.patch_size * c.patch_size, 64);
-    AP_HIP_CHECK(hipGetDevice(&m->device));
     m->full_last_block = getenv("AP_VIT_FULL_LAST_BLOCK") != nullptr;     // defaults only; ap_vit_set_option changes them
     m->two_half_overlap = getenv("AP_VIT_OVERLAP") != nullptr;
     m->f32_stream = getenv("AP_VIT_F32_STREAM") != nullptr;
@@ -682,33 +707,19 @@ int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
         add("attn_pool.ln_out.weight", 1, P, false); add("attn_pool.ln_out.bias", 1, P, false);
     }
     if (rc == AP_OK && m->split_f16) rc = build_split(m);
-    if (rc != AP_OK) { ap_vit_destroy(m); return rc; }
+    if (rc != AP_OK) { delete m; return rc; }
     *out = m;
     return AP_OK;
 }
 
-void ap_vit_destroy(ap_vit* m) {
-    if (!m) return;
-    for (auto& kv : m->params) {
-        if (kv.second.dev) (void)hipFree(kv.second.dev);
-        if (kv.second.dev32) (void)hipFree(kv.second.dev32);
-        if (kv.second.split) (void)hipFree(kv.second.split);
-    }
-    for (void* p : m->fused_allocs) (void)hipFree(p);
-    if (m->prefix_dev) (void)hipFree(m->prefix_dev);
-    if (m->zero_bias) (void)hipFree(m->zero_bias);
-    if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
-    if (m->ev_join) (void)hipEventDestroy(m->ev_join);
-    if (m->side) (void)hipStreamDestroy(m->side);
-    delete m;
-}
+void ap_vit_destroy(ap_vit* m) { delete m; }
 
 int ap_vit_set_param(ap_vit* m, const char* name, const float* host, size_t count) {
     AP_REQUIRE(m && name && host, "vit_set_param: null argument");
-    auto it = m->params.find(name);
-    AP_REQUIRE(it != m->params.end(), "vit_set_param: unknown parameter '%s'", name);
-    Param& p = it->second;
-    AP_REQUIRE(count == p.count, "vit_set_param: '%s' expects %zu values, got %zu", name, p.count, count);
+    Param* found = nullptr;
+    int rc = lookup_param(m, name, count, &found);
+    if (rc != AP_OK) return rc;
+    Param& p = *found;
     if (!p.matrix) {
         AP_HIP_CHECK(hipMemcpy(p.dev, host, count * sizeof(float), hipMemcpyHostToDevice));
     } else {
@@ -717,27 +728,13 @@ int ap_vit_set_param(ap_vit* m, const char* name, const float* host, size_t coun
         AP_HIP_CHECK(hipMemset(tmp, 0, (size_t)p.rows * p.ld * sizeof(float)));
         AP_HIP_CHECK(hipMemcpy2D(tmp, (size_t)p.ld * sizeof(float), host, (size_t)p.cols * sizeof(float),
                                  (size_t)p.cols * sizeof(float), p.rows, hipMemcpyHostToDevice));
-        int rc = ap::launch_convert(m->cfg.compute_dtype, tmp, p.dev, (size_t)p.rows * p.ld, nullptr);
+        rc = ap::launch_convert(m->cfg.compute_dtype, tmp, p.dev, (size_t)p.rows * p.ld, nullptr);
         if (rc == AP_OK && p.split) rc = refresh_split(p, nullptr);
         if (rc != AP_OK) { (void)hipFree(tmp); return rc; }
         AP_HIP_CHECK(hipDeviceSynchronize());
-        if (p.dev32) { (void)hipFree(p.dev32); p.dev32 = nullptr; }
-        // 16-bit compute types: ap_vit_finalize folds the LayerNorm gains / LayerScale into the block weights from the
-        // f32 values (one rounding), so the upload is kept until then
-        const bool is_block = strncmp(name, "blocks.", 7) == 0;
-        if (m->cfg.compute_dtype != AP_F32 && is_block) p.dev32 = tmp;
-        else AP_HIP_CHECK(hipFree(tmp));
+        if (!keep_upload(m, name, p, tmp)) AP_HIP_CHECK(hipFree(tmp));
     }
-    p.set = true;
-    const bool was_finalized = m->finalized;
-    if (strcmp(name, "cls_token") == 0 || strcmp(name, "reg_tokens") == 0 || strcmp(name, "pos_embed") == 0)
-        m->finalized = false;              // the prefix rows (class / register tokens + position rows) are rebuilt by finalize
-    if (was_finalized && m->cfg.compute_dtype != AP_F32 &&
-        (strncmp(name, "blocks.", 7) == 0 || strcmp(name, "pos_embed") == 0)) {
-        // the folded weights / the T copy of the position embedding are stale now: a forward needs a new ap_vit_finalize
-        m->fold_dirty = true;
-        m->finalized = false;
-    }
+    mark_set(m, name, p);
     return AP_OK;
 }
 
@@ -751,10 +748,9 @@ int ap_vit_set_params(ap_vit* m, const char* const* names, const float* const* h
     size_t largest = 0;
     for (int i = 0; i < n; ++i) {
         AP_REQUIRE(names[i] && hosts[i], "vit_set_params: null entry %d", i);
-        auto it = m->params.find(names[i]);
-        AP_REQUIRE(it != m->params.end(), "vit_set_param: unknown parameter '%s'", names[i]);
-        AP_REQUIRE(counts[i] == it->second.count, "vit_set_param: '%s' expects %zu values, got %zu", names[i], it->second.count,
-                   counts[i]);
+        Param* p = nullptr;
+        const int lrc = lookup_param(m, names[i], counts[i], &p);
+        if (lrc != AP_OK) return lrc;
         largest = counts[i] > largest ? counts[i] : largest;
     }
     if (n == 0) return AP_OK;
@@ -789,26 +785,12 @@ int ap_vit_set_params(ap_vit* m, const char* const* names, const float* const* h
             int crc = ap::launch_convert(m->cfg.compute_dtype, tmp, p.dev, padded, stream);
             if (crc == AP_OK && p.split) crc = refresh_split(p, stream);
             if (crc != AP_OK) { rc = crc; (void)hipFree(tmp); break; }
-            if (p.dev32) { (void)hipFree(p.dev32); p.dev32 = nullptr; }     // (hipFree waits for the device: a re-upload is rare)
-            const bool is_block = strncmp(names[i], "blocks.", 7) == 0;
-            if (m->cfg.compute_dtype != AP_F32 && is_block) p.dev32 = tmp;   // kept until ap_vit_finalize has folded it
-            else {
-                // freed once the stream is done with it: collect and release after the final synchronisation
-                p.dev32 = nullptr;
-                m->pending_free.push_back(tmp);
-            }
+            // not kept: freed once the stream is done with it, so collect and release after the final synchronisation
+            if (!keep_upload(m, names[i], p, tmp)) m->pending_free.push_back(tmp);
         }
         if (fail(hipEventRecord(b.done, stream), "hipEventRecord")) break;
         b.busy = true;
-        p.set = true;
-        const bool was_finalized = m->finalized;
-        if (strcmp(names[i], "cls_token") == 0 || strcmp(names[i], "reg_tokens") == 0 || strcmp(names[i], "pos_embed") == 0)
-            m->finalized = false;
-        if (was_finalized && m->cfg.compute_dtype != AP_F32 &&
-            (strncmp(names[i], "blocks.", 7) == 0 || strcmp(names[i], "pos_embed") == 0)) {
-            m->fold_dirty = true;
-            m->finalized = false;
-        }
+        mark_set(m, names[i], p);
     }
     if (stream) fail(hipStreamSynchronize(stream), "hipStreamSynchronize");
     for (float* t : m->pending_free) (void)hipFree(t);
