@@ -273,4 +273,166 @@ int ap_attention(int dtype, const void* qkv, void* out, int n, int tokens, int h
     return ap::launch_attention(dtype, qkv, out, n, tokens, heads, head_dim, 1.0f / sqrtf((float)head_dim), (hipStream_t)stream);
 }
 
+// ---- engine building blocks: the kernels vit.cpp chains, one export each.  Every wrapper checks what its launcher assumes
+// without checking (a refusal launches nothing) and forwards; the launchers' own checks follow.
+static inline bool known_dtype(int dt) { return dt == AP_F32 || dt == AP_F16 || dt == AP_BF16; }
+static inline bool half_dtype(int dt) { return dt == AP_F16 || dt == AP_BF16; }
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int ap_attention_scaled(int dtype, const void* qkv, void* out, int n, int tokens, int heads, int head_dim, float scale,
+                        ap_stream_t stream) {
+    AP_REQUIRE(qkv && out, "ap_attention_scaled: null pointer");
+    AP_REQUIRE(known_dtype(dtype), "ap_attention_scaled: unknown dtype %d", dtype);
+    AP_REQUIRE(n >= 0 && tokens > 0 && heads > 0, "ap_attention_scaled: bad shape (n %d, %d tokens, %d heads)", n, tokens, heads);
+    AP_REQUIRE(head_dim == 64 || ((head_dim == 96 || head_dim == 128) && dtype != AP_F32),
+               "ap_attention_scaled: head_dim %d unsupported (64; 96 / 128 in f16 / bf16)", head_dim);
+    AP_REQUIRE(std::isfinite(scale) && scale > 0.f, "ap_attention_scaled: scale must be positive and finite");
+    return ap::launch_attention(dtype, qkv, out, n, tokens, heads, head_dim, scale, (hipStream_t)stream);
+}
+
+int ap_attention_cls(int dtype, const void* q, const void* kv, int ld, int koff, int voff, void* out, int n, int tokens,
+                     int heads, int head_dim, float scale, ap_stream_t stream) {
+    AP_REQUIRE(q && kv && out, "ap_attention_cls: null pointer");
+    AP_REQUIRE(known_dtype(dtype), "ap_attention_cls: unknown dtype %d", dtype);
+    AP_REQUIRE(head_dim == 64 || head_dim == 96 || head_dim == 128, "ap_attention_cls: head_dim %d unsupported (64 / 96 / 128)", head_dim);
+    AP_REQUIRE(n >= 0 && heads > 0 && heads <= (1 << 16), "ap_attention_cls: bad shape (n %d, %d heads)", n, heads);
+    AP_REQUIRE(tokens > 0 && tokens <= 12000, "ap_attention_cls: %d tokens unsupported (1 .. 12000)", tokens);
+    const long width = (long)heads * head_dim;
+    AP_REQUIRE(ld > 0 && ld % 8 == 0 && koff >= 0 && voff >= 0 && koff % 8 == 0 && voff % 8 == 0 && koff + width <= ld && voff + width <= ld,
+               "ap_attention_cls: k / v (offsets %d / %d, %ld wide) must lie inside rows of %d elements, all multiples of 8", koff, voff, width, ld);
+    AP_REQUIRE(aligned16(q) && aligned16(kv) && (dtype != AP_F32 || (((uintptr_t)q | (uintptr_t)kv) & 31) == 0),
+               "ap_attention_cls: q / kv must be aligned to 8 elements");
+    AP_REQUIRE(std::isfinite(scale), "ap_attention_cls: scale must be finite");
+    return ap::launch_attention_cls(dtype, q, kv, ld, koff, voff, out, n, tokens, heads, head_dim, scale, (hipStream_t)stream);
+}
+
+int ap_attn_pool(int dtype, const void* kv, const float* q, void* out, int n, int tokens, int heads, ap_stream_t stream) {
+    AP_REQUIRE(kv && q && out, "ap_attn_pool: null pointer");
+    AP_REQUIRE(half_dtype(dtype), "ap_attn_pool: dtype %d (f16 / bf16 only)", dtype);
+    AP_REQUIRE(n >= 0 && heads > 0 && heads <= (1 << 16), "ap_attn_pool: bad shape (n %d, %d heads)", n, heads);
+    AP_REQUIRE(tokens > 0 && tokens <= 12000, "ap_attn_pool: %d tokens unsupported (1 .. 12000)", tokens);
+    AP_REQUIRE(aligned16(kv), "ap_attn_pool: kv must be 16-byte aligned");
+    return ap::launch_attn_pool(dtype, kv, q, out, n, tokens, heads, (hipStream_t)stream);
+}
+
+int ap_rope(int dtype, void* qkv, int n, int tokens, int prefix, int heads, int head_dim, const float* cos, const float* sin,
+            int which, ap_stream_t stream) {
+    AP_REQUIRE(qkv && cos && sin, "ap_rope: null pointer");
+    AP_REQUIRE(known_dtype(dtype), "ap_rope: unknown dtype %d", dtype);
+    AP_REQUIRE(n >= 0 && heads > 0 && prefix >= 0 && tokens > prefix, "ap_rope: bad shape (n %d, %d tokens, prefix %d, %d heads)", n, tokens,
+               prefix, heads);
+    AP_REQUIRE(head_dim > 0 && head_dim % 16 == 0, "ap_rope: head_dim %d must be a positive multiple of 16", head_dim);
+    AP_REQUIRE(which >= 1 && which <= 3, "ap_rope: which %d (1 = q, 2 = k, 3 = both)", which);
+    AP_REQUIRE(aligned16(qkv), "ap_rope: qkv must be 16-byte aligned");
+    return ap::launch_rope(dtype, qkv, n, tokens, prefix, heads, head_dim, cos, sin, which, (hipStream_t)stream);
+}
+
+int ap_swiglu(int dtype, const void* x, int rows, int h, void* out, ap_stream_t stream) {
+    AP_REQUIRE(x && out, "ap_swiglu: null pointer");
+    AP_REQUIRE(known_dtype(dtype), "ap_swiglu: unknown dtype %d", dtype);
+    AP_REQUIRE(rows >= 0 && h > 0 && h % 8 == 0, "ap_swiglu: bad shape (%d rows, h %d: a positive multiple of 8)", rows, h);
+    AP_REQUIRE(aligned16(x) && aligned16(out), "ap_swiglu: x / out must be 16-byte aligned");
+    return ap::launch_swiglu(dtype, x, rows, h, out, (hipStream_t)stream);
+}
+
+int ap_add2_layernorm(int delta_dtype, int out_dtype, float* x, long stride, const void* delta0, long dstride0, const float* ls0,
+                      const void* delta1, long dstride1, const float* ls1, int store, int rows, int dim, const float* gamma,
+                      const float* beta, float eps, void* out, ap_stream_t stream) {
+    AP_REQUIRE(x && gamma && beta && out, "ap_add2_layernorm: null pointer");
+    AP_REQUIRE(known_dtype(out_dtype) && ((!delta0 && !delta1) || known_dtype(delta_dtype)), "ap_add2_layernorm: unknown dtype (delta %d, out %d)",
+               delta_dtype, out_dtype);
+    AP_REQUIRE((!delta0 && !delta1) || delta_dtype == out_dtype || (delta_dtype != AP_F32 && out_dtype == AP_F32),
+               "ap_add2_layernorm: unsupported dtype pair (delta %d, out %d): (T, T), (T, f32) or (f32, f32)", delta_dtype, out_dtype);
+    AP_REQUIRE(rows >= 0 && dim > 0 && dim % 4 == 0 && dim <= 4096, "ap_add2_layernorm: bad shape (%d rows, dim %d: a multiple of 4 up to 4096)",
+               rows, dim);
+    AP_REQUIRE(store == 0 || store == 1, "ap_add2_layernorm: store %d (0 / 1)", store);
+    // the 16-lane kernel (dim 768 / 1024) reads a 16-bit branch output eight elements at a time
+    const long dmul = (dim == 768 || dim == 1024) && delta_dtype != AP_F32 ? 8 : 4;
+    AP_REQUIRE(stride >= dim && stride % 4 == 0 && (!delta0 || (dstride0 >= dim && dstride0 % dmul == 0)) &&
+                   (!delta1 || (dstride1 >= dim && dstride1 % dmul == 0)),
+               "ap_add2_layernorm: row strides must be at least dim and multiples of 4 (16-bit delta at dim 768 / 1024: of 8)");
+    AP_REQUIRE(aligned16(x) && aligned16(gamma) && aligned16(beta) && aligned16(out) && aligned16(delta0) && aligned16(delta1) && aligned16(ls0) &&
+                   aligned16(ls1),
+               "ap_add2_layernorm: every buffer must be 16-byte aligned");
+    AP_REQUIRE(std::isfinite(eps) && eps >= 0.f, "ap_add2_layernorm: eps must be finite and non-negative");
+    return ap::launch_add2_layernorm(delta_dtype, out_dtype, x, stride, delta0, dstride0, ls0, delta1, dstride1, ls1, store, rows, dim, gamma,
+                                     beta, eps, out, (hipStream_t)stream);
+}
+
+int ap_fold_ln(int dtype, const float* w32, int rows, int cols, int ld, const float* gamma, const float* beta, const float* bias_in,
+               void* wout, float* colsum, float* bias_out, int swiglu_h, ap_stream_t stream) {
+    AP_REQUIRE(w32 && gamma && beta && bias_in && wout && colsum && bias_out, "ap_fold_ln: null pointer");
+    AP_REQUIRE(half_dtype(dtype), "ap_fold_ln: dtype %d (f16 / bf16 only)", dtype);
+    AP_REQUIRE(rows > 0 && cols > 0 && cols <= ld, "ap_fold_ln: bad shape (%d rows, %d cols, ld %d)", rows, cols, ld);
+    AP_REQUIRE(swiglu_h == 0 || (swiglu_h > 0 && swiglu_h % 32 == 0 && rows == 2 * swiglu_h),
+               "ap_fold_ln: swiglu_h %d needs rows = 2 h and h %% 32 == 0", swiglu_h);
+    return ap::launch_fold_ln(dtype, w32, rows, cols, ld, gamma, beta, bias_in, wout, colsum, bias_out, (hipStream_t)stream, swiglu_h);
+}
+
+int ap_fold_ls(int dtype, const float* w32, int rows, int cols, int ld, const float* ls, const float* bias_in, void* wout,
+               float* bias_out, ap_stream_t stream) {
+    AP_REQUIRE(w32 && bias_in && wout && bias_out, "ap_fold_ls: null pointer");
+    AP_REQUIRE(half_dtype(dtype), "ap_fold_ls: dtype %d (f16 / bf16 only)", dtype);
+    AP_REQUIRE(rows > 0 && cols > 0 && cols <= ld, "ap_fold_ls: bad shape (%d rows, %d cols, ld %d)", rows, cols, ld);
+    return ap::launch_fold_ls(dtype, w32, rows, cols, ld, ls, bias_in, wout, bias_out, (hipStream_t)stream);
+}
+
+int ap_cls_mean_pool(const float* y, int n, int tokens, int prefix, int dim, float* out, ap_stream_t stream) {
+    AP_REQUIRE(y && out, "ap_cls_mean_pool: null pointer");
+    AP_REQUIRE(n >= 0 && n <= 65535 && prefix >= 1 && tokens > prefix && dim > 0,
+               "ap_cls_mean_pool: bad shape (n %d up to 65535, %d tokens, prefix %d, dim %d)", n, tokens, prefix, dim);
+    return ap::launch_cls_mean_pool(y, n, tokens, prefix, dim, out, (hipStream_t)stream);
+}
+
+int ap_stream_to_f32(int dtype, const void* x, long stride, int rows, int dim, float* dst, ap_stream_t stream) {
+    AP_REQUIRE(x && dst, "ap_stream_to_f32: null pointer");
+    AP_REQUIRE(half_dtype(dtype), "ap_stream_to_f32: dtype %d (f16 / bf16 only)", dtype);
+    AP_REQUIRE(rows >= 0 && dim > 0 && dim % 4 == 0 && stride >= dim && stride % 4 == 0,
+               "ap_stream_to_f32: bad shape (%d rows, dim %d, stride %ld: multiples of 4, stride >= dim)", rows, dim, stride);
+    AP_REQUIRE(aligned16(dst) && ((uintptr_t)x & 7) == 0, "ap_stream_to_f32: x must be 8-byte and dst 16-byte aligned");
+    return ap::launch_stream_to_f32(dtype, x, stride, rows, dim, dst, (hipStream_t)stream);
+}
+
+int ap_chw_to_patchrows(int x_dtype, int dtype, const void* x, int n, int S, int ps, void* dst, int ld, ap_stream_t stream) {
+    AP_REQUIRE(x && dst, "ap_chw_to_patchrows: null pointer");
+    AP_REQUIRE(known_dtype(x_dtype) && known_dtype(dtype), "ap_chw_to_patchrows: unknown dtype (input %d, output %d)", x_dtype, dtype);
+    AP_REQUIRE(n >= 0 && ps > 0 && ps <= 1024 && S >= ps && S <= 16384 && S % ps == 0, "ap_chw_to_patchrows: image %d / patch %d unsupported", S, ps);
+    AP_REQUIRE(ld >= 3 * ps * ps, "ap_chw_to_patchrows: ld %d is narrower than a patch row (%d)", ld, 3 * ps * ps);
+    // ps % 4 == 0 takes the kernel that stores four elements at a time
+    AP_REQUIRE(ps % 4 != 0 || (ld % 4 == 0 && aligned16(dst)), "ap_chw_to_patchrows: ld %d must be a multiple of 4 and dst 16-byte aligned", ld);
+    return ap::launch_chw_to_patchrows(x_dtype, dtype, x, n, S, ps, dst, ld, (hipStream_t)stream);
+}
+
+int ap_cls_stream(int dtype, const float* prefix, int prefix_rows, int img_rows, int n, int tokens, int dim, void* x, float* partial,
+                  ap_stream_t stream) {
+    AP_REQUIRE(prefix && x && partial, "ap_cls_stream: null pointer");
+    AP_REQUIRE(half_dtype(dtype), "ap_cls_stream: dtype %d (f16 / bf16 only)", dtype);
+    AP_REQUIRE(dim > 0 && dim % 64 == 0, "ap_cls_stream: dim %d must be a positive multiple of 64", dim);
+    AP_REQUIRE(prefix_rows > 0 && (img_rows == 0 || img_rows == prefix_rows), "ap_cls_stream: img_rows %d must be 0 or prefix_rows (%d > 0)",
+               img_rows, prefix_rows);
+    AP_REQUIRE(n >= 0 && tokens >= prefix_rows && (long)n * prefix_rows <= INT_MAX, "ap_cls_stream: bad shape (n %d, %d tokens, %d prefix rows)", n,
+               tokens, prefix_rows);
+    return ap::launch_cls_stream(dtype, prefix, prefix_rows, img_rows, n, tokens, dim, x, partial, (hipStream_t)stream);
+}
+
+int ap_cls_exact_update(int dtype, float* cls32, const float* branch, int n, int tokens, int dim, void* x, float* partial,
+                        ap_stream_t stream) {
+    AP_REQUIRE(cls32 && branch && x && partial, "ap_cls_exact_update: null pointer");
+    AP_REQUIRE(half_dtype(dtype), "ap_cls_exact_update: dtype %d (f16 / bf16 only)", dtype);
+    AP_REQUIRE(dim > 0 && dim % 64 == 0, "ap_cls_exact_update: dim %d must be a positive multiple of 64", dim);
+    AP_REQUIRE(n >= 0 && tokens > 0, "ap_cls_exact_update: bad shape (n %d, %d tokens)", n, tokens);
+    return ap::launch_cls_exact_update(dtype, cls32, branch, n, tokens, dim, x, partial, (hipStream_t)stream);
+}
+
+int ap_rowstats_finalize_cls(const float* partial, int rows, int groups, int dim, float eps, float* rowstats, int dtype, float* cls32,
+                             const float* branch, void* x, int n, int tokens, ap_stream_t stream) {
+    AP_REQUIRE(partial && rowstats, "ap_rowstats_finalize_cls: null pointer");
+    AP_REQUIRE(rows >= 0 && dim > 0 && dim % 128 == 0 && groups == dim / 64,
+               "ap_rowstats_finalize_cls: bad shape (%d rows, dim %d: a multiple of 128, groups %d = dim / 64)", rows, dim, groups);
+    AP_REQUIRE(aligned16(partial), "ap_rowstats_finalize_cls: partial must be 16-byte aligned");
+    AP_REQUIRE(!cls32 || (half_dtype(dtype) && branch && x && n > 0 && tokens > 0 && (long)n * tokens == rows),
+               "ap_rowstats_finalize_cls: exact class rows need f16 / bf16, the branch buffer, the stream and rows == n * tokens");
+    return ap::launch_rowstats_finalize_cls(partial, rows, groups, dim, eps, rowstats, dtype, cls32, branch, x, n, tokens, (hipStream_t)stream);
+}
+
 }  // extern "C"

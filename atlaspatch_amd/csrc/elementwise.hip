@@ -420,6 +420,15 @@ __device__ __forceinline__ float block_sum256(float v, float* red) {
     return r;
 }
 
+// The folds' contract is one float32 product and one rounding to T (what any IEEE host computes in float32).  Left to itself the
+// compiler selects v_fma_mixlo_f16 for (f16)(a * b), which rounds the EXACT product straight to f16: one weight in ~2^14 then
+// differs by an ulp from T(float(a * b)), and f16 and bf16 follow different arithmetic.  The empty asm keeps the f32 product.
+__device__ __forceinline__ float f32_product(float a, float b) {
+    float p = a * b;
+    asm volatile("" : "+v"(p));
+    return p;
+}
+
 // one 256-thread workgroup per weight row n
 template <typename T>
 __global__ __launch_bounds__(256) void fold_ln_kernel(const float* __restrict__ w32, int cols, int ld,
@@ -437,7 +446,7 @@ __global__ __launch_bounds__(256) void fold_ln_kernel(const float* __restrict__ 
         float wf = 0.f;
         if (k < cols) {
             const float w = src[k];
-            wf = (float)from_f32<T>(w * gamma[k]);
+            wf = (float)from_f32<T>(f32_product(w, gamma[k]));
             bs += w * beta[k];
         }
         dst[k] = from_f32<T>(wf);
@@ -459,7 +468,7 @@ __global__ __launch_bounds__(256) void fold_ls_kernel(const float* __restrict__ 
     const float sc = ls ? ls[n] : 1.0f;
     const float* src = w32 + (size_t)n * ld;
     T* dst = wout + (size_t)n * ld;
-    for (int k = threadIdx.x; k < ld; k += 256) dst[k] = from_f32<T>(k < cols ? src[k] * sc : 0.f);
+    for (int k = threadIdx.x; k < ld; k += 256) dst[k] = from_f32<T>(k < cols ? f32_product(src[k], sc) : 0.f);
     if (threadIdx.x == 0) bias_out[n] = bias_in[n] * sc;
 }
 

@@ -439,6 +439,79 @@ int ap_layernorm(int out_dtype, const float* x, long stride, int rows, int dim,
 int ap_attention(int dtype, const void* qkv, void* out, int n, int tokens, int heads, int head_dim,
                  ap_stream_t stream);
 
+/* ---- engine building blocks (additive to ABI v20) -----------------------------------------
+ * The remaining kernels ap_vit_forward_* chains, one entry point each, so that each can be held against a reference of
+ * its own.  T = the type `dtype` names.  Every function refuses (AP_ERR_INVALID, text in ap_last_error(), nothing
+ * launched) a null pointer, a size that is not positive, a type it does not serve and a layout its kernel cannot
+ * address; n = 0 or rows = 0 is an empty launch.  Pointers are 16-byte aligned unless stated.
+ *
+ * ap_attention_scaled: ap_attention with the softmax scale given (head widths stored zero-padded to 96: scale =
+ *   1 / sqrt(true width)); scale > 0.  float32: 64-wide heads, at most 288 tokens (AP_ERR_UNSUPPORTED beyond).
+ * ap_attention_cls: one query row per (image, head) -- the class row of the last block.  q T [n, heads * head_dim]
+ *   packed; k and v inside rows of kv T [n * tokens, ld] at columns koff + head * head_dim and voff + head * head_dim;
+ *   out T [n, heads * head_dim] = softmax_t(scale * q . k_t) v_t, f32 arithmetic, the maximum subtracted before the
+ *   exponential, one rounding.  head_dim 64 / 96 / 128; ld, koff, voff multiples of 8; 1 <= tokens <= 12000.  q and kv
+ *   are aligned to eight elements: 16 bytes in f16 / bf16, 32 bytes in float32.
+ * ap_attn_pool: attentional pooling with one learned query: kv T [n * tokens, 2 * heads * 64] (k | v), q f32
+ *   [heads * 64] shared by every image, out T [n, heads * 64]; scale 1 / 8.  f16 / bf16; 1 <= tokens <= 12000.
+ * ap_rope: DINOv3's rotary embedding in place on the q (which & 1) and k (which & 2) parts of the packed qkv
+ *   T [n * tokens, 3 * heads * head_dim], patch tokens only (rows >= prefix of every image), p = the patch's index:
+ *     x'[j] = x[j] cos[p][j] - x[j + h] sin[p][j],   x'[j + h] = x[j + h] cos[p][j + h] + x[j] sin[p][j + h],   h = head_dim / 2
+ *   cos / sin f32 [tokens - prefix, head_dim]; f32 arithmetic, one rounding; head_dim % 16 == 0; which 1 .. 3.
+ * ap_swiglu: out[m][j] = T(silu(x[m][j]) * x[m][h + j]), x T [rows, 2h] dense, out T [rows, h] dense; f32 arithmetic;
+ *   h % 8 == 0.
+ * ap_add2_layernorm: x[row] += delta0[row] * ls0, then += delta1[row] * ls1 (f32, in that order; either delta and
+ *   either LayerScale vector ls f32 [dim] may be NULL), then out[row] = LayerNorm(x[row]) (two-pass, biased variance,
+ *   eps inside the sqrt) in out_dtype, dense [rows, dim].  x f32 rows of `stride` elements; the deltas are rows of
+ *   delta_dtype with strides dstride0 / dstride1.  store = 1 writes the updated x back (only when a delta is given),
+ *   store = 0 leaves x untouched.  (delta, out) types: (T, T), (T, f32), (f32, f32).  dim % 4 == 0, dim <= 4096; strides
+ *   multiples of 4 (a 16-bit delta at dim 768 / 1024: of 8) and >= dim.
+ * ap_fold_ln: the LayerNorm fold of a weight matrix w32 f32 [rows, ld] (cols <= ld used): wout T [rows, ld] =
+ *   T(w32[n][k] * gamma[k]), zero for k >= cols; colsum[n] = sum_k float(wout[n][k]); bias_out[n] = bias_in[n] +
+ *   sum_k w32[n][k] * beta[k].  swiglu_h > 0 (rows = 2 swiglu_h, swiglu_h % 32 == 0): output row r is built from source row
+ *   (r % 64 < 32 ? 0 : swiglu_h) + 32 * (r / 64) + r % 32 -- AP_EPI_NORM_SWIGLU's order.  f16 / bf16.
+ * ap_fold_ls: wout T [rows, ld] = T(w32[n][k] * ls[n]), zero for k >= cols; bias_out[n] = bias_in[n] * ls[n]; ls NULL:
+ *   a plain conversion.  f16 / bf16.
+ * ap_cls_mean_pool: y f32 [n * tokens, dim] -> out f32 [n, 2 * dim] = [row 0 of the image | mean of its rows prefix ..
+ *   tokens - 1] (summed in double, one division); prefix >= 1, tokens > prefix.
+ * ap_stream_to_f32: x T rows of `stride` elements -> dst f32 [rows, dim] dense, exact.  f16 / bf16; dim, stride % 4 == 0.
+ * ap_chw_to_patchrows: x [n, 3, S, S] of x_dtype -> dst T [n * g * g, ld], g = S / ps: row (img * g + py) * g + px, column
+ *   (c * ps + ky) * ps + kx = x[img][c][py * ps + ky][px * ps + kx], one rounding; columns >= 3 ps^2 are not written.
+ *   ld >= 3 ps^2; ps % 4 == 0 needs ld % 4 == 0.
+ * ap_cls_stream: the prefix rows (class token, register tokens) of the T stream x [n * tokens, dim]:
+ *   x[img * tokens + j] = T(prefix[img * img_rows + j]), j < prefix_rows, and partial f32 [n * tokens, dim / 64, 2] =
+ *   (sum, sum of squares) per 64-column group of the rounded row.  img_rows = 0: one prefix f32 [prefix_rows, dim] for
+ *   every image; img_rows = prefix_rows: one per image.  f16 / bf16; dim % 64 == 0.
+ * ap_cls_exact_update: cls32[img] += branch[img] (f32 [n, dim] both), x[img * tokens] = T(cls32[img]) and that row's
+ *   partial sums as above.  f16 / bf16; dim % 64 == 0.
+ * ap_rowstats_finalize_cls: ap_rowstats_finalize (groups = dim / 64, dim % 128 == 0) and, when cls32 is not NULL (rows =
+ *   n * tokens), the update of ap_cls_exact_update in the same launch: the rows img * tokens get the statistics of
+ *   T(cls32[img] + branch[img]) computed from the rounded row itself, every other row those of its partial sums. */
+int ap_attention_scaled(int dtype, const void* qkv, void* out, int n, int tokens, int heads, int head_dim, float scale,
+                        ap_stream_t stream);
+int ap_attention_cls(int dtype, const void* q, const void* kv, int ld, int koff, int voff, void* out, int n, int tokens,
+                     int heads, int head_dim, float scale, ap_stream_t stream);
+int ap_attn_pool(int dtype, const void* kv, const float* q, void* out, int n, int tokens, int heads, ap_stream_t stream);
+int ap_rope(int dtype, void* qkv, int n, int tokens, int prefix, int heads, int head_dim, const float* cos, const float* sin,
+            int which, ap_stream_t stream);
+int ap_swiglu(int dtype, const void* x, int rows, int h, void* out, ap_stream_t stream);
+int ap_add2_layernorm(int delta_dtype, int out_dtype, float* x, long stride, const void* delta0, long dstride0, const float* ls0,
+                      const void* delta1, long dstride1, const float* ls1, int store, int rows, int dim, const float* gamma,
+                      const float* beta, float eps, void* out, ap_stream_t stream);
+int ap_fold_ln(int dtype, const float* w32, int rows, int cols, int ld, const float* gamma, const float* beta,
+               const float* bias_in, void* wout, float* colsum, float* bias_out, int swiglu_h, ap_stream_t stream);
+int ap_fold_ls(int dtype, const float* w32, int rows, int cols, int ld, const float* ls, const float* bias_in, void* wout,
+               float* bias_out, ap_stream_t stream);
+int ap_cls_mean_pool(const float* y, int n, int tokens, int prefix, int dim, float* out, ap_stream_t stream);
+int ap_stream_to_f32(int dtype, const void* x, long stride, int rows, int dim, float* dst, ap_stream_t stream);
+int ap_chw_to_patchrows(int x_dtype, int dtype, const void* x, int n, int S, int ps, void* dst, int ld, ap_stream_t stream);
+int ap_cls_stream(int dtype, const float* prefix, int prefix_rows, int img_rows, int n, int tokens, int dim, void* x,
+                  float* partial, ap_stream_t stream);
+int ap_cls_exact_update(int dtype, float* cls32, const float* branch, int n, int tokens, int dim, void* x, float* partial,
+                        ap_stream_t stream);
+int ap_rowstats_finalize_cls(const float* partial, int rows, int groups, int dim, float eps, float* rowstats, int dtype,
+                             float* cls32, const float* branch, void* x, int n, int tokens, ap_stream_t stream);
+
 /* ---- ResNet encoder (additive to ABI v20) ------------------------------------------------
  * Replaces the torchvision resnet18 / 34 / 50 / 101 / 152 forward of models/patch/resnet.py (fc = Identity: the flattened
  * global average pool) with the implicit-GEMM convolution kernels of conv.hip.  Activations are NHWC in the compute type;

@@ -841,7 +841,8 @@ _NO_OPERATOR_TEST = [
     (r"ap_abi_version", "library lifecycle: _lib.load() refuses a library that reports another ABI"),
     (r"ap_device_info", "host query of the runtime, no kernel"),
     (r"ap_host_\w+", "host-only entry points (tile ring, passports, OpenSlide): no device work; CPU tests call them"),
-    (r"ap_(vit|resnet|convnext)_\w+", "engine object lifecycle / forward: driven through the Python engines by the network tests"),
+    (r"ap_(vit|resnet|convnext)_\w+", "engine object lifecycle / forward: driven through the Python engines by the network tests; the engines' building blocks "
+                                      "are exported one by one and tested in test_gpu_vit_ops.py"),
     (r"ap_gemm_trace", "diagnostic switch of the instrumented GEMM twin, which is not in the product library"),
     (r"ap_pillow_reduce_u8", "called through utils.resample.pillow_reduce_device, which test_segmentation_device.py checks against Pillow"),
     (r"ap_tile_content_counts", "called through utils.image, which test_gpu_ops.py checks against the cv2 restatement"),
