@@ -47,6 +47,12 @@ class VitConfig(C.Structure):
         super().__init__(C.sizeof(type(self)), *args, **kw)
 
 
+class VitConfigEx(VitConfig):
+    """``ap_vit_config_ex``: the same bytes followed by the fields appended since ABI v20 (zero = the behaviour before the field
+    existed).  ``struct_size`` records the longer size; ``ap_vit_create`` takes either."""
+    _fields_ = [("no_class_token", C.c_int)]
+
+
 class ResnetConfig(C.Structure):
     """``ap_resnet_config`` (additive to ABI v20); ``struct_size`` is filled in here."""
     _fields_ = [("struct_size", C.c_uint32), ("block", C.c_int), ("depths", C.c_int * 4), ("stem_width", C.c_int),
@@ -192,6 +198,8 @@ SIGNATURES = {
     "ap_attention_cls": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_float, C.c_void_p]),
     "ap_attn_pool": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "ap_attention_probe": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, C.c_float, C.c_void_p]),
     "ap_rope": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                           C.c_void_p]),
     "ap_swiglu": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

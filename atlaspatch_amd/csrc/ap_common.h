@@ -90,6 +90,18 @@ __device__ __forceinline__ f32x2_t quick_gelu2(f32x2_t x) {
     return x * f32x2_t{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
 }
 
+// SigLIP's tanh GELU (models/patch/medsiglip.py; transformers "gelu_pytorch_tanh"): 0.5 x (1 + tanh(u)), u = sqrt(2 / pi) (x + 0.044715 x^3),
+// written x * sigmoid(2 u) = x / (1 + 2^(-2 log2(e) u)): two values, f32, one exp2 and one rcp each and no tanh.  -2 log2(e) sqrt(2 / pi)
+// is folded into the cubic's two constants: z = x * (kA + kB x^2).  Large |x|: x^2 or z may reach +-inf, never NaN (x = 0 gives z = 0):
+// 2^z -> 0 and the result -> x, or 2^z -> inf, rcp -> 0 and the result -> -0.  Both GEMM kernels call THIS routine.
+__device__ __forceinline__ f32x2_t gelu_tanh2(f32x2_t x) {
+    constexpr float kA = -2.0f * 1.4426950408889634f * 0.7978845608028654f, kB = kA * 0.044715f;
+    const f32x2_t t = x * x;
+    const f32x2_t z = x * __builtin_elementwise_fma(t, f32x2_t{kB, kB}, f32x2_t{kA, kA});
+    const f32x2_t d = f32x2_t{1.0f, 1.0f} + f32x2_t{__builtin_amdgcn_exp2f(z[0]), __builtin_amdgcn_exp2f(z[1])};
+    return x * f32x2_t{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+}
+
 // silu(a) * b for two values, f32 (exp2 + rcp; both GEMM kernels call THIS routine so that they stay bit-identical)
 __device__ __forceinline__ f32x2_t swiglu2(f32x2_t a, f32x2_t b) {
     const f32x2_t z = a * f32x2_t{-1.4426950408889634f, -1.4426950408889634f};
@@ -125,6 +137,8 @@ enum GemmEpilogue {
     EPI_NORM_SWIGLU = 8,
     EPI_NORM_QGELU = 9,    // EPI_NORM_GELU with CLIP's QuickGELU x * sigmoid(1.702 x)
     EPI_BIAS_QGELU = 10,   // EPI_BIAS_GELU likewise
+    EPI_NORM_GTANH = 11,   // EPI_NORM_GELU with SigLIP's tanh GELU (gelu_tanh2)
+    EPI_BIAS_GTANH = 12,   // EPI_BIAS_GELU likewise
 };
 
 struct GemmArgs {
@@ -205,6 +219,9 @@ int launch_attention_cls(int dtype, const void* q, const void* kv, int ld, int k
                          int tokens, int heads, int head_dim, float scale, hipStream_t stream);
 int launch_attn_pool(int dtype, const void* kv, const float* q, void* out, int n, int tokens, int heads,
                      hipStream_t stream);
+// launch_attention_cls with one f32 query [heads * head_dim] shared by every image (SigLIP's attention-pooling head)
+int launch_attention_probe(int dtype, const float* q, const void* kv, int ld, int koff, int voff, void* out, int n,
+                           int tokens, int heads, int head_dim, float scale, hipStream_t stream);
 // ---- fused-LayerNorm path (16-bit residual stream) ---------------------------------------
 // tok f32 [rows, dim] (dense) -> x T [rows, dim] and rowstats f32 [rows, 2] = (rstd, -mean * rstd) of the ROUNDED row
 int launch_stream_init(int dtype, const float* tok, int rows, int dim, float eps, void* x, float* rowstats,

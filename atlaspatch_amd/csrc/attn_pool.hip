@@ -8,6 +8,7 @@
 // eight 16-byte loads) and leaves the scaled score in LDS; block max / sum; pass 2: thread = (channel,
 // token group of 4), so a wave reads one 128-byte V row per step; the four groups are reduced through LDS.
 // HBM-bound: k and v are read once (2 * tokens * 128 B per head).
+#include <type_traits>
 #include "ap_common.h"
 
 namespace ap {
@@ -88,12 +89,19 @@ __global__ __launch_bounds__(256) void attn_pool_kernel(const T* __restrict__ kv
 // [tokens x tokens] one.   q : T [n, heads * 64] (the CLS rows' projected queries, packed),
 // kv rows: T [n * tokens, ld] with k at column koff + head * 64 and v at voff + head * 64; out : T [n, heads * 64].
 // Same structure as the pooler above (scores in LDS, block softmax in f32, V rows streamed).
+//
+// PROBE = true (ap_attention_probe): ONE float32 query q [heads * HD] shared by every image instead of a row per image in T --
+// the pooling step of SigLIP's attention-pooling head (transformers SiglipMultiheadAttentionPoolingHead, models/patch/medsiglip.py:
+// the probe's projected query is input independent, the host computes it once).  Everything after the query load is the same code.
+// HBM-bound: k and v are read once, 2 * tokens * HD * sizeof(T) bytes per (image, head) (the real model: 1024 tokens, 16 heads
+// stored 96 wide, f16 = 6.3 MB per image; the scores and the query stay in LDS / registers); out adds HD * sizeof(T).
 template <typename T> struct RowVec { using v8 = typename PoolVec<T>::v8; };
 template <> struct RowVec<float> { typedef float v8 __attribute__((ext_vector_type(8))); };
 
-template <typename T, int HD>
-__global__ __launch_bounds__(256) void attn_cls_kernel(const T* __restrict__ q, const T* __restrict__ kv, int ld, int koff,
-                                                       int voff, T* __restrict__ out, int tokens, int heads, float scale) {
+template <typename T, int HD, bool PROBE = false>
+__global__ __launch_bounds__(256) void attn_cls_kernel(const std::conditional_t<PROBE, float, T>* __restrict__ q, const T* __restrict__ kv,
+                                                       int ld, int koff, int voff, T* __restrict__ out, int tokens, int heads,
+                                                       float scale) {
     // thread = (row slot r of kRows, channel octet sub of kSub): every K / V access is a 16-byte load and a wave covers
     // whole rows per step (HD = 64: eight 128-byte rows; HD = 128: four 256-byte rows; HD = 96: four 192-byte rows, the octets
     // 12 .. 15 of a row slot idle -- kSub stays a power of two for the lane exchanges)
@@ -111,7 +119,12 @@ __global__ __launch_bounds__(256) void attn_cls_kernel(const T* __restrict__ q, 
     const T* kbase = kv + (size_t)img * tokens * ld + koff + head * HD + subc * 8;
     const T* vbase = kv + (size_t)img * tokens * ld + voff + head * HD + subc * 8;
     float qr[8];
-    {
+    if constexpr (PROBE) {
+        const float* qp = q + head * HD + subc * 8;                   // 32-byte steps from a 16-byte aligned base: two 16-byte loads
+        const f32x4 q0 = *(const f32x4*)qp, q1 = *(const f32x4*)(qp + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { qr[e] = oct ? q0[e] : 0.f; qr[4 + e] = oct ? q1[e] : 0.f; }
+    } else {
         const V8 qq = *(const V8*)(q + (size_t)img * P + head * HD + subc * 8);
 #pragma unroll
         for (int e = 0; e < 8; ++e) qr[e] = oct ? (float)qq[e] : 0.f;
@@ -190,6 +203,26 @@ int launch_attention_cls(int dtype, const void* q, const void* kv, int ld, int k
     else { set_error("attention_cls: unsupported dtype %d", dtype); return AP_ERR_INVALID; }
 #undef AP_CLS_HD
 #undef AP_CLS
+    AP_HIP_CHECK(hipGetLastError());
+    return AP_OK;
+}
+
+int launch_attention_probe(int dtype, const float* q, const void* kv, int ld, int koff, int voff, void* out, int n,
+                           int tokens, int heads, int head_dim, float scale, hipStream_t stream) {
+    AP_REQUIRE(head_dim == 64 || head_dim == 96 || head_dim == 128, "attention_probe: head_dim %d unsupported (64 / 96 / 128)", head_dim);
+    AP_REQUIRE(tokens > 0 && tokens <= 12000, "attention_probe: %d tokens unsupported", tokens);
+    AP_REQUIRE(ld % 8 == 0 && koff % 8 == 0 && voff % 8 == 0, "attention_probe: misaligned layout");
+    if (n <= 0) return AP_OK;
+    const size_t lds = ((size_t)((tokens + 3) & ~3) + 4 + 32 * 64) * sizeof(float);       // as launch_attention_cls
+    dim3 grid(n * heads), block(256);
+#define AP_PROBE(T, HD) attn_cls_kernel<T, HD, true><<<grid, block, lds, stream>>>(q, (const T*)kv, ld, koff, voff, (T*)out, tokens, heads, scale)
+#define AP_PROBE_HD(T) do { if (head_dim == 64) AP_PROBE(T, 64); else if (head_dim == 96) AP_PROBE(T, 96); else AP_PROBE(T, 128); } while (0)
+    if (dtype == AP_F16) AP_PROBE_HD(f16);
+    else if (dtype == AP_BF16) AP_PROBE_HD(bf16);
+    else if (dtype == AP_F32) AP_PROBE_HD(float);
+    else { set_error("attention_probe: unsupported dtype %d", dtype); return AP_ERR_INVALID; }
+#undef AP_PROBE_HD
+#undef AP_PROBE
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }

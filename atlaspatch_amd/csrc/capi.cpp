@@ -160,8 +160,8 @@ int ap_gemm(int dtype, int epilogue, const void* A, int lda, const void* W, int 
             int K, const float* bias, const float* gamma, void* out, int ldo, int impl, int variant,
             ap_stream_t stream) {
     AP_REQUIRE(A && W && bias && out, "ap_gemm: null pointer");
-    AP_REQUIRE(epilogue == AP_EPI_BIAS || epilogue == AP_EPI_BIAS_GELU || epilogue == AP_EPI_BIAS_RESID || epilogue == AP_EPI_BIAS_QUICK_GELU,
-               "ap_gemm: unknown epilogue %d", epilogue);
+    AP_REQUIRE(epilogue == AP_EPI_BIAS || epilogue == AP_EPI_BIAS_GELU || epilogue == AP_EPI_BIAS_RESID || epilogue == AP_EPI_BIAS_QUICK_GELU ||
+               epilogue == AP_EPI_BIAS_GELU_TANH, "ap_gemm: unknown epilogue %d", epilogue);
     AP_REQUIRE(dtype == AP_F16 || dtype == AP_BF16 || dtype == AP_F32, "ap_gemm: unknown dtype %d", dtype);
     ap::GemmArgs g{};
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.M = M; g.N = N; g.K = K;
@@ -232,6 +232,7 @@ int ap_gemm_fused(int dtype, int epilogue, const void* A, int lda, const void* W
     else if (epilogue == AP_EPI_NORM_GELU) epi = ap::EPI_NORM_GELU;
     else if (epilogue == AP_EPI_NORM_SWIGLU) epi = ap::EPI_NORM_SWIGLU;
     else if (epilogue == AP_EPI_NORM_QUICK_GELU) epi = ap::EPI_NORM_QGELU;
+    else if (epilogue == AP_EPI_NORM_GELU_TANH) epi = ap::EPI_NORM_GTANH;
     else if (epilogue == AP_EPI_RESID_STATS) epi = ap::EPI_RESID_STATS;
     else { ap::set_error("ap_gemm_fused: unknown epilogue %d", epilogue); return AP_ERR_INVALID; }
     AP_REQUIRE(epi == ap::EPI_RESID_STATS ? partial != nullptr : (colsum && rowstats), "ap_gemm_fused: missing operand for epilogue %d", epilogue);
@@ -304,6 +305,22 @@ int ap_attention_cls(int dtype, const void* q, const void* kv, int ld, int koff,
                "ap_attention_cls: q / kv must be aligned to 8 elements");
     AP_REQUIRE(std::isfinite(scale), "ap_attention_cls: scale must be finite");
     return ap::launch_attention_cls(dtype, q, kv, ld, koff, voff, out, n, tokens, heads, head_dim, scale, (hipStream_t)stream);
+}
+
+int ap_attention_probe(int dtype, const float* q, const void* kv, int ld, int koff, int voff, void* out, int n, int tokens,
+                       int heads, int head_dim, float scale, ap_stream_t stream) {
+    AP_REQUIRE(q && kv && out, "ap_attention_probe: null pointer");
+    AP_REQUIRE(known_dtype(dtype), "ap_attention_probe: unknown dtype %d", dtype);
+    AP_REQUIRE(head_dim == 64 || head_dim == 96 || head_dim == 128, "ap_attention_probe: head_dim %d unsupported (64 / 96 / 128)", head_dim);
+    AP_REQUIRE(n >= 0 && heads > 0 && heads <= (1 << 16), "ap_attention_probe: bad shape (n %d, %d heads)", n, heads);
+    AP_REQUIRE(tokens > 0 && tokens <= 12000, "ap_attention_probe: %d tokens unsupported (1 .. 12000)", tokens);
+    const long width = (long)heads * head_dim;
+    AP_REQUIRE(ld > 0 && ld % 8 == 0 && koff >= 0 && voff >= 0 && koff % 8 == 0 && voff % 8 == 0 && koff + width <= ld && voff + width <= ld,
+               "ap_attention_probe: k / v (offsets %d / %d, %ld wide) must lie inside rows of %d elements, all multiples of 8", koff, voff, width, ld);
+    AP_REQUIRE(aligned16(q) && aligned16(kv) && (dtype != AP_F32 || ((uintptr_t)kv & 31) == 0),
+               "ap_attention_probe: q must be 16-byte aligned and kv aligned to 8 elements");
+    AP_REQUIRE(std::isfinite(scale), "ap_attention_probe: scale must be finite");
+    return ap::launch_attention_probe(dtype, q, kv, ld, koff, voff, out, n, tokens, heads, head_dim, scale, (hipStream_t)stream);
 }
 
 int ap_attn_pool(int dtype, const void* kv, const float* q, void* out, int n, int tokens, int heads, ap_stream_t stream) {

@@ -214,7 +214,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
         for (int g4 = 0; g4 < 4; ++g4) {
             const int nb = n0 + wave_n * 64 + nt * 32 + g4 * 8 + hi * 4;
             const f32x4 b4 = !SPLIT || (nb < g.N && g.bias) ? *(const f32x4*)(g.bias + nb) : f32x4{0.f, 0.f, 0.f, 0.f};
-            constexpr bool kNormInit = EPI == EPI_NORM_STORE || EPI == EPI_NORM_GELU || EPI == EPI_NORM_SWIGLU || EPI == EPI_NORM_QGELU;   // (these start from zero)
+            constexpr bool kNormInit = EPI == EPI_NORM_STORE || EPI == EPI_NORM_GELU || EPI == EPI_NORM_SWIGLU || EPI == EPI_NORM_QGELU || EPI == EPI_NORM_GTANH;   // (these start from zero)
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
         }
         return;
     }
-    if constexpr (sizeof(T) == 2 && (EPI == EPI_NORM_STORE || EPI == EPI_NORM_GELU || EPI == EPI_NORM_QGELU)) {
+    if constexpr (sizeof(T) == 2 && (EPI == EPI_NORM_STORE || EPI == EPI_NORM_GELU || EPI == EPI_NORM_QGELU || EPI == EPI_NORM_GTANH)) {
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             const int m = m0 + wave_m * 64 + mt * 32 + l31;
@@ -376,6 +376,10 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
                     }
                     if constexpr (EPI == EPI_NORM_QGELU) {
                         const f32x2_t a = quick_gelu2(f32x2_t{v[0], v[1]}), b = quick_gelu2(f32x2_t{v[2], v[3]});
+                        v = f32x4{a[0], a[1], b[0], b[1]};
+                    }
+                    if constexpr (EPI == EPI_NORM_GTANH) {
+                        const f32x2_t a = gelu_tanh2(f32x2_t{v[0], v[1]}), b = gelu_tanh2(f32x2_t{v[2], v[3]});
                         v = f32x4{a[0], a[1], b[0], b[1]};
                     }
                     store4<T>((T*)g.out + (size_t)m * (size_t)g.ldo + n, v);
@@ -502,6 +506,21 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
                         for (int e = 0; e < 4; ++e) v[e] = v[e] / (1.0f + expf(-1.702f * v[e]));
                     }
                     store4<T>((T*)g.out + orow + n, v);
+                } else if constexpr (EPI == EPI_BIAS_GTANH) {
+                    if constexpr (sizeof(T) == 2) {      // the packed routine of gemm256 (bit-identical)
+                        const f32x2_t lo = gelu_tanh2(f32x2_t{v[0], v[1]}), hi2 = gelu_tanh2(f32x2_t{v[2], v[3]});
+                        v = f32x4{lo[0], lo[1], hi2[0], hi2[1]};
+                    } else {
+                        // float32: x / (1 + exp(-2 u)) with libm expf keeps the RELATIVE accuracy in the negative tail, where
+                        // 1 + tanhf(u) cancels; u = sqrt(2 / pi) (x + 0.044715 x^3) by two fma
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float x = v[e];
+                            const float u2 = -1.5957691216057308f * fmaf(0.044715f * x * x, x, x);
+                            v[e] = x / (1.0f + expf(u2));
+                        }
+                    }
+                    store4<T>((T*)g.out + orow + n, v);
                 } else if constexpr (EPI == EPI_BIAS_RESID) {
                     float* dst = (float*)g.out + orow + n;
                     f32x4 r = *(const f32x4*)dst;
@@ -534,6 +553,7 @@ int launch_split(int epilogue, const GemmArgs& a, hipStream_t stream) {
         case EPI_BIAS_RESID: gemm_kernel<float, EPI_BIAS_RESID, true><<<grid, block, 0, stream>>>(a); break;
         case EPI_PATCH_EMBED: gemm_kernel<float, EPI_PATCH_EMBED, true><<<grid, block, 0, stream>>>(a); break;
         case EPI_BIAS_QGELU: gemm_kernel<float, EPI_BIAS_QGELU, true><<<grid, block, 0, stream>>>(a); break;
+        case EPI_BIAS_GTANH: gemm_kernel<float, EPI_BIAS_GTANH, true><<<grid, block, 0, stream>>>(a); break;
         default: set_error("gemm: epilogue %d has no split-f16 form", epilogue); return AP_ERR_INVALID;
     }
     AP_HIP_CHECK(hipGetLastError());
@@ -554,6 +574,8 @@ int launch_typed(int epilogue, const GemmArgs& a, hipStream_t stream) {
         case EPI_NORM_SWIGLU: gemm_kernel<T, EPI_NORM_SWIGLU><<<grid, block, 0, stream>>>(a); break;
         case EPI_NORM_QGELU: gemm_kernel<T, EPI_NORM_QGELU><<<grid, block, 0, stream>>>(a); break;
         case EPI_BIAS_QGELU: gemm_kernel<T, EPI_BIAS_QGELU><<<grid, block, 0, stream>>>(a); break;
+        case EPI_NORM_GTANH: gemm_kernel<T, EPI_NORM_GTANH><<<grid, block, 0, stream>>>(a); break;
+        case EPI_BIAS_GTANH: gemm_kernel<T, EPI_BIAS_GTANH><<<grid, block, 0, stream>>>(a); break;
         case EPI_RESID_STATS: gemm_kernel<T, EPI_RESID_STATS><<<grid, block, 0, stream>>>(a); break;
         case EPI_PATCH_STREAM: gemm_kernel<T, EPI_PATCH_STREAM><<<grid, block, 0, stream>>>(a); break;
         default: set_error("gemm: unknown epilogue %d", epilogue); return AP_ERR_INVALID;
@@ -582,11 +604,11 @@ int launch_gemm_impl(int dtype, int epilogue, const GemmArgs& a, int impl, int v
 #endif
     }
     const bool fused_epi = epilogue == EPI_NORM_STORE || epilogue == EPI_NORM_GELU || epilogue == EPI_NORM_SWIGLU || epilogue == EPI_NORM_QGELU ||
-                           epilogue == EPI_RESID_STATS ||
+                           epilogue == EPI_NORM_GTANH || epilogue == EPI_RESID_STATS ||
                            epilogue == EPI_PATCH_STREAM;
     AP_REQUIRE(!fused_epi || dtype != AP_F32, "gemm: the fused-LayerNorm epilogues are f16 / bf16 only");
     AP_REQUIRE(!fused_epi || (epilogue == EPI_RESID_STATS ? a.partial != nullptr :
-                              epilogue == EPI_PATCH_STREAM ? (a.partial && a.pos16 && a.P > 0 && a.R > 0) : (a.colsum && a.rowstats)),
+                              epilogue == EPI_PATCH_STREAM ? (a.partial && a.pos16 && a.P > 0 && a.R >= 0) : (a.colsum && a.rowstats)),
                "gemm: missing operand for the fused-LayerNorm epilogue %d", epilogue);
     // Kernel choice (results are bit-identical either way).  The persistent 256 x 256 kernel needs about one tile per CU to
     // pay: with few row tiles and a narrow N (proj / fc2 of a 32-tile extract_batch: 75 tiles for 256 CUs) the 128 x 128

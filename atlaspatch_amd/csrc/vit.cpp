@@ -45,12 +45,17 @@ struct PoolParams {
     const float *ln_k_w, *ln_k_b, *kv_b, *q, *out_b, *ln_out_w, *ln_out_b;
     const Param *kv, *out;
 };
+// AP_POOL_MAP: SigLIP's attention-pooling head (map.* parameters)
+struct MapParams {
+    const float *q, *kv_b, *out_b, *ln_w, *ln_b, *fc1_b, *fc2_b;
+    const Param *kv, *out, *fc1, *fc2;
+};
 }  // namespace ap
 
 struct ap_vit {
     ap_vit_config cfg;
     int grid = 0, patches = 0, tokens = 0, kpe = 0;
-    int prefix = 1;                         // class token + register tokens
+    int prefix = 1;                         // class token + register tokens (0: no_class_token)
     int pos_rows = 0, pos_row0 = 1;         // rows of pos_embed; the row that belongs to patch 0
     int hd = 64, dattn = 0;                 // head width as stored (64 / 128), heads * hd = width of q, k, v and of proj's input
     int fc1_rows = 0;                       // mlp_dim (GELU) or 2 * mlp_dim (SwiGLU packed)
@@ -61,6 +66,7 @@ struct ap_vit {
     // resolved at finalize
     std::vector<ap::BlockParams> blocks;
     ap::PoolParams pool{};
+    ap::MapParams map{};
     const ap::Param* pe_w = nullptr;
     const float *pe_b = nullptr, *cls = nullptr, *pos = nullptr, *norm_w = nullptr, *norm_b = nullptr;
     const float *pre_w = nullptr, *pre_b = nullptr;        // CLIP ln_pre
@@ -139,6 +145,7 @@ void set_weight(const ap_vit* m, ap::GemmArgs& g, const Param* p, int row0 = 0, 
 int fc1_epilogue(const ap_vit_config& c, bool folded) {
     if (c.mlp_type == AP_MLP_SWIGLU) return folded ? ap::EPI_NORM_SWIGLU : ap::EPI_BIAS_STORE;
     if (c.act == AP_ACT_QUICK_GELU) return folded ? ap::EPI_NORM_QGELU : ap::EPI_BIAS_QGELU;
+    if (c.act == AP_ACT_GELU_TANH) return folded ? ap::EPI_NORM_GTANH : ap::EPI_BIAS_GTANH;
     return folded ? ap::EPI_NORM_GELU : ap::EPI_BIAS_GELU;
 }
 
@@ -203,6 +210,7 @@ int patch_embed(ap_vit* m, int n, const Workspace& w, hipStream_t stream) {
     g.out = w.tok; g.ldo = D; g.P = m->patches; g.R = m->prefix; g.pos_row0 = m->pos_row0;
     { ScopedTimer t(m->prof, AP_PROF_GEMM_PATCH_EMBED, stream);
       if ((rc = ap::launch_gemm(dt, ap::EPI_PATCH_EMBED, g, stream)) != AP_OK) return rc; }
+    if (m->prefix == 0) return AP_OK;                  // no_class_token: every row is a patch row
     return ap::launch_cls_init(w.tok, m->prefix_dev, m->prefix, n, m->tokens, D, stream);
 }
 
@@ -220,7 +228,8 @@ int patch_embed_stream(ap_vit* m, int n, const Workspace& w, hipStream_t stream)
     { ScopedTimer t(m->prof, AP_PROF_GEMM_PATCH_EMBED, stream);
       if ((rc = ap::launch_gemm(dt, ap::EPI_PATCH_STREAM, g, stream)) != AP_OK) return rc; }
     ScopedTimer t(m->prof, AP_PROF_LAYERNORM, stream);
-    if ((rc = ap::launch_cls_stream(dt, m->prefix_dev, m->prefix, 0, n, m->tokens, D, w.x16, w.partial, stream)) != AP_OK) return rc;
+    // (no_class_token: the epilogue has written every row of the stream and of the partial sums)
+    if (m->prefix > 0 && (rc = ap::launch_cls_stream(dt, m->prefix_dev, m->prefix, 0, n, m->tokens, D, w.x16, w.partial, stream)) != AP_OK) return rc;
     return ap::launch_rowstats_finalize(w.partial, n * m->tokens, D / 64, D, c.ln_eps, w.rowstats, stream);
 }
 
@@ -520,6 +529,45 @@ int run_blocks(ap_vit* m, int n, const Workspace& w, float* out, hipStream_t str
                                         n, D, m->norm_w,
                                         m->norm_b, c.ln_eps, out, stream);
 
+    if (c.pool == AP_POOL_MAP) {
+        // ---- SigLIP's attention-pooling head (transformers SiglipMultiheadAttentionPoolingHead): final LN on all tokens in the
+        // compute type (xn, the kv GEMM's A operand), kv T [M, 2 DA] in qkv, the probe's attention per (image, head) (att, T [n, DA]),
+        // out_proj into the caller's buffer in f32 (r), LayerNorm(r) (xn, T [n, D]), fc1 + tanh GELU (hid, T [n, H]) and fc2 added
+        // to r in place in f32.  The n-row GEMMs run on the 128 x 128 kernel (cls_tail_rows).
+        const int DA = m->dattn, H = c.mlp_dim;
+        const ap::MapParams& mp = m->map;
+        { ScopedTimer t(m->prof, AP_PROF_LAYERNORM, stream);
+          if ((rc = ap::launch_add_layernorm(dt, dt, w.tok, D, pending, D, pending_ls, M, D, m->norm_w, m->norm_b, c.ln_eps, w.xn,
+                                             stream)) != AP_OK) return rc; }
+        ScopedTimer t(m->prof, AP_PROF_CLS_TAIL, stream);
+        {
+            ap::GemmArgs g{};
+            g.A = w.xn; g.lda = D; set_weight(m, g, mp.kv); g.M = M; g.N = 2 * DA; g.K = D;
+            g.bias = mp.kv_b; g.out = w.qkv; g.ldo = 2 * DA;
+            if ((rc = ap::launch_gemm(dt, ap::EPI_BIAS_STORE, g, stream)) != AP_OK) return rc;
+        }
+        if ((rc = ap::launch_attention_probe(dt, mp.q, w.qkv, 2 * DA, 0, DA, w.att, n, m->tokens, c.heads, m->hd, m->attn_scale,
+                                             stream)) != AP_OK) return rc;
+        AP_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)n * D * sizeof(float), stream));
+        {
+            ap::GemmArgs g{};
+            g.A = w.att; g.lda = DA; set_weight(m, g, mp.out); g.M = n; g.N = D; g.K = DA;
+            g.bias = mp.out_b; g.out = out; g.ldo = D;
+            if ((rc = ap::launch_gemm_impl(dt, ap::EPI_BIAS_RESID, g, 128, 0, stream)) != AP_OK) return rc;    // r = 0 + (acc + bias), f32
+        }
+        if ((rc = ap::launch_layernorm(dt, out, D, n, D, mp.ln_w, mp.ln_b, c.ln_eps, w.xn, stream)) != AP_OK) return rc;
+        {
+            ap::GemmArgs g{};
+            g.A = w.xn; g.lda = D; set_weight(m, g, mp.fc1); g.M = n; g.N = H; g.K = D;
+            g.bias = mp.fc1_b; g.out = w.hid; g.ldo = H;
+            if ((rc = ap::launch_gemm_impl(dt, ap::EPI_BIAS_GTANH, g, 128, 0, stream)) != AP_OK) return rc;
+        }
+        ap::GemmArgs g{};
+        g.A = w.hid; g.lda = H; set_weight(m, g, mp.fc2); g.M = n; g.N = D; g.K = H;
+        g.bias = mp.fc2_b; g.out = out; g.ldo = D;
+        return ap::launch_gemm_impl(dt, ap::EPI_BIAS_RESID, g, 128, 0, stream);                             // out = r + (acc + bias), f32
+    }
+
     // the other poolings: final LN on ALL tokens (y f32 [M, D], reuses qkv)
     float* y = (float*)w.qkv;
     if ((rc = ap::launch_add_layernorm(dt, AP_F32, w.tok, D, pending, D, pending_ls, M, D, m->norm_w, m->norm_b, c.ln_eps, y,
@@ -612,7 +660,18 @@ int ap_vit_config_init(ap_vit_config* cfg, size_t sizeof_caller) {
 
 int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
     AP_REQUIRE(cfg && out, "vit_create: null argument");
-    static_assert(sizeof(ap_vit_config) == AP_VIT_CONFIG_SIZE_V20, "ap_vit_config grew: append only, keep AP_VIT_CONFIG_SIZE_V20, and drop this assert");
+    static_assert(sizeof(ap_vit_config) == AP_VIT_CONFIG_SIZE_V20, "ap_vit_config is fixed at its ABI v20 fields: append to ap_vit_config_ex");
+    static_assert(sizeof(ap_vit_config_ex) == AP_VIT_CONFIG_SIZE_EX, "ap_vit_config_ex grew: append only, and accept its earlier size below");
+    // The hand-over has had two sizes: ap_vit_config (AP_VIT_CONFIG_SIZE_V20) and ap_vit_config_ex (the same bytes + the fields
+    // appended since).  The longer one's tail is taken here, and its base goes through the size rules as the shorter one.
+    ap_vit_config_ex ex;
+    memset(&ex, 0, sizeof(ex));
+    if (cfg->struct_size == AP_VIT_CONFIG_SIZE_EX) {
+        memcpy(&ex, cfg, sizeof(ex));
+        ex.base.struct_size = AP_VIT_CONFIG_SIZE_V20;
+        cfg = &ex.base;
+    }
+    const int nct = ex.no_class_token;
     // A binding written for ABI <= 19 (no size member, image_size first) presents 224 / 448 / 518 here: only sizes up to 64 bytes
     // past this library's count as a newer caller, so that one is refused as invalid, unread.
     ap_vit_config c;
@@ -634,7 +693,20 @@ int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
     AP_REQUIRE(c.depth > 0, "vit_create: depth %d", c.depth);
     AP_REQUIRE(c.compute_dtype == AP_F16 || c.compute_dtype == AP_BF16 || c.compute_dtype == AP_F32,
                "vit_create: compute dtype %d", c.compute_dtype);
-    AP_REQUIRE(c.pool == AP_POOL_CLS || c.pool == AP_POOL_ATTN || c.pool == AP_POOL_CLS_MEAN, "vit_create: pool %d", c.pool);
+    AP_REQUIRE(c.pool == AP_POOL_CLS || c.pool == AP_POOL_ATTN || c.pool == AP_POOL_CLS_MEAN || c.pool == AP_POOL_MAP,
+               "vit_create: pool %d", c.pool);
+    AP_REQUIRE(nct == 0 || nct == 1, "vit_create: no_class_token %d", nct);
+    if (nct) {
+        AP_REQUIRE(c.pool == AP_POOL_MAP, "vit_create: no_class_token needs a pooling that reads no class row (AP_POOL_MAP), not pool %d", c.pool);
+        AP_REQUIRE(c.reg_tokens == 0, "vit_create: no_class_token with reg_tokens %d: register tokens follow a class token", c.reg_tokens);
+        AP_REQUIRE(c.pre_norm == 0, "vit_create: no_class_token with pre_norm is not part of this build");
+        AP_REQUIRE(c.rope == 0, "vit_create: no_class_token with rope is not part of this build");
+    }
+    if (c.pool == AP_POOL_MAP) {
+        AP_REQUIRE(nct == 1, "vit_create: pool %d (AP_POOL_MAP) on a sequence with a class token is not part of this build: it goes with "
+                   "no_class_token (ap_vit_config_ex)", c.pool);
+        AP_REQUIRE(c.proj_dim == 0, "vit_create: AP_POOL_MAP has no projection (proj_dim %d)", c.proj_dim);
+    }
     if (c.pool == AP_POOL_ATTN) {
         AP_REQUIRE(c.compute_dtype != AP_F32, "vit_create: the attentional pooler runs in float16 / bfloat16 only");
         AP_REQUIRE(c.pool_heads > 0 && c.pool_dim == c.pool_heads * 64 && c.pool_dim % 128 == 0 &&
@@ -642,11 +714,12 @@ int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
                    "vit_create: pool_dim %d / pool_heads %d (heads of 64, multiple of 128)", c.pool_dim, c.pool_heads);
     }
     AP_REQUIRE(c.rope == 0 || (c.head_dim == 0 || c.head_dim * c.heads == c.dim), "vit_create: rope needs the true head width");
-    AP_REQUIRE(c.act == AP_ACT_GELU || (c.act == AP_ACT_QUICK_GELU && c.mlp_type == AP_MLP_GELU), "vit_create: act %d", c.act);
+    AP_REQUIRE(c.act == AP_ACT_GELU || ((c.act == AP_ACT_QUICK_GELU || c.act == AP_ACT_GELU_TANH) && c.mlp_type == AP_MLP_GELU),
+               "vit_create: act %d (AP_ACT_QUICK_GELU and AP_ACT_GELU_TANH go with AP_MLP_GELU only)", c.act);
     AP_REQUIRE(c.proj_dim == 0 || (c.pool == AP_POOL_CLS && c.proj_dim % 128 == 0 && c.proj_dim <= c.dim),
                "vit_create: proj_dim %d (class-token pooling, a multiple of 128, at most dim)", c.proj_dim);
     const int g = c.image_size / c.patch_size;
-    const int prefix = 1 + c.reg_tokens;
+    const int prefix = nct ? 0 : 1 + c.reg_tokens;
     AP_REQUIRE(c.compute_dtype != AP_F32 || (prefix + g * g <= 288 && hd == 64),
                "vit_create: %d tokens / head width %d exceed the float32 attention kernel's limits (288 tokens, 64 wide); use "
                "float16 / bfloat16", prefix + g * g, hd);
@@ -656,7 +729,7 @@ int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
     m->cfg = c;
     m->device = device;
     m->grid = g; m->patches = g * g; m->prefix = prefix; m->tokens = prefix + g * g;
-    m->pos_rows = c.no_embed_class ? g * g : m->tokens;
+    m->pos_rows = c.no_embed_class ? g * g : m->tokens;            // (no_class_token: tokens = g * g either way)
     m->pos_row0 = c.no_embed_class ? 0 : prefix;
     m->hd = hd; m->dattn = c.heads * hd;
     m->attn_scale = c.attn_scale > 0.f ? c.attn_scale : 1.0f / sqrtf((float)hd);
@@ -673,7 +746,7 @@ int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
     const int D = c.dim;
     add("patch_embed.weight", D, 3 * c.patch_size * c.patch_size, true);
     add("patch_embed.bias", 1, D, false);
-    add("cls_token", 1, D, false);
+    if (!nct) add("cls_token", 1, D, false);
     if (c.reg_tokens > 0) add("reg_tokens", c.reg_tokens, D, false);
     add("pos_embed", m->pos_rows, D, false);
     add("norm.weight", 1, D, false);
@@ -705,6 +778,15 @@ int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
         add("attn_pool.q", 1, P, false);
         add("attn_pool.out.weight", P, P, true); add("attn_pool.out.bias", 1, P, false);
         add("attn_pool.ln_out.weight", 1, P, false); add("attn_pool.ln_out.bias", 1, P, false);
+    }
+    if (c.pool == AP_POOL_MAP) {
+        const int DA = m->dattn, H = c.mlp_dim;
+        add("map.q", 1, DA, false);
+        add("map.kv.weight", 2 * DA, D, true); add("map.kv.bias", 1, 2 * DA, false);
+        add("map.out.weight", D, DA, true); add("map.out.bias", 1, D, false);
+        add("map.ln.weight", 1, D, false); add("map.ln.bias", 1, D, false);
+        add("map.fc1.weight", H, D, true); add("map.fc1.bias", 1, H, false);
+        add("map.fc2.weight", D, H, true); add("map.fc2.bias", 1, D, false);
     }
     if (rc == AP_OK && m->split_f16) rc = build_split(m);
     if (rc != AP_OK) { delete m; return rc; }
@@ -820,7 +902,7 @@ int ap_vit_finalize(ap_vit* m) {
     m->pre_w = vec("pre_norm.weight"); m->pre_b = vec("pre_norm.bias");
     m->rope_cos = vec("rope.cos"); m->rope_sin = vec("rope.sin");
     m->head_proj = m->cfg.proj_dim > 0 ? find(m, "head_proj.weight") : nullptr;
-    {   // class / register token rows with their position rows folded in (f32; rebuilt on every finalize: it is tiny)
+    if (m->prefix > 0) {   // class / register token rows with their position rows folded in (f32; rebuilt on every finalize: it is tiny)
         if (!m->prefix_dev) AP_HIP_CHECK(hipMalloc((void**)&m->prefix_dev, (size_t)m->prefix * m->cfg.dim * sizeof(float)));
         int prc = ap::launch_prefix_build(m->cls, vec("reg_tokens"), m->cfg.reg_tokens, m->cfg.no_embed_class ? nullptr : m->pos,
                                           m->cfg.dim, m->prefix_dev, nullptr);
@@ -848,6 +930,14 @@ int ap_vit_finalize(ap_vit* m) {
         pp.kv = find(m, "attn_pool.kv.weight"); pp.kv_b = vec("attn_pool.kv.bias"); pp.q = vec("attn_pool.q");
         pp.out = find(m, "attn_pool.out.weight"); pp.out_b = vec("attn_pool.out.bias");
         pp.ln_out_w = vec("attn_pool.ln_out.weight"); pp.ln_out_b = vec("attn_pool.ln_out.bias");
+    }
+    if (m->cfg.pool == AP_POOL_MAP) {
+        ap::MapParams& mp = m->map;
+        mp.q = vec("map.q"); mp.kv = find(m, "map.kv.weight"); mp.kv_b = vec("map.kv.bias");
+        mp.out = find(m, "map.out.weight"); mp.out_b = vec("map.out.bias");
+        mp.ln_w = vec("map.ln.weight"); mp.ln_b = vec("map.ln.bias");
+        mp.fc1 = find(m, "map.fc1.weight"); mp.fc1_b = vec("map.fc1.bias");
+        mp.fc2 = find(m, "map.fc2.weight"); mp.fc2_b = vec("map.fc2.bias");
     }
     // ---- fused-LayerNorm weights (f16 / bf16): folded once from the f32 uploads, which are released afterwards
     bool any32 = false;

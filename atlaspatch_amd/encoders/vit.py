@@ -76,6 +76,9 @@ TRANSFORM_RESIZE = {
     "dinov3_vits16": (224, "bilinear"), "dinov3_vits16_plus": (224, "bilinear"), "dinov3_vitb16": (224, "bilinear"),
     "dinov3_vitl16": (224, "bilinear"), "dinov3_vitl16_sat": (224, "bilinear"), "dinov3_vith16_plus": (224, "bilinear"),
     "dinov3_vit7b16": (224, "bilinear"), "dinov3_vit7b16_sat": (224, "bilinear"),
+    # medsiglip.py:38 AutoProcessor(use_fast=True) of google/medsiglip-448 = SiglipImageProcessor: resize to 448 x 448 (both sides,
+    # no crop), `resample: 2` = bilinear, rescale 1 / 255, mean = std = 0.5 (public model card, unverifiable offline)
+    "medsiglip": (448, "bilinear"),
 }
 
 # Normalize() constants per registered name (default: ImageNet)
@@ -88,6 +91,7 @@ TRANSFORM_NORM = {
     "dinov3_vitl16_sat": ((0.430, 0.411, 0.296), (0.213, 0.156, 0.143)),        # the satellite (SAT-493M) checkpoints' statistics
     "dinov3_vit7b16_sat": ((0.430, 0.411, 0.296), (0.213, 0.156, 0.143)),       # (their AutoImageProcessor config, dinov3.py:39-41)
     "midnight": ((0.5, 0.5, 0.5), (0.5, 0.5, 0.5)),                                                   # midnight.py:22
+    "medsiglip": ((0.5, 0.5, 0.5), (0.5, 0.5, 0.5)),                          # the processor config's image_mean / image_std
     "h_optimus_0": ((0.707223, 0.578729, 0.703617), (0.211883, 0.230117, 0.177517)),                  # hoptimus.py:24-27
     "h_optimus_1": ((0.707223, 0.578729, 0.703617), (0.211883, 0.230117, 0.177517)),
     "h0_mini": ((0.707223, 0.578729, 0.703617), (0.211883, 0.230117, 0.177517)),          # the hub config's (H-optimus statistics)
@@ -216,6 +220,12 @@ ARCHS = {
                            reg_tokens=4, no_embed_class=True, rope=True, mlp="swiglu"),
     "dinov3_vit7b16_sat": dict(image_size=224, patch_size=16, dim=4096, depth=40, heads=32, mlp_dim=8192, ln_eps=1e-5, layer_scale=True,
                                reg_tokens=4, no_embed_class=True, rope=True, mlp="swiglu"),
+    # models/patch/medsiglip.py: transformers SiglipVisionModel of google/medsiglip-448 (SigLIP so400m/14 at 448 px; public hub
+    # config, unverifiable offline), get_image_features = pooler_output.  No class token (1024 patch tokens with a learned position
+    # row each), tanh GELU, LayerNorm 1e-6, and the attention-pooling head (a learned probe attends over the tokens of the final
+    # LayerNorm, then LayerNorm + MLP with a residual).  Heads 72 wide, stored zero-padded to 96; MLP 4304, stored as 4352.
+    "medsiglip": dict(image_size=448, patch_size=14, dim=1152, depth=27, heads=16, mlp_dim=4304, ln_eps=1e-6, layer_scale=False,
+                      act="gelu_tanh", pool="map", no_class_token=True),
 }
 
 
@@ -230,6 +240,9 @@ def _detect_source(sd: dict) -> str:
         return "timm"
     if "vision_model.pre_layrnorm.weight" in keys or "pre_layrnorm.weight" in keys:
         return "hf_clip"
+    if ("vision_model.head.probe" in keys or "head.probe" in keys) and \
+            ("vision_model.embeddings.patch_embedding.weight" in keys or "embeddings.patch_embedding.weight" in keys):
+        return "hf_siglip"
     if "visual.ln_pre.weight" in keys or "ln_pre.weight" in keys:
         return "open_clip"
     # DINOv3ViTModel: `model.layer.<i>.` in memory (transformers 5), `layer.<i>.` in the published model.safetensors
@@ -450,9 +463,93 @@ def canonical_state_dict(sd: dict, *, depth: int, layer_scale: bool, source: str
             put(b + "fc2.weight", sd[p + f2 + ".weight"]); put(b + "fc2.bias", sd[p + f2 + ".bias"])
             if layer_scale:
                 put(b + "ls1", sd[p + "layer_scale1.lambda1"]); put(b + "ls2", sd[p + "layer_scale2.lambda1"])
+    elif source == "hf_siglip":
+        raise ValueError("hf_siglip checkpoints go through siglip_canonical_state_dict (it needs the architecture for its checks)")
     else:
         raise ValueError(f"unknown state-dict source '{source}'")
     return out
+
+
+def siglip_canonical_shapes(arch: dict) -> dict:
+    """Canonical key -> shape of a SigLIP vision tower BEFORE head / MLP padding (``arch``: an ``ARCHS`` entry with ``pool="map"``)."""
+    d, mlp, ps = arch["dim"], arch["mlp_dim"], arch["patch_size"]
+    patches = (arch["image_size"] // ps) ** 2
+    want = {"patch_embed.weight": (d, 3, ps, ps), "patch_embed.bias": (d,), "pos_embed": (patches, d),
+            "norm.weight": (d,), "norm.bias": (d,),
+            "map.q": (d,), "map.kv.weight": (2 * d, d), "map.kv.bias": (2 * d,), "map.out.weight": (d, d), "map.out.bias": (d,),
+            "map.ln.weight": (d,), "map.ln.bias": (d,), "map.fc1.weight": (mlp, d), "map.fc1.bias": (mlp,),
+            "map.fc2.weight": (d, mlp), "map.fc2.bias": (d,)}
+    for i in range(arch["depth"]):
+        b = f"blocks.{i}."
+        want.update({b + "ln1.weight": (d,), b + "ln1.bias": (d,), b + "qkv.weight": (3 * d, d), b + "qkv.bias": (3 * d,),
+                     b + "proj.weight": (d, d), b + "proj.bias": (d,), b + "ln2.weight": (d,), b + "ln2.bias": (d,),
+                     b + "fc1.weight": (mlp, d), b + "fc1.bias": (mlp,), b + "fc2.weight": (d, mlp), b + "fc2.bias": (d,)})
+    return want
+
+
+def siglip_canonical_state_dict(sd: dict, arch: dict) -> dict:
+    """transformers' SigLIP vision tower -> canonical names (unpadded; ``HipViT`` pads heads and MLP).  Takes the three layouts that
+    occur: ``SiglipVisionModel.state_dict()`` of transformers 5 (bare keys), the same prefixed ``vision_model.`` (older versions
+    and the published ``model.safetensors``), and a whole ``SiglipModel`` checkpoint, whose ``text_model.*``, ``logit_scale`` and
+    ``logit_bias`` are dropped.  ``map.q`` = W_q probe + b_q, the query third of ``head.attention.in_proj`` applied to the probe
+    (input independent; float64 on the host, as for CONCH's pooler).  Every other unknown key, missing key or wrong shape is a
+    ``ValueError`` naming it (``check_canonical``)."""
+    src = {k: v for k, v in sd.items() if not (k.startswith("text_model.") or k in ("logit_scale", "logit_bias"))}
+    if any(k.startswith("vision_model.") for k in src):
+        src = {(k[len("vision_model."):] if k.startswith("vision_model.") else k): v for k, v in src.items()}
+    d, depth = arch["dim"], arch["depth"]
+    out: dict[str, torch.Tensor] = {}
+    used = set()
+
+    def take(key):
+        used.add(key)
+        return src.get(key)
+
+    def put(name, tensor):
+        if tensor is not None:
+            out[name] = tensor.detach().to(dtype=torch.float32, device="cpu").contiguous()
+
+    def cat(*keys):
+        parts = [take(k) for k in keys]
+        if any(p is None for p in parts):
+            return None
+        if any(p.shape[1:] != parts[0].shape[1:] for p in parts):
+            raise ValueError(f"SigLIP checkpoint: {list(keys)} have shapes {[tuple(p.shape) for p in parts]}, which do not stack")
+        return torch.cat(parts, 0)
+
+    put("patch_embed.weight", take("embeddings.patch_embedding.weight")); put("patch_embed.bias", take("embeddings.patch_embedding.bias"))
+    put("pos_embed", take("embeddings.position_embedding.weight"))
+    put("norm.weight", take("post_layernorm.weight")); put("norm.bias", take("post_layernorm.bias"))
+    for i in range(depth):
+        p, b = f"encoder.layers.{i}.", f"blocks.{i}."
+        a = p + "self_attn."
+        put(b + "ln1.weight", take(p + "layer_norm1.weight")); put(b + "ln1.bias", take(p + "layer_norm1.bias"))
+        put(b + "qkv.weight", cat(a + "q_proj.weight", a + "k_proj.weight", a + "v_proj.weight"))
+        put(b + "qkv.bias", cat(a + "q_proj.bias", a + "k_proj.bias", a + "v_proj.bias"))
+        put(b + "proj.weight", take(a + "out_proj.weight")); put(b + "proj.bias", take(a + "out_proj.bias"))
+        put(b + "ln2.weight", take(p + "layer_norm2.weight")); put(b + "ln2.bias", take(p + "layer_norm2.bias"))
+        put(b + "fc1.weight", take(p + "mlp.fc1.weight")); put(b + "fc1.bias", take(p + "mlp.fc1.bias"))
+        put(b + "fc2.weight", take(p + "mlp.fc2.weight")); put(b + "fc2.bias", take(p + "mlp.fc2.bias"))
+    probe, w_in, b_in = take("head.probe"), take("head.attention.in_proj_weight"), take("head.attention.in_proj_bias")
+    if probe is not None and w_in is not None and b_in is not None and tuple(w_in.shape) == (3 * d, d) and \
+            tuple(b_in.shape) == (3 * d,) and probe.numel() == d:
+        f = lambda t: t.detach().to(torch.float64, copy=True).cpu()
+        put("map.q", f(w_in)[:d] @ f(probe).reshape(d) + f(b_in)[:d])
+        put("map.kv.weight", w_in[d:]); put("map.kv.bias", b_in[d:])
+    elif w_in is not None and b_in is not None:
+        put("map.kv.weight", w_in); put("map.kv.bias", b_in)          # wrong shapes: check_canonical names them
+    put("map.out.weight", take("head.attention.out_proj.weight")); put("map.out.bias", take("head.attention.out_proj.bias"))
+    put("map.ln.weight", take("head.layernorm.weight")); put("map.ln.bias", take("head.layernorm.bias"))
+    put("map.fc1.weight", take("head.mlp.fc1.weight")); put("map.fc1.bias", take("head.mlp.fc1.bias"))
+    put("map.fc2.weight", take("head.mlp.fc2.weight")); put("map.fc2.bias", take("head.mlp.fc2.bias"))
+    unknown = sorted(k for k in src if k not in used)
+    absent = sorted(k for k in used if k not in src)
+    try:
+        return check_canonical(out, siglip_canonical_shapes(arch), unknown, family="SigLIP", source="hf_siglip")
+    except ValueError as exc:
+        if unknown or not absent:
+            raise
+        raise ValueError(f"{exc}; the checkpoint lacks {absent[:5]}") from None
 
 
 def stored_head_dim(dim: int, heads: int) -> int:
@@ -488,6 +585,19 @@ def pad_heads(state: dict, *, dim: int, heads: int, depth: int) -> dict:
         pw = state[b + "proj.weight"].reshape(-1, heads, hd)
         pp = torch.zeros((pw.shape[0], heads, hdp), dtype=pw.dtype); pp[:, :, :hd] = pw
         out[b + "proj.weight"] = pp.reshape(pw.shape[0], heads * hdp).contiguous()
+    if "map.kv.weight" in state:                                     # SigLIP's pooling head: q [heads, hd], kv rows [2, heads, hd, :], out columns
+        q = state["map.q"].reshape(heads, hd)
+        qp = torch.zeros((heads, hdp), dtype=q.dtype); qp[:, :hd] = q
+        out["map.q"] = qp.reshape(-1).contiguous()
+        w = state["map.kv.weight"].reshape(2, heads, hd, -1)
+        wp = torch.zeros((2, heads, hdp, w.shape[-1]), dtype=w.dtype); wp[:, :, :hd] = w
+        out["map.kv.weight"] = wp.reshape(2 * heads * hdp, -1).contiguous()
+        bb = state["map.kv.bias"].reshape(2, heads, hd)
+        bp = torch.zeros((2, heads, hdp), dtype=bb.dtype); bp[:, :, :hd] = bb
+        out["map.kv.bias"] = bp.reshape(-1).contiguous()
+        pw = state["map.out.weight"].reshape(-1, heads, hd)
+        pp = torch.zeros((pw.shape[0], heads, hdp), dtype=pw.dtype); pp[:, :, :hd] = pw
+        out["map.out.weight"] = pp.reshape(pw.shape[0], heads * hdp).contiguous()
     return out
 
 
@@ -505,8 +615,8 @@ def pad_mlp(state: dict, *, mlp_dim: int, depth: int, swiglu: bool) -> dict:
     if hp == mlp_dim:
         return state
     out = dict(state)
-    for i in range(depth):
-        b = f"blocks.{i}."
+    prefixes = [f"blocks.{i}." for i in range(depth)] + (["map."] if "map.fc1.weight" in state else [])   # (gelu_tanh(0) = 0 too)
+    for b in prefixes:
         w1, b1, w2 = state[b + "fc1.weight"], state[b + "fc1.bias"], state[b + "fc2.weight"]
         halves = 2 if swiglu else 1
         w1p = torch.zeros((halves, hp, w1.shape[1]), dtype=w1.dtype); w1p[:, :mlp_dim] = w1.reshape(halves, mlp_dim, -1)
@@ -569,7 +679,7 @@ def random_canonical_state_dict(arch: dict, seed: int = 0) -> dict:
     d, mlp, ps = arch["dim"], arch["mlp_dim"], arch["patch_size"]
     reg = int(arch.get("reg_tokens", 0))
     patches = (arch["image_size"] // ps) ** 2
-    tokens = patches if arch.get("no_embed_class") else 1 + reg + patches          # rows of the position embedding
+    tokens = patches if (arch.get("no_embed_class") or arch.get("no_class_token")) else 1 + reg + patches   # rows of the position embedding
     f1 = 2 * mlp if arch.get("mlp") == "swiglu" else mlp
 
     def w(*shape, s=0.02):
@@ -590,6 +700,12 @@ def random_canonical_state_dict(arch: dict, seed: int = 0) -> dict:
         if arch.get("layer_scale"):
             sd[b + "ls1"] = torch.full((d,), 1e-5) + w(d, s=1e-6)
             sd[b + "ls2"] = torch.full((d,), 1e-5) + w(d, s=1e-6)
+    if arch.get("no_class_token"):
+        del sd["cls_token"]
+    if arch.get("pool") == "map":                                    # SigLIP's head, unpadded (map.q as the adapter folds it)
+        sd.update({"map.q": w(d, s=0.5), "map.kv.weight": w(2 * d, d), "map.kv.bias": w(2 * d), "map.out.weight": w(d, d),
+                   "map.out.bias": w(d), "map.ln.weight": 1.0 + w(d, s=0.1), "map.ln.bias": w(d), "map.fc1.weight": w(mlp, d),
+                   "map.fc1.bias": w(mlp), "map.fc2.weight": w(d, mlp), "map.fc2.bias": w(d)})
     if arch.get("pool") == "attn":
         sd.update(attn_pool_canonical(random_attn_pool(arch, seed), pool_eps=arch.get("pool_ln_eps", 1e-5)))
     if arch.get("rope"):
@@ -614,21 +730,25 @@ class HipViT(NativeEncoder):
         self.arch = dict(arch)
         attn_pool = arch.get("pool") == "attn"
         cls_mean = arch.get("pool") == "cls_mean"          # [class token | mean of the patch tokens] (midnight.py:58-61)
+        map_head = arch.get("pool") == "map"               # SigLIP's attention-pooling head (medsiglip.py:63): dim floats
         self.embed_dim = int(arch["pool_dim"] if attn_pool else (2 * arch["dim"] if cls_mean else arch["dim"]))
         if arch.get("proj_dim"):                           # CLIP visual projection
             self.embed_dim = int(arch["proj_dim"])
         hd_true = arch["dim"] // arch["heads"]
         hd_stored = stored_head_dim(arch["dim"], arch["heads"])
-        cfg = _lib.VitConfig(arch["image_size"], arch["patch_size"], arch["dim"], arch["depth"],
+        # the fields appended since ABI v20 travel in the longer structure; every other model hands over the v20 one, as before
+        config = _lib.VitConfigEx if arch.get("no_class_token") else _lib.VitConfig
+        cfg = config(arch["image_size"], arch["patch_size"], arch["dim"], arch["depth"],
                              arch["heads"], stored_mlp_dim(arch["mlp_dim"]), float(arch["ln_eps"]),
                              1 if arch.get("layer_scale") else 0, _lib.torch_dtype_code(dtype),
-                             1 if attn_pool else (2 if cls_mean else 0), int(arch.get("pool_dim", 0)), int(arch.get("pool_heads", 0)),
+                             1 if attn_pool else (2 if cls_mean else (3 if map_head else 0)), int(arch.get("pool_dim", 0)), int(arch.get("pool_heads", 0)),
                              float(arch.get("pool_ln_eps", 1e-5)),
                              int(arch.get("reg_tokens", 0)), 1 if arch.get("no_embed_class") else 0,
                              1 if arch.get("mlp") == "swiglu" else 0, hd_stored,
                              0.0 if hd_stored == hd_true else float(1.0 / np.sqrt(np.float32(hd_true))),
-                             1 if arch.get("pre_norm") else 0, 1 if arch.get("act") == "quick_gelu" else 0,
-                             int(arch.get("proj_dim", 0)), 1 if arch.get("rope") else 0)
+                             1 if arch.get("pre_norm") else 0, {"quick_gelu": 1, "gelu_tanh": 2}.get(arch.get("act"), 0),
+                             int(arch.get("proj_dim", 0)), 1 if arch.get("rope") else 0,
+                     *([1] if arch.get("no_class_token") else []))
         state = pad_heads(state, dim=arch["dim"], heads=arch["heads"], depth=arch["depth"])
         state = pad_mlp(state, mlp_dim=arch["mlp_dim"], depth=arch["depth"], swiglu=arch.get("mlp") == "swiglu")
         self._open(cfg, state)
@@ -740,6 +860,10 @@ def build_hip_vit_extractor(*, name: str, arch, device, dtype, state_dict: Optio
                                          "torchvision, timm or HF ViT")
     if seeded:
         source = "canonical"
+    if spec.get("pool") == "map" and source == "auto" and _detect_source(state_dict) == "hf_siglip":
+        source = "hf_siglip"
+    if source == "hf_siglip":
+        state_dict, source = siglip_canonical_state_dict(state_dict, spec), "canonical"
     pool_state = None
     if spec.get("pool") == "attn" and source != "canonical":
         if any(k.startswith("visual.trunk.") for k in state_dict):          # a CONCH checkpoint
@@ -754,8 +878,87 @@ def build_hip_vit_extractor(*, name: str, arch, device, dtype, state_dict: Optio
     if pool_state:
         state.update({k: v.detach().to(torch.float32).cpu().contiguous() for k, v in pool_state.items()})
     vit = HipViT(spec, state, device=torch.device(device), dtype=dtype)
-    return HipViTFeatureExtractor(name=name, vit=vit, mean=mean or IMAGENET_MEAN, std=std or IMAGENET_STD,
-                                  max_batch=max_batch, resize=resize, expect_size=expect_size)
+    extractor = SquareResizeFeatureExtractor if spec.get("square_resize") else HipViTFeatureExtractor
+    return extractor(name=name, vit=vit, mean=mean or IMAGENET_MEAN, std=std or IMAGENET_STD,
+                     max_batch=max_batch, resize=resize, expect_size=expect_size)
+
+
+class SquareResizeFeatureExtractor(HipViTFeatureExtractor):
+    """``resize`` = (S, filter) means S x S whatever the tile's aspect -- transformers' SiglipImageProcessor (``size: {height, width}``,
+    no crop) -- instead of torchvision's shorter-side ``Resize(S)``.  Square tiles, the usual case, come out the same."""
+
+    def resized(self, tiles_u8: torch.Tensor) -> torch.Tensor:
+        size, filt = self.resize
+        h, w = int(tiles_u8.shape[1]), int(tiles_u8.shape[2])
+        if h == size and w == size:
+            return tiles_u8
+        rs = self._resamplers.get((h, w))
+        if rs is None:
+            from ..utils.resample import DeviceResampler
+            rs = self._resamplers[(h, w)] = DeviceResampler((h, w), (size, size), filt, self.device)
+        return rs(tiles_u8)
+
+
+PIL_RESAMPLE_NAMES = {0: "nearest", 2: "bilinear", 3: "bicubic"}     # PIL.Image.Resampling codes a preprocessor_config.json holds
+
+
+def medsiglip_transform(weights_dir: Optional[str] = None) -> tuple:
+    """(size, filter, mean, std) of the medsiglip preprocess: ``TRANSFORM_RESIZE`` / ``TRANSFORM_NORM`` (the public model card's
+    values, unverifiable offline) unless ``<weights_dir>/medsiglip.preprocessor_config.json`` -- the processor config published
+    with the checkpoint -- is there, whose ``size``, ``resample``, ``image_mean`` and ``image_std`` then win."""
+    import json
+    size, filt = TRANSFORM_RESIZE["medsiglip"]
+    mean, std = TRANSFORM_NORM["medsiglip"]
+    root = weights_dir if weights_dir is not None else os.environ.get("ATLASPATCH_WEIGHTS_DIR")
+    path = Path(root) / "medsiglip.preprocessor_config.json" if root else None
+    if path is not None and path.exists():
+        cfg = json.loads(path.read_text())
+        if "size" in cfg:
+            sz = cfg["size"]
+            h, w = (sz["height"], sz["width"]) if isinstance(sz, dict) else (sz, sz)
+            if int(h) != int(w):
+                raise ValueError(f"{path}: size {sz} is not square")
+            size = int(h)
+        if "resample" in cfg:
+            if int(cfg["resample"]) not in PIL_RESAMPLE_NAMES or PIL_RESAMPLE_NAMES[int(cfg["resample"])] == "nearest":
+                raise ValueError(f"{path}: resample {cfg['resample']} is not a filter of the device resize (2 bilinear, 3 bicubic)")
+            filt = PIL_RESAMPLE_NAMES[int(cfg["resample"])]
+        if "image_mean" in cfg:
+            mean = tuple(float(v) for v in cfg["image_mean"])
+        if "image_std" in cfg:
+            std = tuple(float(v) for v in cfg["image_std"])
+    return size, filt, mean, std
+
+
+def medsiglip_max_batch(vit: "HipViT", cap: int = 128, budget_bytes: int = 16 << 30) -> int:
+    """The largest batch <= cap whose ``ap_vit_workspace_bytes`` fits the budget (1024 tokens of 1152: ~90 MB per image in float16)."""
+    n = cap
+    while n > 1 and int(vit.lib.ap_vit_workspace_bytes(vit._handle, n)) > budget_bytes:
+        n //= 2
+    return n
+
+
+def register_medsiglip(registry, *, device, dtype=torch.float32, num_workers: int = 0, **arch_overrides) -> None:
+    """medsiglip (models/patch/medsiglip.py): transformers' SiglipVisionModel of google/medsiglip-448, features =
+    ``get_image_features`` = ``pooler_output`` of the vision tower (the attention-pooling head's 1152 floats).  Transform: the
+    processor's resize to 448 x 448 (bilinear), rescale, Normalize(0.5, 0.5) -- resize and normalisation on the device.  float16 /
+    bfloat16 only: 1024 tokens and 72-wide heads are outside the float32 attention kernel's limits.  HF state dict (vision tower
+    alone or the whole SiglipModel) as ``$ATLASPATCH_WEIGHTS_DIR/medsiglip.safetensors``."""
+    def build():
+        spec = dict(ARCHS["medsiglip"]); spec.update(arch_overrides)
+        tokens = (spec["image_size"] // spec["patch_size"]) ** 2
+        if dtype == torch.float32 and (tokens > 288 or stored_head_dim(spec["dim"], spec["heads"]) != 64):
+            raise ValueError(f"medsiglip: --feature-precision float32 is not available: {tokens} tokens with heads stored "
+                             f"{stored_head_dim(spec['dim'], spec['heads'])} wide exceed the float32 attention kernel's limits (288 "
+                             "tokens, 64 wide); use float16 or bfloat16")
+        size, filt, mean, std = medsiglip_transform()
+        if size != spec["image_size"]:
+            raise ValueError(f"medsiglip: the preprocessor config resizes to {size}, the model takes {spec['image_size']}")
+        ex = build_hip_vit_extractor(name="medsiglip", arch=spec, device=device, dtype=dtype, random_init_seed=_env_seed(),
+                                     mean=mean, std=std, resize=(size, filt), expect_size=None, max_batch=128, square_resize=True)
+        ex.max_batch = medsiglip_max_batch(ex.vit)
+        return ex
+    registry.register("medsiglip", build)
 
 
 def register_conch(registry, *, device, dtype=torch.float32, num_workers: int = 0) -> None:

@@ -231,17 +231,43 @@ typedef struct ap_vit_config {
                             head_dim must be the true head width */
 } ap_vit_config;
 #define AP_VIT_CONFIG_SIZE_V20 92u   /* struct_size + the 22 fields of ABI v19: the smallest size ap_vit_create accepts */
+/* Fields appended since ABI v20 (additive: AP_ABI_VERSION stays 20).  ap_vit_config itself keeps its v20 fields and size; a caller
+ * that needs a newer field hands ap_vit_create an ap_vit_config_ex -- the SAME bytes followed by the appended fields -- cast to
+ * ap_vit_config*, with base.struct_size = sizeof(ap_vit_config_ex) (ap_vit_config_init(&cfg.base, sizeof cfg) zero-fills all of it
+ * and records that size).  All zero = the behaviour before the field existed, so the two sizes ap_vit_create accepts,
+ * AP_VIT_CONFIG_SIZE_V20 and AP_VIT_CONFIG_SIZE_EX, mean the same for an old caller. */
+typedef struct ap_vit_config_ex {
+    ap_vit_config base;
+    /* ---- SigLIP vision towers (models/patch/medsiglip.py:37,63: transformers SiglipVisionModel, get_image_features) */
+    int no_class_token;  /* 1: the sequence is the patch tokens only (SiglipVisionEmbeddings: patch embedding + position embedding,
+                            no class embedding): tokens = (image_size / patch_size)^2, pos_embed [tokens, dim] is added to every
+                            row, there is no cls_token parameter, reg_tokens must be 0, and the pooling must be AP_POOL_MAP.
+                            AP_VIT_OPT_EXACT_CLS is inert (there is no class row) and the last block always runs in full.  Not
+                            combined with pre_norm or rope in this build */
+} ap_vit_config_ex;
+#define AP_VIT_CONFIG_SIZE_EX 96u    /* sizeof(ap_vit_config_ex) */
 size_t ap_sizeof_vit_config(void);   /* sizeof(ap_vit_config) inside the library */
 /* Zero-fills sizeof_caller bytes at cfg and records sizeof_caller in cfg->struct_size.  AP_ERR_INVALID when cfg is NULL,
  * sizeof_caller < AP_VIT_CONFIG_SIZE_V20 or not a multiple of 4. */
 int ap_vit_config_init(ap_vit_config* cfg, size_t sizeof_caller);
 #define AP_ACT_GELU 0
 #define AP_ACT_QUICK_GELU 1
+#define AP_ACT_GELU_TANH 2    /* 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))): transformers "gelu_pytorch_tanh", SigLIP's
+                                hidden_act (models/patch/medsiglip.py); AP_MLP_GELU only */
 #define AP_MLP_GELU 0
 #define AP_MLP_SWIGLU 1
 #define AP_POOL_CLS 0
 #define AP_POOL_ATTN 1
 #define AP_POOL_CLS_MEAN 2
+/* AP_POOL_MAP: SigLIP's multi-head attention pooling head (transformers SiglipMultiheadAttentionPoolingHead; the features
+ * models/patch/medsiglip.py returns are its output, `pooler_output`).  After the final LayerNorm on all tokens (y):
+ *   kv = y W_kv^T + b_kv            [n * tokens, 2 * heads * head_dim]  (rows k; v of nn.MultiheadAttention's in_proj)
+ *   a  = softmax_t(attn_scale * q_h . k_t) v_t   per (image, head); q = W_q probe + b_q is input independent (map.q)
+ *   r  = a W_out^T + b_out          [n, dim]
+ *   out = r + fc2(gelu_tanh(fc1(LayerNorm(r))))   f32 [n, dim]
+ * heads, head_dim (as stored), attn_scale, ln_eps and mlp_dim are the trunk's; the MLP uses the tanh GELU whatever `act` is.
+ * Requires no_class_token in this build.  f16 / bf16, and float32 inside its limits (288 tokens, 64-wide heads). */
+#define AP_POOL_MAP 3
 
 /* Validates cfg->struct_size as described above, then every field; *out is written only on success. */
 int ap_vit_create(const ap_vit_config* cfg, ap_vit** out);
@@ -258,13 +284,19 @@ void ap_vit_destroy(ap_vit* m);
  *   attn_pool.ln_k.weight|bias [dim]   attn_pool.kv.weight [2P, dim] (rows k_proj; v_proj)   attn_pool.kv.bias [2P]
  *   attn_pool.q [P]  (the projected query q_proj(ln_q(query)) + bias: input independent, computed by the host)
  *   attn_pool.out.weight [P, P] | .bias [P]   attn_pool.ln_out.weight|bias [P]
+ * AP_POOL_MAP adds (DA = heads * head_dim as stored, H = mlp_dim; SiglipMultiheadAttentionPoolingHead):
+ *   map.q [DA]  (W_q probe + b_q, the query third of attention.in_proj applied to the probe: computed by the host)
+ *   map.kv.weight [2 DA, dim] (rows k; v of attention.in_proj_weight, heads zero-padded to head_dim)   map.kv.bias [2 DA]
+ *   map.out.weight [dim, DA] | map.out.bias [dim]   (attention.out_proj)
+ *   map.ln.weight|bias [dim]   (layernorm)   map.fc1.weight [H, dim] | .bias [H]   map.fc2.weight [dim, H] | .bias [dim]
+ * no_class_token: there is no cls_token parameter and pos_embed is [gh*gw, dim].
  * Synchronous (copies before returning).
  * Every upload that a derived buffer depends on UN-FINALISES the object -- forwards return AP_ERR_STATE until
  * ap_vit_finalize succeeds again:
  *   cls_token, reg_tokens, pos_embed   (since ABI v17; before it a class-token upload took effect at once) the prefix rows
  *                                      "class / register token + its position row" are built by ap_vit_finalize;
  *   pos_embed, blocks.*                f16 / bf16: the folded weights / the T copy of pos_embed are stale (see ap_vit_finalize).
- * patch_embed.*, norm.*, pre_norm.*, rope.*, head_proj.weight and attn_pool.* take effect immediately. */
+ * patch_embed.*, norm.*, pre_norm.*, rope.*, head_proj.weight, attn_pool.* and map.* take effect immediately. */
 int ap_vit_set_param(ap_vit* m, const char* name, const float* host, size_t count);
 /* n parameters in one call (same semantics as n ap_vit_set_param calls, in order; stops at the first error) */
 int ap_vit_set_params(ap_vit* m, const char* const* names, const float* const* host, const size_t* counts, int n);
@@ -310,7 +342,7 @@ int ap_vit_finalize(ap_vit* m);
 int ap_vit_set_option(ap_vit* m, int option, int value);
 
 size_t ap_vit_workspace_bytes(const ap_vit* m, int n);
-int ap_vit_embed_dim(const ap_vit* m);   /* dim (AP_POOL_CLS), pool_dim (AP_POOL_ATTN) or 2 * dim (AP_POOL_CLS_MEAN) */
+int ap_vit_embed_dim(const ap_vit* m);   /* dim (AP_POOL_CLS, AP_POOL_MAP), pool_dim (AP_POOL_ATTN) or 2 * dim (AP_POOL_CLS_MEAN) */
 
 /* Optional per-launch timing with HIP events recorded on the forward's own stream (what
  * bench.py's roofline block reads).  Off by default; when on, every kernel launch of a forward
@@ -324,7 +356,7 @@ int ap_vit_embed_dim(const ap_vit* m);   /* dim (AP_POOL_CLS), pool_dim (AP_POOL
 #define AP_PROF_GEMM_FC2 5
 #define AP_PROF_ATTENTION 6
 #define AP_PROF_LAYERNORM 7
-#define AP_PROF_CLS_TAIL 8      /* last block after its K/V projection, CLS rows only (see ap_vit_forward_u8) */
+#define AP_PROF_CLS_TAIL 8      /* last block after its K/V projection, CLS rows only (see ap_vit_forward_u8); AP_POOL_MAP: the head */
 #define AP_PROF_KINDS 9
 int ap_vit_profile_enable(ap_vit* m, int on);
 int ap_vit_profile_read(ap_vit* m, double* ms_by_kind, long long* launches_by_kind, int kinds);
@@ -352,6 +384,9 @@ int ap_vit_forward_chw(ap_vit* m, const void* x, int x_dtype, int n,
  *   AP_EPI_BIAS_GELU   out T   [M, ldo] = gelu_erf(C)             (Linear + nn.GELU())
  *   AP_EPI_BIAS_RESID  out f32 [M, ldo] += C * (gamma ? gamma[n] : 1)   (residual add, LayerScale)
  *   AP_EPI_BIAS_QUICK_GELU  out T [M, ldo] = C * sigmoid(1.702 C)   (CLIP's QuickGELU: models/patch/clip.py, plip.py)
+ *   AP_EPI_BIAS_GELU_TANH   out T [M, ldo] = 0.5 C (1 + tanh(sqrt(2 / pi) (C + 0.044715 C^3)))   (SigLIP's gelu_pytorch_tanh:
+ *                           models/patch/medsiglip.py), evaluated as C * sigmoid(2 sqrt(2 / pi) (C + 0.044715 C^3)): one
+ *                           exponential and one reciprocal, no NaN for any finite C, -> C and -> -0 for large |C|
  * A: T [M, lda], W: T [N, ldw] (both K-contiguous, the checkpoint's [out, in] layout), bias /
  * gamma: f32 [N].  N % 128 == 0 and K % (128 / sizeof(T)) == 0.  impl: 0 = pick, 128 = the
  * 128x128-tile kernel, 256 = the persistent 256x256-tile kernel (f16 / bf16, N % 256 == 0,
@@ -360,6 +395,7 @@ int ap_vit_forward_chw(ap_vit* m, const void* x, int x_dtype, int n,
 #define AP_EPI_BIAS_GELU 1
 #define AP_EPI_BIAS_RESID 2
 #define AP_EPI_BIAS_QUICK_GELU 10
+#define AP_EPI_BIAS_GELU_TANH 12
 int ap_gemm(int dtype, int epilogue, const void* A, int lda, const void* W, int ldw,
             int M, int N, int K, const float* bias, const float* gamma, void* out, int ldo,
             int impl, int variant, ap_stream_t stream);
@@ -400,6 +436,7 @@ int ap_gemm_split_f16_windows(const float* A, int lda, const void* w_split, int 
  *   AP_EPI_NORM         out T [M, ldo] = rstd * acc + (-mean rstd) * colsum[n] + bias[n]
  *   AP_EPI_NORM_GELU    out = gelu(that)
  *   AP_EPI_NORM_QUICK_GELU  out = that * sigmoid(1.702 * that)
+ *   AP_EPI_NORM_GELU_TANH   out = gelu_tanh(that), as AP_EPI_BIAS_GELU_TANH (SigLIP: models/patch/medsiglip.py)
  *   AP_EPI_NORM_SWIGLU  timm SwiGLUPacked (models/patch/uni.py:91-93, uni_v2) with the gate in the epilogue: W / colsum / bias rows
  *                       INTERLEAVED in groups of 64 -- rows 64q .. 64q+31 = fc1 rows 32q .. (x1), rows 64q+32 .. 64q+63 = fc1 rows
  *                       N/2 + 32q .. (x2) -- and out T [M, N / 2]: out[m][32q + j] = silu(norm x1) * norm x2, one rounding
@@ -414,6 +451,7 @@ int ap_gemm_split_f16_windows(const float* A, int lda, const void* w_split, int 
 #define AP_EPI_RESID_STATS 6
 #define AP_EPI_NORM_SWIGLU 8
 #define AP_EPI_NORM_QUICK_GELU 9
+#define AP_EPI_NORM_GELU_TANH 11
 int ap_gemm_fused(int dtype, int epilogue, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
                   const float* bias, const float* colsum, const float* rowstats, float* partial,
                   void* out, int ldo, int impl, ap_stream_t stream);
@@ -454,6 +492,10 @@ int ap_attention(int dtype, const void* qkv, void* out, int n, int tokens, int h
  *   are aligned to eight elements: 16 bytes in f16 / bf16, 32 bytes in float32.
  * ap_attn_pool: attentional pooling with one learned query: kv T [n * tokens, 2 * heads * 64] (k | v), q f32
  *   [heads * 64] shared by every image, out T [n, heads * 64]; scale 1 / 8.  f16 / bf16; 1 <= tokens <= 12000.
+ * ap_attention_probe: ap_attention_cls with ONE float32 query shared by every image -- the pooling step of SigLIP's
+ *   attention-pooling head (models/patch/medsiglip.py; AP_POOL_MAP): q f32 [heads * head_dim], everything else as
+ *   ap_attention_cls (kv / out of type T, head_dim 64 / 96 / 128, ld / koff / voff multiples of 8, 1 <= tokens <= 12000, kv
+ *   aligned to eight elements, q to 16 bytes).
  * ap_rope: DINOv3's rotary embedding in place on the q (which & 1) and k (which & 2) parts of the packed qkv
  *   T [n * tokens, 3 * heads * head_dim], patch tokens only (rows >= prefix of every image), p = the patch's index:
  *     x'[j] = x[j] cos[p][j] - x[j + h] sin[p][j],   x'[j + h] = x[j + h] cos[p][j + h] + x[j] sin[p][j + h],   h = head_dim / 2
@@ -492,6 +534,8 @@ int ap_attention_scaled(int dtype, const void* qkv, void* out, int n, int tokens
 int ap_attention_cls(int dtype, const void* q, const void* kv, int ld, int koff, int voff, void* out, int n, int tokens,
                      int heads, int head_dim, float scale, ap_stream_t stream);
 int ap_attn_pool(int dtype, const void* kv, const float* q, void* out, int n, int tokens, int heads, ap_stream_t stream);
+int ap_attention_probe(int dtype, const float* q, const void* kv, int ld, int koff, int voff, void* out, int n, int tokens,
+                       int heads, int head_dim, float scale, ap_stream_t stream);
 int ap_rope(int dtype, void* qkv, int n, int tokens, int prefix, int heads, int head_dim, const float* cos, const float* sin,
             int which, ap_stream_t stream);
 int ap_swiglu(int dtype, const void* x, int rows, int h, void* out, ap_stream_t stream);
