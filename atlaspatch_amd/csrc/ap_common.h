@@ -112,6 +112,8 @@ __device__ __forceinline__ f32x2_t swiglu2(f32x2_t a, f32x2_t b) {
 // ---- GEMM ------------------------------------------------------------------------------
 // C[m][n] = sum_k A[m][k] * W[n][k]  (+ epilogue); A: activations [M, lda], W: weights [N, ldw],
 // both K-contiguous in the compute dtype.
+// The codes are the C ABI's AP_EPI_* values.  Every value has one row in kEpiTraits (gemm_epilogue.h), which also holds
+// what the two kernels share of the epilogues and the recipe for adding an activation.
 enum GemmEpilogue {
     EPI_BIAS_STORE = 0,    // out[m][n] = T((acc + bias[n]) * (gamma ? gamma[n] : 1))
     EPI_BIAS_GELU = 1,     // out[m][n] = T(gelu_erf(acc + bias[n]))

@@ -9,6 +9,7 @@
 #include <zlib.h>
 #include <cmath>
 #include "ap_common.h"
+#include "gemm_epilogue.h"
 
 namespace ap {
 
@@ -160,8 +161,10 @@ int ap_gemm(int dtype, int epilogue, const void* A, int lda, const void* W, int 
             int K, const float* bias, const float* gamma, void* out, int ldo, int impl, int variant,
             ap_stream_t stream) {
     AP_REQUIRE(A && W && bias && out, "ap_gemm: null pointer");
-    AP_REQUIRE(epilogue == AP_EPI_BIAS || epilogue == AP_EPI_BIAS_GELU || epilogue == AP_EPI_BIAS_RESID || epilogue == AP_EPI_BIAS_QUICK_GELU ||
-               epilogue == AP_EPI_BIAS_GELU_TANH, "ap_gemm: unknown epilogue %d", epilogue);
+    static_assert(AP_EPI_BIAS == ap::EPI_BIAS_STORE && AP_EPI_BIAS_GELU == ap::EPI_BIAS_GELU && AP_EPI_BIAS_RESID == ap::EPI_BIAS_RESID &&
+                  AP_EPI_BIAS_QUICK_GELU == ap::EPI_BIAS_QGELU && AP_EPI_BIAS_GELU_TANH == ap::EPI_BIAS_GTANH, "AP_EPI_* are the GemmEpilogue codes");
+    AP_REQUIRE(ap::epi_known(epilogue) && !ap::epi_is_norm(epilogue) && !ap::epi_is_resid(epilogue) && epilogue != ap::EPI_PATCH_EMBED,
+               "ap_gemm: unknown epilogue %d", epilogue);
     AP_REQUIRE(dtype == AP_F16 || dtype == AP_BF16 || dtype == AP_F32, "ap_gemm: unknown dtype %d", dtype);
     ap::GemmArgs g{};
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.M = M; g.N = N; g.K = K;
@@ -227,23 +230,19 @@ int ap_gemm_fused(int dtype, int epilogue, const void* A, int lda, const void* W
                   int impl, ap_stream_t stream) {
     AP_REQUIRE(A && W && bias && out, "ap_gemm_fused: null pointer");
     AP_REQUIRE(dtype == AP_F16 || dtype == AP_BF16, "ap_gemm_fused: f16 / bf16 only");
-    int epi;
-    if (epilogue == AP_EPI_NORM) epi = ap::EPI_NORM_STORE;
-    else if (epilogue == AP_EPI_NORM_GELU) epi = ap::EPI_NORM_GELU;
-    else if (epilogue == AP_EPI_NORM_SWIGLU) epi = ap::EPI_NORM_SWIGLU;
-    else if (epilogue == AP_EPI_NORM_QUICK_GELU) epi = ap::EPI_NORM_QGELU;
-    else if (epilogue == AP_EPI_NORM_GELU_TANH) epi = ap::EPI_NORM_GTANH;
-    else if (epilogue == AP_EPI_RESID_STATS) epi = ap::EPI_RESID_STATS;
-    else { ap::set_error("ap_gemm_fused: unknown epilogue %d", epilogue); return AP_ERR_INVALID; }
-    AP_REQUIRE(epi == ap::EPI_RESID_STATS ? partial != nullptr : (colsum && rowstats), "ap_gemm_fused: missing operand for epilogue %d", epilogue);
+    static_assert(AP_EPI_NORM == ap::EPI_NORM_STORE && AP_EPI_NORM_GELU == ap::EPI_NORM_GELU && AP_EPI_NORM_SWIGLU == ap::EPI_NORM_SWIGLU &&
+                  AP_EPI_NORM_QUICK_GELU == ap::EPI_NORM_QGELU && AP_EPI_NORM_GELU_TANH == ap::EPI_NORM_GTANH &&
+                  AP_EPI_RESID_STATS == ap::EPI_RESID_STATS, "AP_EPI_* are the GemmEpilogue codes");
+    AP_REQUIRE(ap::epi_is_norm(epilogue) || epilogue == ap::EPI_RESID_STATS, "ap_gemm_fused: unknown epilogue %d", epilogue);
     ap::GemmArgs g{};
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.M = M; g.N = N; g.K = K;
     g.bias = bias; g.colsum = colsum; g.rowstats = rowstats; g.partial = partial; g.out = out; g.ldo = ldo;
+    AP_REQUIRE(ap::epi_operands_ok(epilogue, g), "ap_gemm_fused: missing operand for epilogue %d", epilogue);
     const int variant = (int)((unsigned)impl >> 12);      // bits 12..: kernel tuning variant (tools only), low 12 bits: implementation
     impl &= 0xfff;
     AP_REQUIRE(impl == 0 || impl == 128 || impl == 256 || impl == 257, "ap_gemm_fused: impl %d (0 = pick, 128, 256; 257 = the A/B twin)", impl);
-    AP_REQUIRE(M > 0 && (impl == 128 || ap::gemm256_supports(dtype, epi, g)), "ap_gemm_fused: unsupported problem (N %% 256, K %% 128, 16-byte strides)");
-    return ap::launch_gemm_impl(dtype, epi, g, impl, variant, (hipStream_t)stream);
+    AP_REQUIRE(M > 0 && (impl == 128 || ap::gemm256_supports(dtype, epilogue, g)), "ap_gemm_fused: unsupported problem (N %% 256, K %% 128, 16-byte strides)");
+    return ap::launch_gemm_impl(dtype, epilogue, g, impl, variant, (hipStream_t)stream);
 }
 
 int ap_stream_init(int dtype, const float* tok, int rows, int dim, float eps, void* x, float* rowstats, ap_stream_t stream) {

@@ -27,9 +27,12 @@
 //    32-deep K-tile and wave against 32 x 4 of the exact f32 instruction: 2.7x the arithmetic rate at ~2^-22 per product.
 //  * XCD-aware tile order: block b runs on XCD b % 8; logical tile ids are remapped so
 //    each XCD owns a contiguous run of tiles (all n-tiles of an m-panel share one L2).
+//  * the epilogue family (traits, activations, the LayerNorm-affine step, the residual element step, the runtime -> template
+//    dispatch) is defined once for this kernel and gemm256.hip in gemm_epilogue.h; the codes: GemmEpilogue in ap_common.h.
 //
 // Roofline: MFMA (2*M*N*K flop); HBM traffic ~ A once + output once (weights L2-resident).
 #include "ap_common.h"
+#include "gemm_mma.h"
 
 namespace ap {
 namespace {
@@ -38,24 +41,6 @@ constexpr int kTile = 128;            // BM = BN
 constexpr int kRowBytes = 128;        // bytes of K per tile row
 constexpr int kTileBytes = kTile * kRowBytes;   // 16 KiB per operand tile
 constexpr int kBufBytes = 2 * kTileBytes;       // W tile + A tile
-
-template <typename T> struct Mma;
-template <> struct Mma<f16> {
-    using Frag = f16x8;
-    static __device__ __forceinline__ f32x16 run(Frag a, Frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Mma<bf16> {
-    using Frag = bf16x8;
-    static __device__ __forceinline__ f32x16 run(Frag a, Frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-};
-
-__device__ __forceinline__ float gelu_erf(float x) {
-    return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
-}
 
 template <typename T> __device__ __forceinline__ void store4(T* p, f32x4 v);
 template <> __device__ __forceinline__ void store4<float>(float* p, f32x4 v) { *(f32x4*)p = v; }
@@ -68,68 +53,19 @@ template <> __device__ __forceinline__ void store4<bf16>(bf16* p, f32x4 v) {
     *(bf16x4*)p = h;
 }
 
-// ---- fused-LayerNorm epilogues (twins of gemm256.hip's, bit for bit: a problem may be served by either kernel) ----
-// A lane holds 4 consecutive n of one row (two packed pairs); its partner lane ^ 32 holds the next 4.  The persistent
+// ---- fused-LayerNorm epilogues (twins of gemm256.hip's, bit for bit: a problem may be served by either kernel; the
+// arithmetic both call is in gemm_epilogue.h) ----
+// Row statistics: a lane holds 4 consecutive n of one row (two packed pairs); its partner lane ^ 32 holds the next 4.  The persistent
 // kernel sums a 16-byte chunk (8 columns) as ONE chain  s = dot2(c3, dot2(c2, dot2(c1, dot2(c0, 0))))  and then combines
-// the 8 chunks of a 64-column group as ((s0+s1)+(s2+s3)) + ((s4+s5)+(s6+s7)); here the chain starts on the lower lane,
-// crosses to the partner through one v_permlane32_swap and finishes there, and the tree is evaluated in that lane.
-template <typename T> __device__ __forceinline__ u32x2 resid_add4(u32x2 d, u32x2 r);
-template <> __device__ __forceinline__ u32x2 resid_add4<f16>(u32x2 d, u32x2 r) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    u32x2 y;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const uint32_t dk = d[k], rk = r[k];
-        y[k] = __builtin_bit_cast(uint32_t, (h2)(__builtin_bit_cast(h2, dk) + __builtin_bit_cast(h2, rk)));
-    }
-    return y;
-}
-template <> __device__ __forceinline__ u32x2 resid_add4<bf16>(u32x2 d, u32x2 r) {
-    u32x2 y;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const float d0 = __builtin_bit_cast(float, d[k] << 16), d1 = __builtin_bit_cast(float, d[k] & 0xffff0000u);
-        const float r0 = __builtin_bit_cast(float, r[k] << 16), r1 = __builtin_bit_cast(float, r[k] & 0xffff0000u);
-        const bf16x4 c4 = {(bf16)(d0 + r0), (bf16)(d1 + r1), (bf16)0.0f, (bf16)0.0f};
-        y[k] = __builtin_bit_cast(u32x2, c4)[0];
-    }
-    return y;
-}
-template <typename T> __device__ __forceinline__ void stats_chain4(u32x2 y, float& s, float& q);
-template <> __device__ __forceinline__ void stats_chain4<f16>(u32x2 y, float& s, float& q) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const uint32_t yk = y[k];
-        const h2 c = __builtin_bit_cast(h2, yk);
-        s = __builtin_amdgcn_fdot2(c, h2{(_Float16)1.0f, (_Float16)1.0f}, s, false);
-        q = __builtin_amdgcn_fdot2(c, c, q, false);
-    }
-}
-template <> __device__ __forceinline__ void stats_chain4<bf16>(u32x2 y, float& s, float& q) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const float c0 = __builtin_bit_cast(float, y[k] << 16), c1 = __builtin_bit_cast(float, y[k] & 0xffff0000u);
-        s += c0 + c1;
-        q = __builtin_fmaf(c1, c1, __builtin_fmaf(c0, c0, q));
-    }
-}
+// the 8 chunks of a 64-column group as ((s0+s1)+(s2+s3)) + ((s4+s5)+(s6+s7)); here the chain (stats2 per dword) starts on the
+// lower lane, crosses to the partner through one v_permlane32_swap and finishes there, and the tree is evaluated in that lane.
+
 // value of the partner lane (lane ^ 32)
 __device__ __forceinline__ float partner32(float v) {
     float a = v, b = v;
     asm volatile("v_nop\n\tv_nop\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));     // a = {lo, lo}, b = {hi, hi}
     return (threadIdx.x & 32) ? a : b;
 }
-template <typename T> __device__ __forceinline__ u32x2 pack4t(f32x4 v);
-template <> __device__ __forceinline__ u32x2 pack4t<f16>(f32x4 v) {
-    f16x4 h = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
-    return __builtin_bit_cast(u32x2, h);
-}
-template <> __device__ __forceinline__ u32x2 pack4t<bf16>(f32x4 v) {
-    bf16x4 h = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-    return __builtin_bit_cast(u32x2, h);
-}
-template <> __device__ __forceinline__ u32x2 pack4t<float>(f32x4) { return u32x2{0, 0}; }
 
 // 8 f32 -> hi (f16, round to nearest) and lo = f16((x - hi) * 2^11): x = hi + lo * 2^-11 to ~2^-22 |x|
 // (~3.7 VALU per value as hipcc compiles it; measured: a kernel with the split removed altogether is 10 % faster, with
@@ -214,11 +150,10 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
         for (int g4 = 0; g4 < 4; ++g4) {
             const int nb = n0 + wave_n * 64 + nt * 32 + g4 * 8 + hi * 4;
             const f32x4 b4 = !SPLIT || (nb < g.N && g.bias) ? *(const f32x4*)(g.bias + nb) : f32x4{0.f, 0.f, 0.f, 0.f};
-            constexpr bool kNormInit = EPI == EPI_NORM_STORE || EPI == EPI_NORM_GELU || EPI == EPI_NORM_SWIGLU || EPI == EPI_NORM_QGELU || EPI == EPI_NORM_GTANH;   // (these start from zero)
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) acc[nt][mt][g4 * 4 + e] = kNormInit ? 0.0f : b4[e];
+                for (int e = 0; e < 4; ++e) acc[nt][mt][g4 * 4 + e] = epi_is_norm(EPI) ? 0.0f : b4[e];     // (the NORM epilogues start from zero)
         }
 
     f32x16 accl[SPLIT ? 2 : 1][SPLIT ? 2 : 1];                      // split-f16: the 2^-11 terms
@@ -245,7 +180,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
         if (kt + 1 < nk) stage(cur ^ 1, kt + 1);
         const char* buf = smem + cur * kBufBytes;
         if constexpr (sizeof(T) == 2) {
-            using Frag = typename Mma<T>::Frag;
+            using Frag = typename Mma32x32<T>::Frag;
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
                 const int co = ((kk * 2 + hi) ^ xr) << 4;
@@ -253,10 +188,10 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
                 Frag w1 = *(const Frag*)(buf + rowW + 32 * kRowBytes + co);
                 Frag a0 = *(const Frag*)(buf + rowA + co);
                 Frag a1 = *(const Frag*)(buf + rowA + 32 * kRowBytes + co);
-                acc[0][0] = Mma<T>::run(w0, a0, acc[0][0]);
-                acc[0][1] = Mma<T>::run(w0, a1, acc[0][1]);
-                acc[1][0] = Mma<T>::run(w1, a0, acc[1][0]);
-                acc[1][1] = Mma<T>::run(w1, a1, acc[1][1]);
+                acc[0][0] = Mma32x32<T>::run(w0, a0, acc[0][0]);
+                acc[0][1] = Mma32x32<T>::run(w0, a1, acc[0][1]);
+                acc[1][0] = Mma32x32<T>::run(w1, a0, acc[1][0]);
+                acc[1][1] = Mma32x32<T>::run(w1, a1, acc[1][1]);
             }
         } else if constexpr (SPLIT) {
             // split-f16: W row = [hi 32 | lo 32] f16, A row = 32 f32.  MFMA step s covers k = 16 s .. 16 s + 15, the lane's
@@ -314,80 +249,51 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
     }
 
     // ---- epilogue: lane owns m = .. + l31 and, per (nt, g4), n = .. + 8*g4 + 4*hi + {0..3}
-    if constexpr (sizeof(T) == 2 && EPI == EPI_NORM_SWIGLU) {
-        // the wave's two n blocks are x1 and x2 of the same 32 output columns (interleaved weight rows, see ap_common.h)
+    constexpr EpiAct kAct = epi_act(EPI);
+    auto acc4 = [&](int nt, int mt, int g4) {
+        f32x4 v;
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            const int m = m0 + wave_m * 64 + mt * 32 + l31;
-            if (m >= g.M) continue;
-            const float rstd = g.rowstats[2 * (size_t)m], nmr = g.rowstats[2 * (size_t)m + 1];
-            const f32x2_t rs2 = {rstd, rstd}, nm2 = {nmr, nmr};
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                f32x4 y[2];
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    const int n = n0 + wave_n * 64 + nt * 32 + g4 * 8 + hi * 4;
-                    const f32x4 cs = *(const f32x4*)(g.colsum + n), bb = *(const f32x4*)(g.bias + n);
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc[nt][mt][g4 * 4 + e];
-                    const f32x2_t lo = __builtin_elementwise_fma(rs2, f32x2_t{v[0], v[1]},
-                        __builtin_elementwise_fma(nm2, f32x2_t{cs[0], cs[1]}, f32x2_t{bb[0], bb[1]}));
-                    const f32x2_t hi2 = __builtin_elementwise_fma(rs2, f32x2_t{v[2], v[3]},
-                        __builtin_elementwise_fma(nm2, f32x2_t{cs[2], cs[3]}, f32x2_t{bb[2], bb[3]}));
-                    y[nt] = f32x4{lo[0], lo[1], hi2[0], hi2[1]};
-                }
-                const f32x2_t a = swiglu2(f32x2_t{y[0][0], y[0][1]}, f32x2_t{y[1][0], y[1][1]});
-                const f32x2_t b = swiglu2(f32x2_t{y[0][2], y[0][3]}, f32x2_t{y[1][2], y[1][3]});
-                const int nout = ((n0 + wave_n * 64) >> 1) + g4 * 8 + hi * 4;
-                store4<T>((T*)g.out + (size_t)m * (size_t)g.ldo + nout, f32x4{a[0], a[1], b[0], b[1]});
-            }
-        }
-        return;
-    }
-    if constexpr (sizeof(T) == 2 && (EPI == EPI_NORM_STORE || EPI == EPI_NORM_GELU || EPI == EPI_NORM_QGELU || EPI == EPI_NORM_GTANH)) {
+        for (int e = 0; e < 4; ++e) v[e] = acc[nt][mt][g4 * 4 + e];
+        return v;
+    };
+    if constexpr (sizeof(T) == 2 && epi_is_norm(EPI)) {
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             const int m = m0 + wave_m * 64 + mt * 32 + l31;
             if (m >= g.M) continue;
             float rstd = g.rowstats[2 * (size_t)m], nmr = g.rowstats[2 * (size_t)m + 1];
-            if constexpr (EPI == EPI_NORM_GELU) { rstd *= kGeluS; nmr *= kGeluS; }      // y * kGeluS for the GELU routine (twin of gemm256)
+            if constexpr (kAct == ACT_GELU_S) { rstd *= kGeluS; nmr *= kGeluS; }      // y * kGeluS for the GELU routine (twin of gemm256)
             const f32x2_t rs2 = {rstd, rstd}, nm2 = {nmr, nmr};
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
+            auto norm4 = [&](int n, f32x4 v) {            // columns n .. n + 3 of the row
+                const f32x4 cs = *(const f32x4*)(g.colsum + n);
+                f32x4 bb = *(const f32x4*)(g.bias + n);
+                if constexpr (kAct == ACT_GELU_S) bb *= kGeluS;
+                return norm_affine4(rs2, nm2, v, cs, bb);
+            };
+            if constexpr (kAct == ACT_SWIGLU) {
+                // the wave's two n blocks are x1 and x2 of the same 32 output columns (interleaved weight rows, see ap_common.h)
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
-                    const int n = n0 + wave_n * 64 + nt * 32 + g4 * 8 + hi * 4;
-                    const f32x4 cs = *(const f32x4*)(g.colsum + n);
-                    f32x4 bb = *(const f32x4*)(g.bias + n);
-                    if constexpr (EPI == EPI_NORM_GELU) bb *= kGeluS;
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc[nt][mt][g4 * 4 + e];
-                    const f32x2_t lo = __builtin_elementwise_fma(rs2, f32x2_t{v[0], v[1]},
-                        __builtin_elementwise_fma(nm2, f32x2_t{cs[0], cs[1]}, f32x2_t{bb[0], bb[1]}));
-                    const f32x2_t hi2 = __builtin_elementwise_fma(rs2, f32x2_t{v[2], v[3]},
-                        __builtin_elementwise_fma(nm2, f32x2_t{cs[2], cs[3]}, f32x2_t{bb[2], bb[3]}));
-                    v = f32x4{lo[0], lo[1], hi2[0], hi2[1]};
-                    if constexpr (EPI == EPI_NORM_GELU) {
-                        const f32x2_t a = gelu_sigmoid_poly2_s(f32x2_t{v[0], v[1]}), b = gelu_sigmoid_poly2_s(f32x2_t{v[2], v[3]});
-                        v = f32x4{a[0], a[1], b[0], b[1]};
-                    }
-                    if constexpr (EPI == EPI_NORM_QGELU) {
-                        const f32x2_t a = quick_gelu2(f32x2_t{v[0], v[1]}), b = quick_gelu2(f32x2_t{v[2], v[3]});
-                        v = f32x4{a[0], a[1], b[0], b[1]};
-                    }
-                    if constexpr (EPI == EPI_NORM_GTANH) {
-                        const f32x2_t a = gelu_tanh2(f32x2_t{v[0], v[1]}), b = gelu_tanh2(f32x2_t{v[2], v[3]});
-                        v = f32x4{a[0], a[1], b[0], b[1]};
-                    }
-                    store4<T>((T*)g.out + (size_t)m * (size_t)g.ldo + n, v);
+                    const int n = n0 + wave_n * 64 + g4 * 8 + hi * 4;
+                    const f32x4 y0 = norm4(n, acc4(0, mt, g4)), y1 = norm4(n + 32, acc4(1, mt, g4));
+                    const f32x2_t a = swiglu2(f32x2_t{y0[0], y0[1]}, f32x2_t{y1[0], y1[1]});
+                    const f32x2_t b = swiglu2(f32x2_t{y0[2], y0[3]}, f32x2_t{y1[2], y1[3]});
+                    const int nout = ((n0 + wave_n * 64) >> 1) + g4 * 8 + hi * 4;
+                    store4<T>((T*)g.out + (size_t)m * (size_t)g.ldo + nout, f32x4{a[0], a[1], b[0], b[1]});
                 }
+            } else {
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                    for (int g4 = 0; g4 < 4; ++g4) {
+                        const int n = n0 + wave_n * 64 + nt * 32 + g4 * 8 + hi * 4;
+                        store4<T>((T*)g.out + (size_t)m * (size_t)g.ldo + n, act4<kAct>(norm4(n, acc4(nt, mt, g4))));
+                    }
+            }
         }
         return;
     }
-    if constexpr (sizeof(T) == 2 && (EPI == EPI_RESID_STATS || EPI == EPI_PATCH_STREAM)) {
+    if constexpr (sizeof(T) == 2 && epi_is_resid(EPI)) {
         constexpr bool kPatch = EPI == EPI_PATCH_STREAM;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
@@ -416,18 +322,22 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
                 for (int g4 = 0; g4 < 4; ++g4) {
                     const int n = n0 + wave_n * 64 + nt * 32 + g4 * 8 + hi * 4;
                     T* px = (T*)g.out + orow * (size_t)g.ldo + n;
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc[nt][mt][g4 * 4 + e];
+                    const f32x4 v = acc4(nt, mt, g4);
                     if constexpr (!kPatch) { if (cbr) *(f32x4*)(cbr + n) = v; }
-                    const u32x2 y = resid_add4<T>(pack4t<T>(v), *(const u32x2*)(srow + n));
+                    const u32x2 d = pack4<T>(v), r = *(const u32x2*)(srow + n);
+                    u32x2 y;
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        const uint32_t dk = d[k], rk = r[k];
+                        y[k] = resid_add2<T>(dk, rk);
+                    }
                     if (live) *(u32x2*)px = y;
                     // chain: lower lane (columns 0-3 of the chunk) first, then the partner continues with columns 4-7
                     float s = 0.f, q = 0.f;
-                    if (hi == 0) stats_chain4<T>(y, s, q);
+                    if (hi == 0) { stats2<T>(y[0], s, q); stats2<T>(y[1], s, q); }
                     s = partner32(s);                            // upper lane now holds the lower lane's partial chain
                     q = partner32(q);
-                    if (hi == 1) stats_chain4<T>(y, s, q);
+                    if (hi == 1) { stats2<T>(y[0], s, q); stats2<T>(y[1], s, q); }
                     cs8[nt * 4 + g4] = s;
                     cq8[nt * 4 + g4] = q;
                 }
@@ -467,15 +377,11 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
             for (int g4 = 0; g4 < 4; ++g4) {
                 const int n = n0 + wave_n * 64 + nt * 32 + g4 * 8 + hi * 4;
                 if constexpr (SPLIT) { if (n >= g.N) continue; }
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[nt][mt][g4 * 4 + e];
+                f32x4 v = acc4(nt, mt, g4);
                 if constexpr (SPLIT && (EPI == EPI_BIAS_STORE || EPI == EPI_BIAS_GELU)) {
                     // separate residual (the SAM2 trunk's x = shortcut + f(x)): added AFTER the activation, GemmArgs::resid
-                    if constexpr (EPI == EPI_BIAS_GELU) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
-                    }
+                    for (int e = 0; e < 4; ++e) v[e] = act_f32<kAct>(v[e]);
                     if (g.resid) {
                         const f32x4 r = *(const f32x4*)(g.resid + (size_t)rrow * (size_t)g.ldr + n);
 #pragma unroll
@@ -489,36 +395,12 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
                         for (int e = 0; e < 4; ++e) v[e] *= ga[e];
                     }
                     store4<T>((T*)g.out + orow + n, v);
-                } else if constexpr (EPI == EPI_BIAS_GELU) {
+                } else if constexpr (kAct != ACT_NONE && !epi_is_norm(EPI)) {      // EPI_BIAS_<activation>
+                    if constexpr (sizeof(T) == 2) {      // the packed routines of gemm256: the two kernels stay bit-identical
+                        v = act4<kAct>(v);
+                    } else {                             // float32: libm
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) if (sizeof(T) != 2) v[e] = gelu_erf(v[e]);
-                    if constexpr (sizeof(T) == 2) {      // the same packed routine as gemm256: the two kernels stay bit-identical
-                        const f32x2_t lo = gelu_sigmoid_poly2(f32x2_t{v[0], v[1]}), hi2 = gelu_sigmoid_poly2(f32x2_t{v[2], v[3]});
-                        v = f32x4{lo[0], lo[1], hi2[0], hi2[1]};
-                    }
-                    store4<T>((T*)g.out + orow + n, v);
-                } else if constexpr (EPI == EPI_BIAS_QGELU) {
-                    if constexpr (sizeof(T) == 2) {      // the packed routine of gemm256 (bit-identical); float32: libm expf
-                        const f32x2_t lo = quick_gelu2(f32x2_t{v[0], v[1]}), hi2 = quick_gelu2(f32x2_t{v[2], v[3]});
-                        v = f32x4{lo[0], lo[1], hi2[0], hi2[1]};
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = v[e] / (1.0f + expf(-1.702f * v[e]));
-                    }
-                    store4<T>((T*)g.out + orow + n, v);
-                } else if constexpr (EPI == EPI_BIAS_GTANH) {
-                    if constexpr (sizeof(T) == 2) {      // the packed routine of gemm256 (bit-identical)
-                        const f32x2_t lo = gelu_tanh2(f32x2_t{v[0], v[1]}), hi2 = gelu_tanh2(f32x2_t{v[2], v[3]});
-                        v = f32x4{lo[0], lo[1], hi2[0], hi2[1]};
-                    } else {
-                        // float32: x / (1 + exp(-2 u)) with libm expf keeps the RELATIVE accuracy in the negative tail, where
-                        // 1 + tanhf(u) cancels; u = sqrt(2 / pi) (x + 0.044715 x^3) by two fma
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float x = v[e];
-                            const float u2 = -1.5957691216057308f * fmaf(0.044715f * x * x, x, x);
-                            v[e] = x / (1.0f + expf(u2));
-                        }
+                        for (int e = 0; e < 4; ++e) v[e] = act_f32<kAct>(v[e]);
                     }
                     store4<T>((T*)g.out + orow + n, v);
                 } else if constexpr (EPI == EPI_BIAS_RESID) {
@@ -543,43 +425,18 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
     }
 }
 
-// float32 buffers, split-f16 products (GemmArgs::split; W = the [hi | lo] rows of launch_split_f16_weights)
-int launch_split(int epilogue, const GemmArgs& a, hipStream_t stream) {
-    const int tiles = ((a.M + kTile - 1) / kTile) * ((a.N + kTile - 1) / kTile);
-    dim3 grid(tiles), block(256);
-    switch (epilogue) {
-        case EPI_BIAS_STORE: gemm_kernel<float, EPI_BIAS_STORE, true><<<grid, block, 0, stream>>>(a); break;
-        case EPI_BIAS_GELU: gemm_kernel<float, EPI_BIAS_GELU, true><<<grid, block, 0, stream>>>(a); break;
-        case EPI_BIAS_RESID: gemm_kernel<float, EPI_BIAS_RESID, true><<<grid, block, 0, stream>>>(a); break;
-        case EPI_PATCH_EMBED: gemm_kernel<float, EPI_PATCH_EMBED, true><<<grid, block, 0, stream>>>(a); break;
-        case EPI_BIAS_QGELU: gemm_kernel<float, EPI_BIAS_QGELU, true><<<grid, block, 0, stream>>>(a); break;
-        case EPI_BIAS_GTANH: gemm_kernel<float, EPI_BIAS_GTANH, true><<<grid, block, 0, stream>>>(a); break;
-        default: set_error("gemm: epilogue %d has no split-f16 form", epilogue); return AP_ERR_INVALID;
-    }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
-}
-
-template <typename T>
+// SPLIT: float32 buffers, split-f16 products (GemmArgs::split; W = the [hi | lo] rows of launch_split_f16_weights)
+template <typename T, bool SPLIT = false>
 int launch_typed(int epilogue, const GemmArgs& a, hipStream_t stream) {
-    const int tiles = ((a.M + kTile - 1) / kTile) * (a.N / kTile);
+    const int tiles = ((a.M + kTile - 1) / kTile) * (SPLIT ? (a.N + kTile - 1) / kTile : a.N / kTile);
     dim3 grid(tiles), block(256);
-    switch (epilogue) {
-        case EPI_BIAS_STORE: gemm_kernel<T, EPI_BIAS_STORE><<<grid, block, 0, stream>>>(a); break;
-        case EPI_BIAS_GELU: gemm_kernel<T, EPI_BIAS_GELU><<<grid, block, 0, stream>>>(a); break;
-        case EPI_BIAS_RESID: gemm_kernel<T, EPI_BIAS_RESID><<<grid, block, 0, stream>>>(a); break;
-        case EPI_PATCH_EMBED: gemm_kernel<T, EPI_PATCH_EMBED><<<grid, block, 0, stream>>>(a); break;
-        case EPI_NORM_STORE: gemm_kernel<T, EPI_NORM_STORE><<<grid, block, 0, stream>>>(a); break;
-        case EPI_NORM_GELU: gemm_kernel<T, EPI_NORM_GELU><<<grid, block, 0, stream>>>(a); break;
-        case EPI_NORM_SWIGLU: gemm_kernel<T, EPI_NORM_SWIGLU><<<grid, block, 0, stream>>>(a); break;
-        case EPI_NORM_QGELU: gemm_kernel<T, EPI_NORM_QGELU><<<grid, block, 0, stream>>>(a); break;
-        case EPI_BIAS_QGELU: gemm_kernel<T, EPI_BIAS_QGELU><<<grid, block, 0, stream>>>(a); break;
-        case EPI_NORM_GTANH: gemm_kernel<T, EPI_NORM_GTANH><<<grid, block, 0, stream>>>(a); break;
-        case EPI_BIAS_GTANH: gemm_kernel<T, EPI_BIAS_GTANH><<<grid, block, 0, stream>>>(a); break;
-        case EPI_RESID_STATS: gemm_kernel<T, EPI_RESID_STATS><<<grid, block, 0, stream>>>(a); break;
-        case EPI_PATCH_STREAM: gemm_kernel<T, EPI_PATCH_STREAM><<<grid, block, 0, stream>>>(a); break;
-        default: set_error("gemm: unknown epilogue %d", epilogue); return AP_ERR_INVALID;
-    }
+    const int err = dispatch_epilogue(epilogue, [&](auto e) {
+        constexpr int EPI = decltype(e)::value;
+        if constexpr (SPLIT ? epi_has_split(EPI) : epi_known(EPI)) { gemm_kernel<T, EPI, SPLIT><<<grid, block, 0, stream>>>(a); return (int)AP_OK; }
+        else if constexpr (SPLIT) { set_error("gemm: epilogue %d has no split-f16 form", epilogue); return (int)AP_ERR_INVALID; }
+        else { set_error("gemm: unknown epilogue %d", epilogue); return (int)AP_ERR_INVALID; }
+    });
+    if (err != AP_OK) return err;
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }
@@ -603,21 +460,13 @@ int launch_gemm_impl(int dtype, int epilogue, const GemmArgs& a, int impl, int v
         return AP_ERR_UNSUPPORTED;
 #endif
     }
-    const bool fused_epi = epilogue == EPI_NORM_STORE || epilogue == EPI_NORM_GELU || epilogue == EPI_NORM_SWIGLU || epilogue == EPI_NORM_QGELU ||
-                           epilogue == EPI_NORM_GTANH || epilogue == EPI_RESID_STATS ||
-                           epilogue == EPI_PATCH_STREAM;
+    const bool fused_epi = epi_is_norm(epilogue) || epi_is_resid(epilogue);
     AP_REQUIRE(!fused_epi || dtype != AP_F32, "gemm: the fused-LayerNorm epilogues are f16 / bf16 only");
-    AP_REQUIRE(!fused_epi || (epilogue == EPI_RESID_STATS ? a.partial != nullptr :
-                              epilogue == EPI_PATCH_STREAM ? (a.partial && a.pos16 && a.P > 0 && a.R >= 0) : (a.colsum && a.rowstats)),
-               "gemm: missing operand for the fused-LayerNorm epilogue %d", epilogue);
+    AP_REQUIRE(epi_operands_ok(epilogue, a), "gemm: missing operand for the fused-LayerNorm epilogue %d", epilogue);
     // Kernel choice (results are bit-identical either way).  The persistent 256 x 256 kernel needs about one tile per CU to
     // pay: with few row tiles and a narrow N (proj / fc2 of a 32-tile extract_batch: 75 tiles for 256 CUs) the 128 x 128
     // kernel's four times as many workgroups finish sooner.
-    static const int num_cu = [] {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-        return prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }();
+    const int num_cu = device_cu_count();
     const long tiles256 = (long)((a.M + 255) / 256) * (a.N / 256);
     const bool few_tiles = tiles256 * 2 <= num_cu && a.N % kTile == 0;
     if (impl == 256 || (impl == 0 && a.M >= 256 && !few_tiles && gemm256_supports(dtype, epilogue, a)))
@@ -632,7 +481,7 @@ int launch_gemm_impl(int dtype, int epilogue, const GemmArgs& a, int impl, int v
                "gemm: row strides must be 16-byte multiples");
     if (a.split) {
         AP_REQUIRE(dtype == AP_F32, "gemm: the split-f16 product runs on float32 buffers");
-        return launch_split(epilogue, a, stream);
+        return launch_typed<float, true>(epilogue, a, stream);
     }
     switch (dtype) {
         case AP_F16: return launch_typed<f16>(epilogue, a, stream);

@@ -43,7 +43,9 @@
 //  * accumulators start from the bias; epilogue: (GELU | *LayerScale) in registers, transposed through the wave's private LDS
 //    scratch (XOR-swizzled) so that global stores / the f32 residual read-modify-write are whole
 //    128-byte rows, 16 B per lane.
-//  * fused-LayerNorm epilogues (EPI_NORM_STORE / EPI_NORM_GELU / EPI_RESID_STATS / EPI_PATCH_STREAM, see ap_common.h): the A operand
+//  * the epilogue family (which epilogues exist, their traits, activations and the LayerNorm-affine step) is defined once for
+//    this kernel and gemm.hip in gemm_epilogue.h; the codes and what each computes: GemmEpilogue in ap_common.h.
+//  * fused-LayerNorm epilogues (EPI_NORM_* / EPI_RESID_STATS / EPI_PATCH_STREAM): the A operand
 //    is the raw 16-bit residual stream; NORM applies the row statistics and the rank-one mean correction per element
 //    (accumulators start from zero there), RESID_STATS / PATCH_STREAM add the accumulator to the stream window (or to the
 //    position-embedding row) after the transposition, 16 bytes per lane, and emit per-row partial sums for the next
@@ -141,16 +143,16 @@ template <typename T, int EPI>
 __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
     __shared__ __attribute__((aligned(16))) char smem[kLdsBytes];
 
-    constexpr bool kNorm = EPI == EPI_NORM_STORE || EPI == EPI_NORM_GELU || EPI == EPI_NORM_SWIGLU || EPI == EPI_NORM_QGELU || EPI == EPI_NORM_GTANH;
-    constexpr bool kSwiglu = EPI == EPI_NORM_SWIGLU;       // x1 | x2 in the wave's two n blocks -> 32 gated output columns
+    constexpr bool kNorm = epi_is_norm(EPI), kRes = epi_is_resid(EPI);         // the traits: gemm_epilogue.h
+    constexpr EpiAct kAct = epi_act(EPI);
+    constexpr bool kSwiglu = kAct == ACT_SWIGLU;           // x1 | x2 in the wave's two n blocks -> 32 gated output columns
     constexpr bool kPatch = EPI == EPI_PATCH_STREAM;
-    constexpr bool kRes = EPI == EPI_RESID_STATS || kPatch;
     constexpr bool kStoreNT = !kRes && EPI != EPI_BIAS_RESID;       // every epilogue whose 16-bit output another kernel reads next
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wr = wave >> 2, wc = wave & 3;
     const AccMap am(lane);
-    using Frag = typename Mma<T>::Frag;
+    using Frag = typename Mma16x16<T>::Frag;
 
     // ---- tile list (XCD-aware, see header)
     TileWalk tw;
@@ -316,7 +318,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
     __builtin_amdgcn_sched_barrier(0);                        \
     if (!(kDiag && abl_nobar)) __builtin_amdgcn_s_barrier();  \
     __builtin_amdgcn_sched_barrier(0)
-#define AP_MMA(ACC, B, A) ACC = Mma<T>::run(B, A, ACC)
+#define AP_MMA(ACC, B, A) ACC = Mma16x16<T>::run(B, A, ACC)
     // A phase = 64 m x 32 n x 64 k per wave = 16 MFMAs.  AP_MMA2: activation block J (16 rows) of X-unit half H against both weight
     // blocks of the phase's Y unit (fragments FB, accumulator column block NB), k-step KK; AP_MMA8: the four blocks J of one k-step.
 #define AP_MMA2(NB, H, FB, J, KK)                                                      \
@@ -647,7 +649,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
             AP_BIAS_WAIT(0);
         }
         stamp(ti, 2);
-        if constexpr (EPI == EPI_NORM_GELU) {
+        if constexpr (kAct == ACT_GELU_S) {
             // the GELU routine takes y * kGeluS (its clamp is the packed multiply's CLAMP bit, ap_common.h): scale the tile's bias
             // registers and the rows' (rstd, -mean rstd) once -- 16 packed multiplies per tile and wave instead of 128 v_min
 #pragma unroll
@@ -710,13 +712,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
                     const f32x2_t rs2 = {rst[mb][mh][0], rst[mb][mh][0]}, nm2 = {rst[mb][mh][1], rst[mb][mh][1]};
                     f32x4 y[2];
 #pragma unroll
-                    for (int nb = 0; nb < 2; ++nb) {
-                        const f32x2_t lo = __builtin_elementwise_fma(rs2, f32x2_t{acc[nb][mb][g4][0], acc[nb][mb][g4][1]},
-                            __builtin_elementwise_fma(nm2, f32x2_t{ncs[nb][nh][0], ncs[nb][nh][1]}, f32x2_t{nbias[nb][nh][0], nbias[nb][nh][1]}));
-                        const f32x2_t hi2 = __builtin_elementwise_fma(rs2, f32x2_t{acc[nb][mb][g4][2], acc[nb][mb][g4][3]},
-                            __builtin_elementwise_fma(nm2, f32x2_t{ncs[nb][nh][2], ncs[nb][nh][3]}, f32x2_t{nbias[nb][nh][2], nbias[nb][nh][3]}));
-                        y[nb] = f32x4{lo[0], lo[1], hi2[0], hi2[1]};
-                    }
+                    for (int nb = 0; nb < 2; ++nb) y[nb] = norm_affine4(rs2, nm2, acc[nb][mb][g4], ncs[nb][nh], nbias[nb][nh]);
                     const f32x2_t a = swiglu2(f32x2_t{y[0][0], y[0][1]}, f32x2_t{y[1][0], y[1][1]});
                     const f32x2_t b = swiglu2(f32x2_t{y[0][2], y[0][3]}, f32x2_t{y[1][2], y[1][3]});
                     // row m of the 32-row block, 8 bytes at output column n: 16-byte chunk n / 8 (XOR row & 3), half (n / 4) & 1
@@ -738,31 +734,11 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
                         const int nh = AccMap::nh(g4), mh = AccMap::mh(g4);
                         f32x4 v = acc[nb][mb][g4];
                         if constexpr (kNorm) {
-                            // two values per instruction (v_pk_fma_f32): y = rstd * acc + (nmr * colsum + bias)
-                            // (EPI_NORM_GELU: rst and nbias were multiplied by kGeluS above -> y * kGeluS, what the GELU routine takes)
+                            // (ACT_GELU_S: rst and nbias were multiplied by kGeluS above -> y * kGeluS, what the GELU routine takes)
                             const f32x2_t rs2 = {rst[mb][mh][0], rst[mb][mh][0]}, nm2 = {rst[mb][mh][1], rst[mb][mh][1]};
-                            const f32x2_t lo = __builtin_elementwise_fma(rs2, f32x2_t{v[0], v[1]},
-                                __builtin_elementwise_fma(nm2, f32x2_t{ncs[nb][nh][0], ncs[nb][nh][1]}, f32x2_t{nbias[nb][nh][0], nbias[nb][nh][1]}));
-                            const f32x2_t hi2 = __builtin_elementwise_fma(rs2, f32x2_t{v[2], v[3]},
-                                __builtin_elementwise_fma(nm2, f32x2_t{ncs[nb][nh][2], ncs[nb][nh][3]}, f32x2_t{nbias[nb][nh][2], nbias[nb][nh][3]}));
-                            v = f32x4{lo[0], lo[1], hi2[0], hi2[1]};
+                            v = norm_affine4(rs2, nm2, v, ncs[nb][nh], nbias[nb][nh]);
                         }
-                        if constexpr (EPI == EPI_BIAS_GELU) {
-                            const f32x2_t lo = gelu_sigmoid_poly2(f32x2_t{v[0], v[1]}), hi2 = gelu_sigmoid_poly2(f32x2_t{v[2], v[3]});
-                            v = f32x4{lo[0], lo[1], hi2[0], hi2[1]};
-                        }
-                        if constexpr (EPI == EPI_NORM_GELU) {
-                            const f32x2_t lo = gelu_sigmoid_poly2_s(f32x2_t{v[0], v[1]}), hi2 = gelu_sigmoid_poly2_s(f32x2_t{v[2], v[3]});
-                            v = f32x4{lo[0], lo[1], hi2[0], hi2[1]};
-                        }
-                        if constexpr (EPI == EPI_BIAS_QGELU || EPI == EPI_NORM_QGELU) {
-                            const f32x2_t lo = quick_gelu2(f32x2_t{v[0], v[1]}), hi2 = quick_gelu2(f32x2_t{v[2], v[3]});
-                            v = f32x4{lo[0], lo[1], hi2[0], hi2[1]};
-                        }
-                        if constexpr (EPI == EPI_BIAS_GTANH || EPI == EPI_NORM_GTANH) {
-                            const f32x2_t lo = gelu_tanh2(f32x2_t{v[0], v[1]}), hi2 = gelu_tanh2(f32x2_t{v[2], v[3]});
-                            v = f32x4{lo[0], lo[1], hi2[0], hi2[1]};
-                        }
+                        v = act4<kAct>(v);
                         if (has_gamma) {
                             const f32x4 ga = *(const f32x4*)(gp + nb * 32 + nh * 16);
 #pragma unroll
@@ -826,22 +802,11 @@ int launch_epi(const GemmArgs& a, int num_cu, int variant, hipStream_t stream) {
 
 template <typename T>
 int launch_typed(int epilogue, const GemmArgs& a, int num_cu, int variant, hipStream_t stream) {
-    switch (epilogue) {
-        case EPI_BIAS_STORE: return launch_epi<T, EPI_BIAS_STORE>(a, num_cu, variant, stream);
-        case EPI_BIAS_GELU: return launch_epi<T, EPI_BIAS_GELU>(a, num_cu, variant, stream);
-        case EPI_BIAS_RESID: return launch_epi<T, EPI_BIAS_RESID>(a, num_cu, variant, stream);
-        case EPI_NORM_STORE: return launch_epi<T, EPI_NORM_STORE>(a, num_cu, variant, stream);
-        case EPI_NORM_GELU: return launch_epi<T, EPI_NORM_GELU>(a, num_cu, variant, stream);
-        case EPI_NORM_SWIGLU: return launch_epi<T, EPI_NORM_SWIGLU>(a, num_cu, variant, stream);
-        case EPI_NORM_QGELU: return launch_epi<T, EPI_NORM_QGELU>(a, num_cu, variant, stream);
-        case EPI_BIAS_QGELU: return launch_epi<T, EPI_BIAS_QGELU>(a, num_cu, variant, stream);
-        case EPI_NORM_GTANH: return launch_epi<T, EPI_NORM_GTANH>(a, num_cu, variant, stream);
-        case EPI_BIAS_GTANH: return launch_epi<T, EPI_BIAS_GTANH>(a, num_cu, variant, stream);
-        case EPI_RESID_STATS: return launch_epi<T, EPI_RESID_STATS>(a, num_cu, variant, stream);
-        case EPI_PATCH_STREAM: return launch_epi<T, EPI_PATCH_STREAM>(a, num_cu, variant, stream);
-    }
-    set_error("gemm256: unsupported epilogue %d", epilogue);
-    return AP_ERR_INVALID;
+    return dispatch_epilogue(epilogue, [&](auto e) {
+        constexpr int EPI = decltype(e)::value;
+        if constexpr (epi_in_gemm256(EPI)) return launch_epi<T, EPI>(a, num_cu, variant, stream);
+        else { set_error("gemm256: unsupported epilogue %d", epilogue); return (int)AP_ERR_INVALID; }
+    });
 }
 
 }  // namespace
@@ -857,16 +822,8 @@ extern int g_gemm_trace_tiles;
 
 bool AP_G256_FN(gemm256_supports)(int dtype, int epilogue, const GemmArgs& a) {
     if (dtype != AP_F16 && dtype != AP_BF16) return false;
-    if (epilogue != EPI_BIAS_STORE && epilogue != EPI_BIAS_GELU && epilogue != EPI_BIAS_RESID &&
-        epilogue != EPI_NORM_STORE && epilogue != EPI_NORM_GELU && epilogue != EPI_NORM_SWIGLU && epilogue != EPI_RESID_STATS &&
-        epilogue != EPI_NORM_QGELU && epilogue != EPI_BIAS_QGELU && epilogue != EPI_NORM_GTANH && epilogue != EPI_BIAS_GTANH &&
-        epilogue != EPI_PATCH_STREAM)
-        return false;
-    if (epilogue == EPI_PATCH_STREAM && (!a.partial || !a.pos16 || a.P <= 0 || a.R < 0 || a.M >= (1 << 24))) return false;
-    if ((epilogue == EPI_NORM_STORE || epilogue == EPI_NORM_GELU || epilogue == EPI_NORM_SWIGLU || epilogue == EPI_NORM_QGELU ||
-         epilogue == EPI_NORM_GTANH) &&
-        (!a.colsum || !a.rowstats)) return false;
-    if (epilogue == EPI_RESID_STATS && !a.partial) return false;
+    if (!epi_in_gemm256(epilogue) || !epi_operands_ok(epilogue, a)) return false;
+    if (epilogue == EPI_PATCH_STREAM && a.M >= (1 << 24)) return false;      // its m / P by a float estimate
     if (a.N % kBN != 0 || a.K % 128 != 0 || a.K < 128) return false;
     if (((size_t)a.lda * 2) % 16 != 0 || ((size_t)a.ldw * 2) % 16 != 0) return false;
     if ((size_t)255 * a.lda * 2 + 128 > 0xffffffffull || (size_t)255 * a.ldw * 2 + 128 > 0xffffffffull) return false;
@@ -877,14 +834,7 @@ bool AP_G256_FN(gemm256_supports)(int dtype, int epilogue, const GemmArgs& a) {
 }
 
 int AP_G256_FN(launch_gemm256)(int dtype, int epilogue, const GemmArgs& a, int variant, hipStream_t stream) {
-    static int num_cu = 0;
-    if (num_cu == 0) {
-        int dev = 0;
-        AP_HIP_CHECK(hipGetDevice(&dev));
-        hipDeviceProp_t prop;
-        AP_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    const int num_cu = device_cu_count();
     AP_REQUIRE(AP_G256_FN(gemm256_supports)(dtype, epilogue, a), "gemm256: unsupported problem");
     GemmArgs b = a;
     b.trace = nullptr; b.trace_tiles = 0; b.skew_ticks = 0; b.ablate = 0;

@@ -65,7 +65,7 @@ __device__ __forceinline__ size_t source_pixel(const WaArgs& a, long win, int yi
 
 template <typename T>
 __global__ __launch_bounds__(WA_WAVES * 64) void swin_window_attention_mma(WaArgs a) {
-    using Frag = typename Mma<T>::Frag;
+    using Frag = typename Mma16x16<T>::Frag;
     __shared__ __attribute__((aligned(16))) T vt_all[WA_WAVES][HD * VT_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, q = lane >> 4;
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(WA_WAVES * 64) void swin_window_attention_mma(WaArg
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
 #pragma unroll
-            for (int jt = 0; jt < 4; ++jt) s[it][jt] = Mma<T>::run(kf[jt], qf[it], f32x4{0.f, 0.f, 0.f, 0.f});
+            for (int jt = 0; jt < 4; ++jt) s[it][jt] = Mma16x16<T>::run(kf[jt], qf[it], f32x4{0.f, 0.f, 0.f, 0.f});
             const bool qhy = ty[it] >= edge, qhx = tx[it] >= edge;
             float m = -3.0e38f;
 #pragma unroll
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(WA_WAVES * 64) void swin_window_attention_mma(WaArg
             for (int dt = 0; dt < 2; ++dt) {
                 f32x4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int ks = 0; ks < 2; ++ks) o = Mma<T>::run(vtf[dt][ks], pf[ks], o);
+                for (int ks = 0; ks < 2; ++ks) o = Mma16x16<T>::run(vtf[dt][ks], pf[ks], o);
                 o *= inv[it];
                 if (ok && tv[it]) *(u32x2*)(out + pix[it] * (size_t)C + head * HD + dt * 16 + q * 4) = pack4<T>(o);
             }

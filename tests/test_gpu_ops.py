@@ -9,7 +9,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-EPI = {"bias": 0, "gelu": 1, "resid": 2}
+EPI = {"bias": 0, "gelu": 1, "resid": 2, "quick_gelu": 10, "gelu_tanh": 12}
 
 
 @pytest.fixture(scope="module")
@@ -28,10 +28,16 @@ def _gemm(env, dt, epi, A, W, bias, gamma, out, impl):
     torch.cuda.synchronize()
 
 
+_PERSISTENT_SHAPES = [(300, 256, 128), (1182, 768, 768), (100, 256, 384), (3941, 768, 3072), (20000, 2304, 768)]
+# QuickGELU / tanh-GELU at two of the shapes: the smallest the 256 kernel accepts (N % 256, K >= 128) with a ragged second
+# row tile, and the one with more tiles (711) than CUs, so that the tile seam and the next tile's bias run
+_PERSISTENT_CASES = [(i, e) for i in range(len(_PERSISTENT_SHAPES)) for e in ("bias", "gelu", "resid")] + \
+                    [(i, e) for i in (0, 4) for e in ("quick_gelu", "gelu_tanh")]
+
+
 @pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
-@pytest.mark.parametrize("epi", ["bias", "gelu", "resid"])
-@pytest.mark.parametrize("shape", [(300, 256, 128), (1182, 768, 768), (100, 256, 384), (3941, 768, 3072),
-                                   (20000, 2304, 768)])
+@pytest.mark.parametrize("shape,epi", [(_PERSISTENT_SHAPES[i], e) for i, e in _PERSISTENT_CASES],
+                         ids=[f"shape{i}-{e}" for i, e in _PERSISTENT_CASES])
 def test_gemm_persistent_kernel_vs_torch(env, dt, epi, shape):
     """256x256 persistent kernel (impl 256): ragged M, one-tile and multi-tile-per-workgroup problems, all
     epilogues; also bit-identical to the 128x128 kernel (the product may pick either by problem size)."""
@@ -41,11 +47,15 @@ def test_gemm_persistent_kernel_vs_torch(env, dt, epi, shape):
     A = (torch.rand((M, K), device=dev, generator=g) * 2 - 1).to(dt)
     W = ((torch.rand((N, K), device=dev, generator=g) * 2 - 1) * (2.0 / K ** 0.5)).to(dt)
     bias = torch.rand(N, device=dev, generator=g) - 0.5
-    gamma = torch.rand(N, device=dev, generator=g) + 0.5 if epi != "gelu" and M % 2 else None
+    gamma = torch.rand(N, device=dev, generator=g) + 0.5 if epi in ("bias", "resid") and M % 2 else None
     resid = torch.rand((M, N), device=dev, generator=g) if epi == "resid" else None
     ref = A.float() @ W.float().t() + bias
     if epi == "gelu":
         ref = torch.nn.functional.gelu(ref)
+    elif epi == "quick_gelu":
+        ref = ref * torch.sigmoid(1.702 * ref)
+    elif epi == "gelu_tanh":
+        ref = torch.nn.functional.gelu(ref, approximate="tanh")
     elif gamma is not None:
         ref = ref * gamma
     if epi == "resid":
@@ -180,17 +190,25 @@ def test_gemm_resid_stats_epilogue(env, dt, shape):
     assert (rs[:, 1].double() + mean * rstd).abs().max().item() < 2e-6
 
 
+NORM_ACT = {"none": 4, "gelu": 5, "quick_gelu": 9, "gelu_tanh": 11}          # AP_EPI_NORM*
+_NORM_ACT_ID = {"none": "False", "gelu": "True"}       # (the ids these cases had when the parameter was `gelu: bool`)
+_NORM_SHAPES = [(1, 768, 768), (300, 2304, 768), (20000, 3072, 768), (348 * 197, 1536, 1024)]
+# QuickGELU / tanh-GELU at two of the shapes; the second has 12 column tiles, which takes the grouped tile walk
+_NORM_CASES = [(i, a) for i in range(len(_NORM_SHAPES)) for a in ("none", "gelu")] + \
+              [(i, a) for i in (1, 2) for a in ("quick_gelu", "gelu_tanh")]
+
+
 @pytest.mark.parametrize("dt,tol", [(torch.float16, 1.5e-3), (torch.bfloat16, 1.2e-2)])
-@pytest.mark.parametrize("gelu", [False, True])
-@pytest.mark.parametrize("shape", [(1, 768, 768), (300, 2304, 768), (20000, 3072, 768), (348 * 197, 1536, 1024)])
-def test_gemm_norm_epilogue_equals_layernorm_then_linear(env, dt, tol, gelu, shape):
-    """AP_EPI_NORM / AP_EPI_NORM_GELU: rstd (x W'^T - mean colsum) + b' with W' = T(W gamma), b' = b + W beta equals
-    Linear(LayerNorm(x)) (+ GELU) computed by torch in float32 -- including rows with a mean far from zero, where the
+@pytest.mark.parametrize("shape,act", [(_NORM_SHAPES[i], a) for i, a in _NORM_CASES],
+                         ids=[f"shape{i}-{_NORM_ACT_ID.get(a, a)}" for i, a in _NORM_CASES])
+def test_gemm_norm_epilogue_equals_layernorm_then_linear(env, dt, tol, act, shape):
+    """AP_EPI_NORM / AP_EPI_NORM_GELU / AP_EPI_NORM_QUICK_GELU / AP_EPI_NORM_GELU_TANH: rstd (x W'^T - mean colsum) + b' with W' = T(W gamma), b' = b + W beta equals
+    Linear(LayerNorm(x)) (+ the activation) computed by torch in float32 -- including rows with a mean far from zero, where the
     rank-one mean correction cancels most of the accumulator.  Bound: rounding of the output to T plus the rounding of
     W gamma to T (element-wise, relative to the output scale)."""
     _lib, lib, dev, stream = env
     M, N, K = shape
-    g = torch.Generator(device=dev).manual_seed(M + N + K + int(gelu))
+    g = torch.Generator(device=dev).manual_seed(M + N + K + list(NORM_ACT).index(act))
     x = torch.randn((M, K), device=dev, generator=g) * 1.5
     x[: max(1, M // 4)] += 6.0                                  # rows with |mean| = 4 sigma
     x[:, 7] += 40.0                                             # one massive channel
@@ -210,15 +228,19 @@ def test_gemm_norm_epilogue_equals_layernorm_then_linear(env, dt, tol, gelu, sha
     outs = []
     for _ in range(3):
         out = torch.full((M, N), float("nan"), device=dev, dtype=dt)
-        _fused(env, dt, 5 if gelu else 4, x16, Wf, bf, colsum, stats, None, out)
+        _fused(env, dt, NORM_ACT[act], x16, Wf, bf, colsum, stats, None, out)
         outs.append(out)
     assert all(torch.equal(outs[0], o) for o in outs[1:])
     out128 = torch.full((M, N), float("nan"), device=dev, dtype=dt)
-    _fused(env, dt, 5 if gelu else 4, x16, Wf, bf, colsum, stats, None, out128, impl=128)
+    _fused(env, dt, NORM_ACT[act], x16, Wf, bf, colsum, stats, None, out128, impl=128)
     assert torch.equal(out128, outs[0])                      # 128 x 128 twin: same bits
     want = torch.nn.functional.layer_norm(x.float(), (K,), gamma, beta, 1e-6) @ Wl.t() + b
-    if gelu:
+    if act == "gelu":
         want = torch.nn.functional.gelu(want)
+    elif act == "quick_gelu":
+        want = want * torch.sigmoid(1.702 * want)
+    elif act == "gelu_tanh":
+        want = torch.nn.functional.gelu(want, approximate="tanh")
     err = ((outs[0].float() - want).abs() / (want.abs() + 0.05 * want.abs().max())).max().item()
     assert err <= tol * 4, err          # element-wise statistic: ~4 x the norm-wise one
     assert (torch.linalg.norm(outs[0].float() - want) / torch.linalg.norm(want)).item() <= tol
