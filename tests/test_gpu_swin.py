@@ -7,7 +7,11 @@ single operator).  float32 network features are exact-f32 paths: 1e-5.  The floa
 the restatement itself runs on the GPU in that dtype (how the reference runs 16-bit) and its norm-wise error e_ref against the
 float32 CPU restatement on the same tiles sets the bound, ours <= 1.5 x e_ref -- the margin covers two accumulation orders at
 equal precision; a softmax or LayerNorm statistic kept in 16 bits would cost multiples.  First MI355X run (33 tiles): float16 ours
-1.08e-03 against e_ref 1.44e-03, bfloat16 8.24e-03 against 1.12e-02, float32 2.9e-7."""
+1.08e-03 against e_ref 1.44e-03, bfloat16 8.24e-03 against 1.12e-02, float32 2.9e-7.
+
+The two operators element by element against float64 -- with runs of several windows per wave, which no shape here reaches,
+and the bits' independence of the run length -- are tests/test_gpu_swin_ops.py (restatements and the acceptance check:
+tests/swin_ops_reference.py, held to its rules on the CPU by tests/test_swin_ops_reference.py)."""
 import json
 
 import numpy as np
