@@ -157,6 +157,33 @@ int ap_tile_content_counts(const uint8_t* tiles, int n, int h, int w, int black_
                                    (unsigned*)counts, (hipStream_t)stream);
 }
 
+static inline bool known_dtype(int dt) { return dt == AP_F32 || dt == AP_F16 || dt == AP_BF16; }
+static inline bool half_dtype(int dt) { return dt == AP_F16 || dt == AP_BF16; }
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static inline bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+
+// The layout rule of ap_gemm / ap_gemm_fused (include/atlaspatch_hip.h states it): what the two MFMA kernels assume of a call
+// without checking it.  LDS-DMA stages 16 bytes per lane from A and W; a lane stores four consecutive columns (the 256 x 256
+// kernel: 16 bytes), reads bias / gamma / colsum as float4 and the row statistics of a row pair as 16 bytes, and writes the partial
+// sums as float2.
+static int gemm_contract(const char* fn, int dtype, int epilogue, const ap::GemmArgs& g, int impl) {
+    const size_t es = ap::dtype_size(dtype), oes = epilogue == ap::EPI_BIAS_RESID ? 4 : es;
+    const int kt = 128 / (int)es, ocols = epilogue == ap::EPI_NORM_SWIGLU ? g.N / 2 : g.N;
+    AP_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, "%s: empty problem %d x %d x %d", fn, g.M, g.N, g.K);
+    AP_REQUIRE(g.N % 128 == 0 && g.K % kt == 0, "%s: N = %d must be a multiple of 128 and K = %d of %d", fn, g.N, g.K, kt);
+    AP_REQUIRE(g.lda >= g.K && g.ldw >= g.K && g.ldo >= ocols, "%s: row strides (lda %d, ldw %d, ldo %d) smaller than the rows (K = %d, %d output columns)",
+               fn, g.lda, g.ldw, g.ldo, g.K, ocols);
+    AP_REQUIRE(((size_t)g.lda * es) % 16 == 0 && ((size_t)g.ldw * es) % 16 == 0 && aligned16(g.A) && aligned16(g.W),
+               "%s: A and W need 16-byte aligned pointers and row strides", fn);
+    AP_REQUIRE(g.ldo % 4 == 0 && ((uintptr_t)g.out % (4 * oes)) == 0, "%s: out needs ldo %% 4 == 0 and a pointer aligned to four elements (%zu bytes)",
+               fn, 4 * oes);
+    AP_REQUIRE(aligned16(g.bias) && aligned16(g.gamma) && aligned16(g.colsum) && aligned16(g.rowstats) && aligned8(g.partial),
+               "%s: bias / gamma / colsum / rowstats need 16-byte aligned pointers, partial an 8-byte aligned one", fn);
+    AP_REQUIRE((impl != 256 && impl != 257) || ap::gemm256_supports(dtype, epilogue, g),
+               "%s: impl %d (the 256 x 256 kernel) takes f16 / bf16, N %% 256 == 0, K %% 128 == 0, K >= 128, 16-byte aligned output rows", fn, impl);
+    return AP_OK;
+}
+
 int ap_gemm(int dtype, int epilogue, const void* A, int lda, const void* W, int ldw, int M, int N,
             int K, const float* bias, const float* gamma, void* out, int ldo, int impl, int variant,
             ap_stream_t stream) {
@@ -166,6 +193,8 @@ int ap_gemm(int dtype, int epilogue, const void* A, int lda, const void* W, int 
     AP_REQUIRE(ap::epi_known(epilogue) && !ap::epi_is_norm(epilogue) && !ap::epi_is_resid(epilogue) && epilogue != ap::EPI_PATCH_EMBED,
                "ap_gemm: unknown epilogue %d", epilogue);
     AP_REQUIRE(dtype == AP_F16 || dtype == AP_BF16 || dtype == AP_F32, "ap_gemm: unknown dtype %d", dtype);
+    AP_REQUIRE(impl == 0 || impl == 128 || impl == 129 || impl == 256 || impl == 257,
+               "ap_gemm: impl %d (0 = pick, 128, 129 = split-f16 products, 256; 257 = the A/B twin)", impl);
     ap::GemmArgs g{};
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.M = M; g.N = N; g.K = K;
     g.bias = bias; g.gamma = gamma; g.out = out; g.ldo = ldo;
@@ -173,6 +202,8 @@ int ap_gemm(int dtype, int epilogue, const void* A, int lda, const void* W, int 
         AP_REQUIRE(dtype == AP_F32, "ap_gemm: impl 129 (split-f16 products) takes float32 buffers");
         g.split = 1;
         impl = 128;
+    } else if (const int rc = gemm_contract("ap_gemm", dtype, epilogue, g, impl); rc != AP_OK) {
+        return rc;
     }
     return ap::launch_gemm_impl(dtype, epilogue, g, impl, variant, (hipStream_t)stream);
 }
@@ -241,7 +272,7 @@ int ap_gemm_fused(int dtype, int epilogue, const void* A, int lda, const void* W
     const int variant = (int)((unsigned)impl >> 12);      // bits 12..: kernel tuning variant (tools only), low 12 bits: implementation
     impl &= 0xfff;
     AP_REQUIRE(impl == 0 || impl == 128 || impl == 256 || impl == 257, "ap_gemm_fused: impl %d (0 = pick, 128, 256; 257 = the A/B twin)", impl);
-    AP_REQUIRE(M > 0 && (impl == 128 || ap::gemm256_supports(dtype, epilogue, g)), "ap_gemm_fused: unsupported problem (N %% 256, K %% 128, 16-byte strides)");
+    if (const int rc = gemm_contract("ap_gemm_fused", dtype, epilogue, g, impl); rc != AP_OK) return rc;
     return ap::launch_gemm_impl(dtype, epilogue, g, impl, variant, (hipStream_t)stream);
 }
 
@@ -275,10 +306,6 @@ int ap_attention(int dtype, const void* qkv, void* out, int n, int tokens, int h
 
 // ---- engine building blocks: the kernels vit.cpp chains, one export each.  Every wrapper checks what its launcher assumes
 // without checking (a refusal launches nothing) and forwards; the launchers' own checks follow.
-static inline bool known_dtype(int dt) { return dt == AP_F32 || dt == AP_F16 || dt == AP_BF16; }
-static inline bool half_dtype(int dt) { return dt == AP_F16 || dt == AP_BF16; }
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 int ap_attention_scaled(int dtype, const void* qkv, void* out, int n, int tokens, int heads, int head_dim, float scale,
                         ap_stream_t stream) {
     AP_REQUIRE(qkv && out, "ap_attention_scaled: null pointer");

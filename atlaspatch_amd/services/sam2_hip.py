@@ -184,7 +184,8 @@ class Sam2HipPredictor:
             return out
         if (self.wide_gemm and not self.split_gemm and plain and resid is None and bias is not None
                 and n % 128 == 0 and k % 32 == 0 and k <= 768 and -(-(m // stack) // 128) * (n // 128) >= 512
-                and (ldo is None or ldo == n) and a.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0):
+                and (ldo is None or ldo == n) and a.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
+                and w.data_ptr() % 16 == 0 and bias.data_ptr() % 16 == 0):
             _lib.check(self.lib.ap_gemm(_lib.AP_F32, act, a.data_ptr(), k, w.data_ptr(), k, m, n, k, bias.data_ptr(), None,
                                         out.data_ptr(), n, 128, 0, self._stream()), "ap_gemm")
             return out

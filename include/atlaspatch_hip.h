@@ -390,7 +390,20 @@ int ap_vit_forward_chw(ap_vit* m, const void* x, int x_dtype, int n,
  * A: T [M, lda], W: T [N, ldw] (both K-contiguous, the checkpoint's [out, in] layout), bias /
  * gamma: f32 [N].  N % 128 == 0 and K % (128 / sizeof(T)) == 0.  impl: 0 = pick, 128 = the
  * 128x128-tile kernel, 256 = the persistent 256x256-tile kernel (f16 / bf16, N % 256 == 0,
- * K % 128 == 0); variant selects a schedule variant of the 256 kernel (0 = default). */
+ * K % 128 == 0, K >= 128); variant selects a schedule variant of the 256 kernel (0 = default).
+ *
+ * Layout rule of ap_gemm and ap_gemm_fused (To = the output's element type: float for AP_EPI_BIAS_RESID, else T; the output has
+ * N columns, N / 2 under AP_EPI_NORM_SWIGLU).  The three strides are independent, in elements, and what lies between a row's
+ * end and the next row is neither read (A, W) nor written (out):
+ *   M, N, K > 0;  lda >= K, ldw >= K, ldo >= the output's columns;
+ *   A, W: 16-byte aligned pointers, lda * sizeof(T) and ldw * sizeof(T) multiples of 16 (LDS-DMA moves 16 bytes per lane);
+ *   out: ldo % 4 == 0 and the pointer aligned to 4 * sizeof(To) (a lane stores four consecutive columns); the 256 x 256
+ *        kernel stores 16 bytes per lane: impl 256 needs ldo * sizeof(To) % 16 == 0 and a 16-byte aligned pointer, and
+ *        impl 0 picks it only then;
+ *   bias, gamma, colsum, rowstats: 16-byte aligned;  partial: 8-byte aligned (rowstats [M, 2] and partial [M, N / 64, 2] are dense).
+ * Both entry points refuse anything else, and an impl that does not take the problem, with AP_ERR_INVALID and their name
+ * in ap_last_error(); nothing is launched.  Whichever kernel runs, the same call gives the same bits.  (impl 129, below, has
+ * its own rule: N % 32 == 0.) */
 #define AP_EPI_BIAS 0
 #define AP_EPI_BIAS_GELU 1
 #define AP_EPI_BIAS_RESID 2
@@ -445,6 +458,7 @@ int ap_gemm_split_f16_windows(const float* A, int lda, const void* w_split, int 
  *                       ap_rowstats_finalize turns them into the next rowstats (deterministic, fixed order, double).
  * impl: 0 = pick, 256 = the persistent 256 x 256 kernel (N % 256 == 0, K % 128 == 0; any M >= 1), 128 = the 128 x 128
  * kernel (N % 128 == 0, K % 64 == 0); the two give the same bits (the statistics are summed in one fixed order).  f16 / bf16.
+ * Strides and alignment: the layout rule stated at ap_gemm.
  * ap_stream_init: tok f32 [rows, dim] -> x T [rows, dim] + rowstats of the rounded rows (two-pass). */
 #define AP_EPI_NORM 4
 #define AP_EPI_NORM_GELU 5

@@ -1,6 +1,7 @@
 """Shared test helpers (inputs that reproduce the golden generator's seeds; the convolutional encoders' GPU tests)."""
 import functools
 import json
+import math
 import os
 
 import numpy as np
@@ -128,3 +129,49 @@ def _conv_bound_ratio(got, x, w, b, stride, pad, resid, act, dtype_name):
     K = w[0].numel()
     bound = (K + 4) * 2.0 ** -24 * mag + U_T[dtype_name] * ref.abs() * 1.001 + extra
     return float(((got.double() - ref).abs() / bound.clamp_min(1e-300)).max())
+
+
+# ----------------------------------------------------------------------------- guard bands (GPU operator tests)
+PATTERN = {2: 0x7FC1, 4: 0x7FC12345}            # a NaN in float16, bfloat16 and float32
+
+
+def _bits(t):
+    return t.contiguous().view({2: torch.int16, 4: torch.int32}[t.element_size()])
+
+
+def fill_pattern(t):
+    """Fills a contiguous float tensor with the NaN pattern of its element size, bit for bit; returns it."""
+    _bits(t).fill_(PATTERN[t.element_size()])
+    return t
+
+
+class Guarded:
+    """A device buffer of `shape` between two guard bands filled with a NaN pattern (at least one row and 64 elements each, a
+    multiple of 64 so that the payload keeps the allocation's alignment).  init: a CPU tensor copied in bit for bit; None: the
+    payload holds the pattern as well."""
+
+    def __init__(self, shape, dtype, dev, init=None):
+        numel = math.prod(shape)
+        row = shape[-1] if len(shape) else 1
+        self.guard = (max(64, row) + 63) // 64 * 64
+        self.numel, self.shape = numel, tuple(shape)
+        self.flat = fill_pattern(torch.empty(numel + 2 * self.guard, dtype=dtype, device=dev))
+        self.t = self.flat[self.guard:self.guard + numel].view(shape)
+        if init is not None:
+            assert init.dtype == dtype and tuple(init.shape) == self.shape
+            self.t.copy_(init)
+
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def cpu(self):
+        """The payload on the host, after checking both guard bands."""
+        host = self.flat.cpu()
+        flat = _bits(host)
+        want = PATTERN[self.flat.element_size()]
+        assert bool((flat[:self.guard] == want).all()), "the guard band in front of the buffer was written"
+        assert bool((flat[self.guard + self.numel:] == want).all()), "the guard band behind the buffer was written"
+        return host[self.guard:self.guard + self.numel].view(self.shape)
+
+    def untouched(self):
+        return bool((_bits(self.flat.cpu()) == PATTERN[self.flat.element_size()]).all())

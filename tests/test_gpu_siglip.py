@@ -12,10 +12,10 @@ import pytest
 import torch
 
 from tests import siglip_reference as S
+from tests.helpers import Guarded
 
 pytestmark = pytest.mark.gpu
 
-PATTERN = {2: 0x7FC1, 4: 0x7FC12345}            # a NaN in float16, bfloat16 and float32
 TOL = {torch.float32: 2e-5, torch.float16: 4e-3, torch.bfloat16: 3e-2}      # tests/test_encoder_zoo.py's device-vs-HF bounds
 
 # The real width (hidden 1152, 16 heads of 72, MLP 4304, 2 layers, n = 5) against the HF model in float32 on the CPU, norm-wise:
@@ -33,31 +33,6 @@ def env():
     from atlaspatch_amd import _lib
     dev = torch.device("cuda:0")
     return _lib, _lib.load(), dev, _lib.current_stream_ptr(dev)
-
-
-class Guarded:
-    """A device buffer of `shape` between two guard bands filled with a NaN pattern (tests/test_gpu_vit_ops.py's scheme)."""
-
-    def __init__(self, shape, dtype, dev):
-        numel = math.prod(shape)
-        self.guard = (max(64, shape[-1]) + 63) // 64 * 64
-        self.numel, self.shape = numel, tuple(shape)
-        self.flat = torch.empty(numel + 2 * self.guard, dtype=dtype, device=dev)
-        S.bits(self.flat).fill_(PATTERN[self.flat.element_size()])
-        self.t = self.flat[self.guard:self.guard + numel].view(shape)
-
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def cpu(self):
-        flat = S.bits(self.flat.cpu())
-        want = PATTERN[self.flat.element_size()]
-        assert bool((flat[:self.guard] == want).all()), "the guard band in front of the buffer was written"
-        assert bool((flat[self.guard + self.numel:] == want).all()), "the guard band behind the buffer was written"
-        return self.flat.cpu()[self.guard:self.guard + self.numel].view(self.shape)
-
-    def untouched(self):
-        return bool((S.bits(self.flat.cpu()) == PATTERN[self.flat.element_size()]).all())
 
 
 def _verify(op, case_results):

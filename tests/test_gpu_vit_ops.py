@@ -15,10 +15,9 @@ import pytest
 import torch
 
 from tests import vit_ops_reference as R
+from tests.helpers import PATTERN, Guarded
 
 pytestmark = pytest.mark.gpu
-
-PATTERN = {2: 0x7FC1, 4: 0x7FC12345}            # a NaN in float16, bfloat16 and float32
 
 
 @pytest.fixture(scope="module")
@@ -26,38 +25,6 @@ def env():
     from atlaspatch_amd import _lib
     dev = torch.device("cuda:0")
     return _lib, _lib.load(), dev, _lib.current_stream_ptr(dev)
-
-
-class Guarded:
-    """A device buffer of `shape` between two guard bands (at least one row and 64 elements each, a multiple of 64 so that the
-    payload keeps the allocation's alignment).  init: a CPU tensor copied in bit for bit; None: the payload holds the pattern."""
-
-    def __init__(self, shape, dtype, dev, init=None):
-        numel = math.prod(shape)
-        row = shape[-1] if len(shape) else 1
-        self.guard = (max(64, row) + 63) // 64 * 64
-        self.numel, self.shape = numel, tuple(shape)
-        self.flat = torch.empty(numel + 2 * self.guard, dtype=dtype, device=dev)
-        R.bits(self.flat).fill_(PATTERN[self.flat.element_size()])
-        self.t = self.flat[self.guard:self.guard + numel].view(shape)
-        if init is not None:
-            assert init.dtype == dtype and tuple(init.shape) == self.shape
-            self.t.copy_(init)
-
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def cpu(self):
-        """The payload on the host, after checking both guard bands."""
-        flat = R.bits(self.flat.cpu())
-        want = PATTERN[self.flat.element_size()]
-        assert bool((flat[:self.guard] == want).all()), "the guard band in front of the buffer was written"
-        assert bool((flat[self.guard + self.numel:] == want).all()), "the guard band behind the buffer was written"
-        return self.flat.cpu()[self.guard:self.guard + self.numel].view(self.shape)
-
-    def untouched(self):
-        flat = R.bits(self.flat.cpu())
-        return bool((flat == PATTERN[self.flat.element_size()]).all())
 
 
 def _dev(t, dev):
