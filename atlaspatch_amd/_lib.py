@@ -89,6 +89,18 @@ class SwinConfig(C.Structure):
 SWIN_PROF_KINDS = ("stem", "ln", "qkv", "window_attn", "proj", "fc1", "fc2", "merge", "pool")
 
 
+class ClipResnetConfig(C.Structure):
+    """``ap_clip_resnet_config`` (additive to ABI v20); ``struct_size`` is filled in here."""
+    _fields_ = [("struct_size", C.c_uint32), ("depths", C.c_int * 4), ("width", C.c_int), ("image_size", C.c_int),
+                ("output_dim", C.c_int), ("compute_dtype", C.c_int)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(C.sizeof(type(self)), *args, **kw)
+
+
+CLIP_RESNET_PROF_KINDS = ("stem", "conv1x1", "conv3x3", "avgpool", "head")
+
+
 # name -> (restype, argtypes); every symbol include/atlaspatch_hip.h declares
 SIGNATURES = {
     "ap_abi_version": (C.c_int, []),
@@ -178,6 +190,21 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p]),
     "ap_patch_merge_ln": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                     C.c_void_p, C.c_void_p]),
+    "ap_sizeof_clip_resnet_config": (C.c_size_t, []),
+    "ap_clip_resnet_config_init": (C.c_int, [C.POINTER(ClipResnetConfig), C.c_size_t]),
+    "ap_clip_resnet_create": (C.c_int, [C.POINTER(ClipResnetConfig), C.POINTER(C.c_void_p)]),
+    "ap_clip_resnet_destroy": (None, [C.c_void_p]),
+    "ap_clip_resnet_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]),
+    "ap_clip_resnet_finalize": (C.c_int, [C.c_void_p]),
+    "ap_clip_resnet_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "ap_clip_resnet_embed_dim": (C.c_int, [C.c_void_p]),
+    "ap_clip_resnet_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "ap_clip_resnet_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_int]),
+    "ap_clip_resnet_forward_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                            C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ap_avgpool2x2_nhwc": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ap_clip_attnpool_tokens": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "ap_gemm": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ap_gemm_fused": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -291,6 +291,10 @@ int launch_avgpool_nhwc(int dtype, const void* x, int n, int hw, int c, float* o
 // conv.hip (ConvNeXt): the implicit GEMM with Cout % 32 == 0 and act 0 none / 1 ReLU / 2 GELU (erf)
 int launch_conv2d_nhwc_ex(int dtype, const void* x, int n, int h, int w, int cin, const void* weight, const float* bias, int cout,
                           int ksize, int stride, int pad, const void* resid, int act, void* out, hipStream_t stream);
+// clip_resnet.hip (OpenAI CLIP ResNets): 2x2 stride-2 mean, and the attention-pool head's token matrix (mean token | map) + pos
+int launch_avgpool2x2_nhwc(int dtype, const void* x, int n, int h, int w, int c, void* out, hipStream_t stream);
+int launch_clip_attnpool_tokens(int dtype, const void* x, const float* pos, int n, int hw, int c, void* tokens_out, void* q_rows_out,
+                                hipStream_t stream);
 // convnext.hip: fused depthwise 7x7 + bias + LayerNorm, and LayerNorm over T rows
 int launch_dwconv7_ln_nhwc(int dtype, const void* x, int n, int h, int w, int c, const float* dw_weight, const float* dw_bias,
                            const float* ln_weight, const float* ln_bias, float eps, void* out, hipStream_t stream);

@@ -1,4 +1,4 @@
-// Host plumbing shared by the encoder objects behind the C ABI (vit.cpp, resnet.cpp, convnext.cpp, swin.cpp): per-kind launch timing,
+// Host plumbing shared by the encoder objects behind the C ABI (vit.cpp, resnet.cpp, convnext.cpp, swin.cpp, clip_resnet.cpp): per-kind launch timing,
 // the config size hand-over, the forward argument check, the centre-crop offset and the parameter store of the
 // convolutional and Swin engines.  Host C++ only; no kernel source includes it.
 #pragma once
@@ -135,7 +135,8 @@ enum ParamKind { P_CONV_W, P_DW_W, P_VEC };
 struct DevParam {
     ParamKind kind = P_VEC;
     int cout = 0, cin = 0, cin_stored = 0, ks = 0;   // P_CONV_W: torch [cout, cin, ks, ks]; P_DW_W: [cout, 1, 7, 7]; P_VEC: [cout]
-    void* d = nullptr;          // P_CONV_W: T [cout][ks][ks][cin_stored]; P_DW_W: f32 [49][cout]; P_VEC: f32 [cout]
+    int cout_stored = 0;        // rows of the device buffer: cout, or more (add_padded: zero weight rows, zero bias behind cout)
+    void* d = nullptr;          // P_CONV_W: T [cout_stored][ks][ks][cin_stored]; P_DW_W: f32 [49][cout]; P_VEC: f32 [cout_stored]
     bool set = false;
     size_t torch_count() const { return kind == P_VEC ? (size_t)cout : (size_t)cout * cin * ks * ks; }
 };
@@ -154,13 +155,25 @@ class ParamStore {
 
     // a zeroed device buffer for `name`; *out stays valid for the store's lifetime (std::map nodes are stable)
     int add(const std::string& name, ParamKind kind, int cout, int cin, int ks, DevParam** out) {
+        return add_padded(name, kind, cout, cin, ks, cout, kind == P_CONV_W ? (int)align_up(cin, 8) : cin, out);
+    }
+
+    // the same with the stored channel counts given (P_CONV_W: cout_stored >= cout rows of cin_stored >= cin channels, P_VEC:
+    // cout_stored >= cout values): what lies behind the checkpoint's channels stays zero, so a padded output channel is exactly
+    // bias 0 + 0 and a padded input channel contributes nothing.  The caller still uploads the checkpoint's own shape.
+    int add_padded(const std::string& name, ParamKind kind, int cout, int cin, int ks, int cout_stored, int cin_stored,
+                   DevParam** out) {
+        AP_REQUIRE(kind != P_DW_W || cout_stored == cout, "parameter %s: a depthwise weight cannot be padded", name.c_str());
+        AP_REQUIRE(cout_stored >= cout && cin_stored >= cin && (kind != P_CONV_W || cin_stored % 8 == 0),
+                   "parameter %s: stored shape %d x %d smaller than %d x %d", name.c_str(), cout_stored, cin_stored, cout, cin);
         DevParam p;
         p.kind = kind; p.cout = cout; p.cin = cin; p.ks = ks;
-        p.cin_stored = kind == P_CONV_W ? (int)align_up(cin, 8) : cin;
+        p.cout_stored = cout_stored;
+        p.cin_stored = cin_stored;
         size_t bytes;
-        if (kind == P_CONV_W) bytes = (size_t)cout * ks * ks * p.cin_stored * dtype_size(dtype);
+        if (kind == P_CONV_W) bytes = (size_t)cout_stored * ks * ks * p.cin_stored * dtype_size(dtype);
         else if (kind == P_DW_W) bytes = (size_t)49 * cout * sizeof(float);
-        else bytes = (size_t)cout * sizeof(float);
+        else bytes = (size_t)cout_stored * sizeof(float);
         AP_HIP_CHECK(hipMalloc(&p.d, bytes));
         DevParam& slot = params_[name] = p;
         AP_HIP_CHECK(hipMemset(slot.d, 0, bytes));
@@ -204,9 +217,10 @@ class ParamStore {
   private:
     std::map<std::string, DevParam> params_;
 
-    // torch [cout][cin][ky][kx] -> [cout][ky][kx][cin_stored] (zero channels past cin), then to T on the device
+    // torch [cout][cin][ky][kx] -> [cout_stored][ky][kx][cin_stored] (zero channels past cin, zero rows past cout), then to T
+    // on the device
     int upload_conv_weight(const char* who, const char* name, DevParam& p, const float* host) {
-        const size_t elems = (size_t)p.cout * p.ks * p.ks * p.cin_stored;
+        const size_t elems = (size_t)p.cout_stored * p.ks * p.ks * p.cin_stored;
         std::vector<float> perm(elems, 0.f);
         for (int o = 0; o < p.cout; ++o)
             for (int ci = 0; ci < p.cin; ++ci)

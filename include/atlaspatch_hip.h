@@ -767,6 +767,71 @@ int ap_swin_window_attention(int dtype, const void* qkv, int n, int h, int w, in
 int ap_patch_merge_ln(int dtype, const void* x, int n, int h, int w, int c, const float* ln_weight, const float* ln_bias, float eps,
                       void* out, ap_stream_t stream);
 
+/* ---- OpenAI CLIP ResNet image towers (additive to ABI v20) --------------------------------
+ * Replaces open_clip's encode_image for RN50 / RN101 / RN50x4 / RN50x16 / RN50x64 with the `openai` weights
+ * (models/patch/clip.py: clip_rn50, clip_rn101, clip_rn50x4, clip_rn50x16, clip_rn50x64) with the kernels of conv.hip,
+ * clip_resnet.hip and attn_pool.hip.  The network is CLIP's modified ResNet: a stem of three 3x3 convolutions (the first of
+ * stride 2) and a 2x2 average pool; bottleneck blocks (expansion 4) in which every convolution has stride 1 and a stride of 2
+ * is a 2x2 average pool behind the 3x3 convolution and in front of the shortcut's 1x1 projection; and an attention-pool
+ * head: the mean of the final map's g x g tokens (g = image_size / 32) is put in front of them, a positional embedding is added
+ * to all g g + 1, and the mean token alone queries them (C = 32 x width channels in heads of 64, scale 1 / 8) before the output
+ * projection.  Activations are NHWC in the compute type; BatchNorm is folded into the convolutions by the caller;
+ * accumulation, the pools' sums and the softmax are f32.  Maps whose channel count is not a multiple of 32 are stored padded
+ * with channels that are exactly zero.  Same structure rules as ap_resnet_config. */
+typedef struct ap_clip_resnet ap_clip_resnet;
+typedef struct ap_clip_resnet_config {
+    uint32_t struct_size; /* sizeof(ap_clip_resnet_config) as the caller sees it; written by ap_clip_resnet_config_init */
+    int depths[4];        /* blocks per stage: 3 4 6 3 / 3 4 23 3 / 4 6 10 6 / 6 8 18 8 / 3 15 36 10, each 1 .. 64 */
+    int width;            /* 64 / 64 / 80 / 96 / 128: the stem's output channels and the first stage's planes (a multiple of 16) */
+    int image_size;       /* 224 / 224 / 288 / 384 / 448: the centre crop the network sees (a multiple of 32 in 64 .. 1024) */
+    int output_dim;       /* 1024 / 512 / 640 / 768 / 1024: the embedding (a multiple of 32) */
+    int compute_dtype;    /* AP_F16 / AP_BF16 / AP_F32 (exact f32 MFMA products) */
+} ap_clip_resnet_config;
+#define AP_CLIP_RESNET_CONFIG_SIZE_V20 36u   /* the smallest size ap_clip_resnet_create accepts */
+size_t ap_sizeof_clip_resnet_config(void);
+int ap_clip_resnet_config_init(ap_clip_resnet_config* cfg, size_t sizeof_caller);
+/* AP_ERR_INVALID (before any device call) for an image size that is not a multiple of 32 or lies outside 64 .. 1024, a width
+ * that is not a multiple of 16, a depth outside 1 .. 64 or an output dimension that is not a multiple of 32. */
+int ap_clip_resnet_create(const ap_clip_resnet_config* cfg, ap_clip_resnet** out);
+void ap_clip_resnet_destroy(ap_clip_resnet* m);
+/* Upload one parameter (host float32, torch layout, `count` elements); synchronous.  Names (BatchNorm folded; W = width,
+ * P = W 2^(s-1) the planes of layer<s>, C = 32 W, g = image_size / 32):
+ *   conv1.weight [W/2, 3, 3, 3] | conv2.weight [W/2, W/2, 3, 3] | conv3.weight [W, W/2, 3, 3] | conv<k>.bias
+ *   layer<s>.<b>.conv1.weight [P, Cin, 1, 1] | .conv2.weight [P, P, 3, 3] | .conv3.weight [4P, P, 1, 1] | .conv<k>.bias
+ *   layer<s>.<b>.downsample.weight [4P, Cin, 1, 1] | .bias [4P]        (the first block of every stage)
+ *   attnpool.pos [g g + 1, C]                                           (any other row count is refused: no interpolation)
+ *   attnpool.q.weight [C, C] | .bias [C]
+ *   attnpool.kv.weight [2C, C] | .bias [2C]                             (k_proj's rows, then v_proj's)
+ *   attnpool.c.weight [output_dim, C] | .bias [output_dim]
+ * The library permutes the weights to [Cout][ky][kx][Cin] and pads both channel counts with zeros.  Setting a parameter
+ * un-finalises the object. */
+int ap_clip_resnet_set_param(ap_clip_resnet* m, const char* name, const float* host, size_t count);
+int ap_clip_resnet_finalize(ap_clip_resnet* m);          /* AP_ERR_STATE if a parameter was never set */
+size_t ap_clip_resnet_workspace_bytes(const ap_clip_resnet* m, int n);
+int ap_clip_resnet_embed_dim(const ap_clip_resnet* m);   /* output_dim */
+#define AP_CLIP_RESNET_PROF_STEM 0      /* NHWC preprocess + the three stem convolutions */
+#define AP_CLIP_RESNET_PROF_CONV1X1 1
+#define AP_CLIP_RESNET_PROF_CONV3X3 2
+#define AP_CLIP_RESNET_PROF_AVGPOOL 3   /* every 2x2 average pool: the stem's and the strided blocks' two each */
+#define AP_CLIP_RESNET_PROF_HEAD 4      /* tokens, k | v and q projections, attention, output projection, T -> f32 */
+#define AP_CLIP_RESNET_PROF_KINDS 5
+int ap_clip_resnet_profile_enable(ap_clip_resnet* m, int on);
+int ap_clip_resnet_profile_read(ap_clip_resnet* m, double* ms_by_kind, long long* launches_by_kind, int kinds);
+/* Same arguments and semantics as ap_resnet_forward_u8; out: device float32 [n, output_dim]. */
+int ap_clip_resnet_forward_u8(ap_clip_resnet* m, const uint8_t* patches, int n, int h, int w,
+                              const float mean[3], const float stdv[3],
+                              float* out, void* workspace, size_t workspace_bytes, ap_stream_t stream);
+
+/* Single operators of the CLIP ResNet forward (NHWC, T = dtype: f16 / bf16 / f32, device pointers 16-byte aligned):
+ * ap_avgpool2x2_nhwc: x T [n, h, w, c] (h, w even, c % 8 == 0) -> out T [n, h/2, w/2, c]: the mean of each 2x2 block, the four
+ *   taps summed in f32 as (x00 + x01) + (x10 + x11), one rounding; out must not alias x.
+ * ap_clip_attnpool_tokens: x T [n, hw, c] and pos f32 [hw + 1, c] -> tokens_out T [n, hw + 1, c]: row 0 = T(mean over the hw
+ *   rows of x (summed in f32) + pos[0]), row 1 + p = T(x[p] + pos[1 + p]); q_rows_out T [n, c] receives row 0 again, packed.
+ *   One pass over x; c % 8 == 0, c <= 65536, hw <= 4096, n <= 65535; no atomics: an image's rows do not depend on n. */
+int ap_avgpool2x2_nhwc(int dtype, const void* x, int n, int h, int w, int c, void* out, ap_stream_t stream);
+int ap_clip_attnpool_tokens(int dtype, const void* x, const float* pos, int n, int hw, int c, void* tokens_out, void* q_rows_out,
+                            ap_stream_t stream);
+
 /* ---- float32 operator set of the SAM2 (Hiera-T) tissue segmenter ------------------------
  * Replaces the torch modules behind SAM2ImagePredictor.set_image / predict as the reference drives them
  * (services/segmentation.py:120-140: one 1024 x 1024 thumbnail per slide, box prompt = whole image,
