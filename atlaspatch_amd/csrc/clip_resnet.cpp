@@ -1,7 +1,8 @@
 // OpenAI CLIP "modified ResNet" image tower behind the C ABI (ap_clip_resnet_*): RN50 / RN101 / RN50x4 / RN50x16 / RN50x64.
 // Parameter storage in HBM, workspace carving and the launch sequence of one forward pass.  Host C++ only; the kernels live in
 // conv.hip (preprocess, implicit-GEMM convolution), clip_resnet.hip (2x2 average pool, token matrix of the head),
-// attn_pool.hip (one-query attention) and elementwise.hip (T -> f32).
+// attn_pool.hip (one-query attention) and elementwise.hip (T -> f32).  The block records, the stage walk, the convolution launch
+// and the four-buffer workspace are resnet_host.h's, shared with resnet.cpp.
 //
 // Forward for n images (T = compute dtype, NHWC everywhere, W = width, g = S / 32, C = 32 W):
 //   preprocess  u8 tiles -> centre crop -> normalised T [n, S, S, 8] (channels 3..7 zero)
@@ -21,32 +22,17 @@
 //   stride 2:  conv1 x -> f0;  conv2 f0 -> f1;  pool x -> f0;  downsample f0 -> f2;  pool f1 -> f0;  conv3 f0 + f2 -> f1;  next x = f1
 //   stem:      preprocess -> b0;  conv1 b0 -> b1;  conv2 b1 -> b2;  conv3 b2 -> b1;  pool b1 -> b2;               x = b2
 //   head:      tokens x -> f0, q rows -> f1;  k | v f0 -> f2;  q f1 -> x;  attention (x, f2) -> f0;  c_proj f0 -> f1;  f1 -> out
-#include <algorithm>
-#include <string>
-#include <vector>
-#include "engine_host.h"
+#include "resnet_host.h"
 
-namespace {
-
+using ap::Block;
+using ap::ConvOp;
 using ap::DevParam;
 using ap::ScopedTimer;
+using ap::padded32;
 
+namespace {
 constexpr int HEAD_DIM = 64;
-
-struct ConvOp {                 // one convolution of the forward, resolved at create; padding ks / 2
-    DevParam* w = nullptr;      // "<conv>.weight": T [cout_stored][ks][ks][cin_stored]
-    DevParam* b = nullptr;      // "<conv>.bias": f32 [cout_stored]
-};
-
-struct Block {
-    ConvOp c1, c2, c3;
-    ConvOp down;                // down.w == nullptr: identity shortcut
-    int stride = 1;
-};
-
-inline int padded(int c) { return (int)ap::align_up((size_t)c, 32); }
-
-}  // namespace
+}
 
 struct ap_clip_resnet {
     ap_clip_resnet_config cfg;
@@ -63,25 +49,9 @@ struct ap_clip_resnet {
 
 namespace {
 
-// cin_stored: the channel count of the map the convolution reads (its producer's padded Cout)
-int add_conv(ap_clip_resnet* m, const std::string& name, int cout, int cin, int ks, int cin_stored, ConvOp* op) {
-    const int rc = m->params.add_padded(name + ".weight", ap::P_CONV_W, cout, cin, ks, padded(cout), cin_stored, &op->w);
-    return rc != AP_OK ? rc : m->params.add_padded(name + ".bias", ap::P_VEC, cout, 0, 0, padded(cout), 0, &op->b);
-}
-
-size_t align256(size_t v) { return ap::align_up(v, 256); }
-
-// x T [n, h, w, cin_stored] -> out T [n, ho, wo, cout_stored] = act(conv + bias (+ resid)); every convolution but the stem's
-// first has stride 1
-int run_conv(ap_clip_resnet* m, int kind, const ConvOp& op, const void* x, int n, int h, int w, const void* resid, int relu,
-             void* out, hipStream_t s, int stride = 1) {
-    const DevParam& p = *op.w;
-    ScopedTimer t(m->prof, kind, s);
-    if (p.cout_stored % 64 == 0)
-        return ap::launch_conv2d_nhwc(m->cfg.compute_dtype, x, n, h, w, p.cin_stored, p.d, (const float*)op.b->d, p.cout_stored, p.ks,
-                                      stride, p.ks / 2, resid, relu, out, s);
-    return ap::launch_conv2d_nhwc_ex(m->cfg.compute_dtype, x, n, h, w, p.cin_stored, p.d, (const float*)op.b->d, p.cout_stored, p.ks,
-                                     stride, p.ks / 2, resid, relu, out, s);
+int run_conv(ap_clip_resnet* m, int kind, const ConvOp& op, const void* x, int n, int hw, const void* resid, int relu, void* out,
+             hipStream_t s) {
+    return ap::run_conv(m->prof, kind, m->cfg.compute_dtype, op, x, n, hw, hw, resid, relu, out, s);
 }
 
 int run_pool(ap_clip_resnet* m, const void* x, int n, int hw, int c, void* out, hipStream_t s) {
@@ -116,47 +86,31 @@ int ap_clip_resnet_create(const ap_clip_resnet_config* cfg, ap_clip_resnet** out
                "clip_resnet_create: image_size %d (a multiple of 32 in 64 .. 1024: the network reduces it 32-fold)", c.image_size);
     AP_REQUIRE(c.output_dim >= 32 && c.output_dim % 32 == 0 && c.output_dim <= 8192,
                "clip_resnet_create: output_dim %d (a multiple of 32)", c.output_dim);
-    AP_REQUIRE(c.compute_dtype == AP_F16 || c.compute_dtype == AP_BF16 || c.compute_dtype == AP_F32,
-               "clip_resnet_create: compute dtype %d", c.compute_dtype);
+    if ((rc = ap::check_compute_dtype("clip_resnet", c.compute_dtype)) != AP_OK) return rc;
     ap_clip_resnet* m = new ap_clip_resnet();
     m->cfg = c;
     m->params.dtype = c.compute_dtype;
+    // cin_stored: the channel count of the map the convolution reads (its producer's stored Cout; the image: 8)
     auto add = [&](const std::string& name, int cout, int cin, int ks, int cin_stored, ConvOp* op) {
-        if (rc == AP_OK) rc = add_conv(m, name, cout, cin, ks, cin_stored, op);
+        if (rc == AP_OK) rc = ap::add_conv(m->params, name, cout, cin, ks, padded32(cout), cin_stored, op);
     };
     const int W = c.width, S = c.image_size;
+    m->stem[0].stride = 2;
     add("conv1", W / 2, 3, 3, 8, &m->stem[0]);
-    add("conv2", W / 2, W / 2, 3, padded(W / 2), &m->stem[1]);
-    add("conv3", W, W / 2, 3, padded(W / 2), &m->stem[2]);
-    int hw = S / 2;
-    size_t max_act = std::max((size_t)S * S * 8, (size_t)hw * hw * padded(W));
-    hw /= 2;
-    int inplanes = W;
-    for (int s = 0; s < 4; ++s) {
-        const int planes = W << s, outc = planes * 4;
-        for (int b = 0; b < c.depths[s]; ++b) {
-            const std::string pre = "layer" + std::to_string(s + 1) + "." + std::to_string(b) + ".";
-            Block blk{};
-            blk.stride = (s > 0 && b == 0) ? 2 : 1;
-            add(pre + "conv1", planes, inplanes, 1, padded(inplanes), &blk.c1);
-            add(pre + "conv2", planes, planes, 3, padded(planes), &blk.c2);
-            add(pre + "conv3", outc, planes, 1, padded(planes), &blk.c3);
-            if (blk.stride != 1 || inplanes != outc) add(pre + "downsample", outc, inplanes, 1, padded(inplanes), &blk.down);
-            max_act = std::max(max_act, (size_t)hw * hw * (size_t)std::max(padded(planes), padded(inplanes)));
-            hw /= blk.stride;
-            max_act = std::max(max_act, (size_t)hw * hw * (size_t)outc);
-            inplanes = outc;
-            m->blocks.push_back(blk);
-        }
-    }
-    m->C = inplanes;
-    m->grid = hw;
-    const int C = m->C, tokens = hw * hw + 1;
+    add("conv2", W / 2, W / 2, 3, padded32(W / 2), &m->stem[1]);
+    add("conv3", W, W / 2, 3, padded32(W / 2), &m->stem[2]);
+    ap::Stages st;
+    if (rc == AP_OK) rc = ap::add_stages(m->params, {true, W, c.depths, true, false}, W, S / 4, &st);
+    m->blocks = std::move(st.blocks);
+    m->C = st.channels;
+    m->grid = st.hw;
+    const int C = m->C, tokens = m->grid * m->grid + 1;
     if (rc == AP_OK) rc = m->params.add("attnpool.pos", ap::P_VEC, tokens * C, 0, 0, &m->pos);
     add("attnpool.q", C, C, 1, C, &m->q);
     add("attnpool.kv", 2 * C, C, 1, C, &m->kv);
     add("attnpool.c", c.output_dim, C, 1, C, &m->cproj);
-    m->max_act = std::max(max_act, (size_t)tokens * 2 * C);
+    // the preprocessed image, the stem's third convolution, the stages and the head's k | v matrix
+    m->max_act = std::max({(size_t)S * S * 8, (size_t)(S / 2) * (S / 2) * padded32(W), st.max_act, (size_t)tokens * 2 * C});
     if (rc != AP_OK) { delete m; return rc; }
     *out = m;
     return AP_OK;
@@ -165,28 +119,19 @@ int ap_clip_resnet_create(const ap_clip_resnet_config* cfg, ap_clip_resnet** out
 void ap_clip_resnet_destroy(ap_clip_resnet* m) { delete m; }
 
 int ap_clip_resnet_set_param(ap_clip_resnet* m, const char* name, const float* host, size_t count) {
-    AP_REQUIRE(m && name && host, "clip_resnet_set_param: null argument");
-    if (std::string(name) == "attnpool.pos") {
+    if (m && name && std::string(name) == "attnpool.pos") {
         const size_t rows = (size_t)m->grid * m->grid + 1;
         AP_REQUIRE(count == rows * m->C,
                    "clip_resnet_set_param: attnpool.pos has %zu values, expected %zu rows of %d (image_size %d: a %d x %d map and the "
                    "mean token; the positional embedding is not interpolated)", count, rows, m->C, m->cfg.image_size, m->grid, m->grid);
     }
-    const int rc = m->params.set("clip_resnet", name, host, count);
-    if (rc == AP_OK) m->finalized = false;
-    return rc;
+    return ap::set_param(m, "clip_resnet", name, host, count);
 }
 
-int ap_clip_resnet_finalize(ap_clip_resnet* m) {
-    AP_REQUIRE(m, "clip_resnet_finalize: null handle");
-    const int rc = m->params.check_all_set("clip_resnet");
-    if (rc == AP_OK) m->finalized = true;
-    return rc;
-}
+int ap_clip_resnet_finalize(ap_clip_resnet* m) { return ap::finalize(m, "clip_resnet"); }
 
 size_t ap_clip_resnet_workspace_bytes(const ap_clip_resnet* m, int n) {
-    if (!m || n <= 0) return 0;
-    return 4 * align256(m->max_act * (size_t)n * ap::dtype_size(m->cfg.compute_dtype));
+    return m && n > 0 ? ap::Workspace4::bytes(m->max_act, n, m->cfg.compute_dtype) : 0;
 }
 
 int ap_clip_resnet_embed_dim(const ap_clip_resnet* m) { return m ? m->cfg.output_dim : 0; }
@@ -206,52 +151,50 @@ int ap_clip_resnet_forward_u8(ap_clip_resnet* m, const uint8_t* patches, int n, 
     AP_REQUIRE(h >= S && w >= S, "clip_resnet_forward_u8: %dx%d tiles smaller than the %d model input", h, w, S);
     hipStream_t s = (hipStream_t)stream;
     const int dt = m->cfg.compute_dtype;
-    const size_t slot = align256(m->max_act * (size_t)n * ap::dtype_size(dt));
-    char* buf[4];
-    for (int i = 0; i < 4; ++i) buf[i] = (char*)workspace + i * slot;
+    ap::Workspace4 ws(workspace, m->max_act, n, dt);
+    char* const* buf = ws.buf;
+    const int* f = ws.f;
 
     { ScopedTimer t(m->prof, AP_CLIP_RESNET_PROF_STEM, s);
       rc = ap::launch_preproc_nhwc8(patches, n, h, w, ap::center_crop_offset(h, S), ap::center_crop_offset(w, S), S, mean, stdv,
                                     buf[0], dt, s); }
     if (rc != AP_OK) return rc;
     int hw = S / 2;
-    if ((rc = run_conv(m, AP_CLIP_RESNET_PROF_STEM, m->stem[0], buf[0], n, S, S, nullptr, 1, buf[1], s, 2)) != AP_OK) return rc;
-    if ((rc = run_conv(m, AP_CLIP_RESNET_PROF_STEM, m->stem[1], buf[1], n, hw, hw, nullptr, 1, buf[2], s)) != AP_OK) return rc;
-    if ((rc = run_conv(m, AP_CLIP_RESNET_PROF_STEM, m->stem[2], buf[2], n, hw, hw, nullptr, 1, buf[1], s)) != AP_OK) return rc;
+    if ((rc = run_conv(m, AP_CLIP_RESNET_PROF_STEM, m->stem[0], buf[0], n, S, nullptr, 1, buf[1], s)) != AP_OK) return rc;
+    if ((rc = run_conv(m, AP_CLIP_RESNET_PROF_STEM, m->stem[1], buf[1], n, hw, nullptr, 1, buf[2], s)) != AP_OK) return rc;
+    if ((rc = run_conv(m, AP_CLIP_RESNET_PROF_STEM, m->stem[2], buf[2], n, hw, nullptr, 1, buf[1], s)) != AP_OK) return rc;
     if ((rc = run_pool(m, buf[1], n, hw, m->stem[2].w->cout_stored, buf[2], s)) != AP_OK) return rc;
     hw /= 2;
     int xi = 2;                                     // buffer holding the current activation
     for (const Block& b : m->blocks) {
-        int f[3], k = 0;
-        for (int i = 0; i < 4; ++i) if (i != xi) f[k++] = i;
+        ws.others(xi);
         const void* x = buf[xi];
         const int cin = b.c1.w->cin_stored, planes = b.c2.w->cout_stored;
-        if ((rc = run_conv(m, conv_kind(b.c1), b.c1, x, n, hw, hw, nullptr, 1, buf[f[0]], s)) != AP_OK) return rc;
-        if ((rc = run_conv(m, conv_kind(b.c2), b.c2, buf[f[0]], n, hw, hw, nullptr, 1, buf[f[1]], s)) != AP_OK) return rc;
+        if ((rc = run_conv(m, conv_kind(b.c1), b.c1, x, n, hw, nullptr, 1, buf[f[0]], s)) != AP_OK) return rc;
+        if ((rc = run_conv(m, conv_kind(b.c2), b.c2, buf[f[0]], n, hw, nullptr, 1, buf[f[1]], s)) != AP_OK) return rc;
         int oi;
         if (b.stride == 2) {
             const int ho = hw / 2;
             if ((rc = run_pool(m, x, n, hw, cin, buf[f[0]], s)) != AP_OK) return rc;
-            if ((rc = run_conv(m, conv_kind(b.down), b.down, buf[f[0]], n, ho, ho, nullptr, 0, buf[f[2]], s)) != AP_OK) return rc;
+            if ((rc = run_conv(m, conv_kind(b.down), b.down, buf[f[0]], n, ho, nullptr, 0, buf[f[2]], s)) != AP_OK) return rc;
             if ((rc = run_pool(m, buf[f[1]], n, hw, planes, buf[f[0]], s)) != AP_OK) return rc;
             oi = f[1];
-            if ((rc = run_conv(m, conv_kind(b.c3), b.c3, buf[f[0]], n, ho, ho, buf[f[2]], 1, buf[oi], s)) != AP_OK) return rc;
+            if ((rc = run_conv(m, conv_kind(b.c3), b.c3, buf[f[0]], n, ho, buf[f[2]], 1, buf[oi], s)) != AP_OK) return rc;
             hw = ho;
         } else {
             const void* sc = x;
             if (b.down.w) {
-                if ((rc = run_conv(m, conv_kind(b.down), b.down, x, n, hw, hw, nullptr, 0, buf[f[2]], s)) != AP_OK) return rc;
+                if ((rc = run_conv(m, conv_kind(b.down), b.down, x, n, hw, nullptr, 0, buf[f[2]], s)) != AP_OK) return rc;
                 sc = buf[f[2]];
             }
             oi = f[0];
-            if ((rc = run_conv(m, conv_kind(b.c3), b.c3, buf[f[1]], n, hw, hw, sc, 1, buf[oi], s)) != AP_OK) return rc;
+            if ((rc = run_conv(m, conv_kind(b.c3), b.c3, buf[f[1]], n, hw, sc, 1, buf[oi], s)) != AP_OK) return rc;
         }
         xi = oi;
     }
 
     // ---- attention-pool head
-    int f[3], k = 0;
-    for (int i = 0; i < 4; ++i) if (i != xi) f[k++] = i;
+    ws.others(xi);
     const int C = m->C, tokens = hw * hw + 1, D = m->cfg.output_dim;
     ScopedTimer t(m->prof, AP_CLIP_RESNET_PROF_HEAD, s);
     rc = ap::launch_clip_attnpool_tokens(dt, buf[xi], (const float*)m->pos->d, n, hw * hw, C, buf[f[0]], buf[f[1]], s);

@@ -21,17 +21,12 @@ namespace {
 
 constexpr float LN_EPS = 1e-6f;
 
+using ap::Conv;
 using ap::DevParam;
 using ap::ParamKind;
-using ap::P_CONV_W;
 using ap::P_DW_W;
 using ap::P_VEC;
 using ap::ScopedTimer;
-
-struct Conv {                   // a convolution / linear layer: weight and bias
-    DevParam* w = nullptr;
-    DevParam* b = nullptr;
-};
 
 struct Block {
     DevParam *dw_w, *dw_b, *ln_w, *ln_b;
@@ -92,8 +87,7 @@ int ap_convnext_create(const ap_convnext_config* cfg, ap_convnext** out) {
         AP_REQUIRE(c.widths[s] >= 32 && c.widths[s] % 32 == 0 && c.widths[s] <= 4096,
                    "convnext_create: widths[%d] = %d (a multiple of 32)", s, c.widths[s]);
     }
-    AP_REQUIRE(c.compute_dtype == AP_F16 || c.compute_dtype == AP_BF16 || c.compute_dtype == AP_F32,
-               "convnext_create: compute dtype %d", c.compute_dtype);
+    if ((rc = ap::check_compute_dtype("convnext", c.compute_dtype)) != AP_OK) return rc;
     AP_REQUIRE(c.image_size >= 32 && c.image_size <= 1024 && c.image_size % 32 == 0,
                "convnext_create: image_size %d (a multiple of 32)", c.image_size);
     ap_convnext* m = new ap_convnext();
@@ -102,9 +96,11 @@ int ap_convnext_create(const ap_convnext_config* cfg, ap_convnext** out) {
     auto add = [&](const std::string& name, ParamKind kind, int cout, int cin, int ks, DevParam** p) {
         if (rc == AP_OK) rc = m->params.add(name, kind, cout, cin, ks, p);
     };
+    auto add_conv = [&](const std::string& name, int cout, int cin, int ks, Conv* l) {
+        if (rc == AP_OK) rc = ap::add_conv(m->params, name, cout, cin, ks, l);
+    };
     const int S = c.image_size;
-    add("features.0.0.weight", P_CONV_W, c.widths[0], 3, 4, &m->stem.w);
-    add("features.0.0.bias", P_VEC, c.widths[0], 0, 0, &m->stem.b);
+    add_conv("features.0.0", c.widths[0], 3, 4, &m->stem);
     add("features.0.1.weight", P_VEC, c.widths[0], 0, 0, &m->stem_ln_w);
     add("features.0.1.bias", P_VEC, c.widths[0], 0, 0, &m->stem_ln_b);
     size_t small = 0, big = (size_t)S * S * 8;
@@ -117,8 +113,7 @@ int ap_convnext_create(const ap_convnext_config* cfg, ap_convnext** out) {
             const std::string d = "features." + std::to_string(2 * s) + ".";
             add(d + "0.weight", P_VEC, c.widths[s - 1], 0, 0, &st.ds_ln_w);
             add(d + "0.bias", P_VEC, c.widths[s - 1], 0, 0, &st.ds_ln_b);
-            add(d + "1.weight", P_CONV_W, C, c.widths[s - 1], 2, &st.ds.w);
-            add(d + "1.bias", P_VEC, C, 0, 0, &st.ds.b);
+            add_conv(d + "1", C, c.widths[s - 1], 2, &st.ds);
             hw /= 2;
         }
         small = std::max(small, (size_t)hw * hw * C);
@@ -131,10 +126,8 @@ int ap_convnext_create(const ap_convnext_config* cfg, ap_convnext** out) {
             add(pre + "0.bias", P_VEC, C, 0, 0, &b.dw_b);
             add(pre + "2.weight", P_VEC, C, 0, 0, &b.ln_w);
             add(pre + "2.bias", P_VEC, C, 0, 0, &b.ln_b);
-            add(pre + "3.weight", P_CONV_W, 4 * C, C, 1, &b.fc1.w);
-            add(pre + "3.bias", P_VEC, 4 * C, 0, 0, &b.fc1.b);
-            add(pre + "5.weight", P_CONV_W, C, 4 * C, 1, &b.fc2.w);
-            add(pre + "5.bias", P_VEC, C, 0, 0, &b.fc2.b);
+            add_conv(pre + "3", 4 * C, C, 1, &b.fc1);
+            add_conv(pre + "5", C, 4 * C, 1, &b.fc2);
         }
     }
     m->small_elems = small;
@@ -147,18 +140,10 @@ int ap_convnext_create(const ap_convnext_config* cfg, ap_convnext** out) {
 void ap_convnext_destroy(ap_convnext* m) { delete m; }
 
 int ap_convnext_set_param(ap_convnext* m, const char* name, const float* host, size_t count) {
-    AP_REQUIRE(m && name && host, "convnext_set_param: null argument");
-    const int rc = m->params.set("convnext", name, host, count);
-    if (rc == AP_OK) m->finalized = false;
-    return rc;
+    return ap::set_param(m, "convnext", name, host, count);
 }
 
-int ap_convnext_finalize(ap_convnext* m) {
-    AP_REQUIRE(m, "convnext_finalize: null handle");
-    const int rc = m->params.check_all_set("convnext");
-    if (rc == AP_OK) m->finalized = true;
-    return rc;
-}
+int ap_convnext_finalize(ap_convnext* m) { return ap::finalize(m, "convnext"); }
 
 size_t ap_convnext_workspace_bytes(const ap_convnext* m, int n) {
     if (!m || n <= 0) return 0;

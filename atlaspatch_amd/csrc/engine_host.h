@@ -1,6 +1,7 @@
-// Host plumbing shared by the encoder objects behind the C ABI (vit.cpp, resnet.cpp, convnext.cpp, swin.cpp, clip_resnet.cpp): per-kind launch timing,
-// the config size hand-over, the forward argument check, the centre-crop offset and the parameter store of the
-// convolutional and Swin engines.  Host C++ only; no kernel source includes it.
+// Host plumbing shared by the encoder objects behind the C ABI (vit.cpp, resnet.cpp, convnext.cpp, swin.cpp, clip_resnet.cpp):
+// per-kind launch timing, the config size hand-over, the forward argument check, the centre-crop offset and, for the
+// convolutional and Swin engines, the parameter store (padded parameters included), the {weight, bias} record of a convolution
+// and the bodies of ap_<who>_set_param / ap_<who>_finalize.  Host C++ only; no kernel source includes it.
 #pragma once
 #include <cstring>
 #include <map>
@@ -244,5 +245,44 @@ class ParamStore {
         return rc;
     }
 };
+
+// ---- a convolution / linear layer of an engine, resolved at create: "<name>.weight" and "<name>.bias" (null: bias-free)
+struct Conv {
+    DevParam* w = nullptr;      // T [cout_stored][ks][ks][cin_stored]
+    DevParam* b = nullptr;      // f32 [cout_stored]
+};
+
+inline int add_conv(ParamStore& store, const std::string& name, int cout, int cin, int ks, int cout_stored, int cin_stored,
+                    Conv* out) {
+    const int rc = store.add_padded(name + ".weight", P_CONV_W, cout, cin, ks, cout_stored, cin_stored, &out->w);
+    return rc != AP_OK ? rc : store.add_padded(name + ".bias", P_VEC, cout, 0, 0, cout_stored, 0, &out->b);
+}
+
+inline int add_conv(ParamStore& store, const std::string& name, int cout, int cin, int ks, Conv* out) {   // unpadded
+    return add_conv(store, name, cout, cin, ks, cout, (int)align_up(cin, 8), out);
+}
+
+// ---- the bodies of ap_<who>_set_param / ap_<who>_finalize and the dtype check of ap_<who>_create, for an engine that keeps
+// its parameters in `params` (a ParamStore) and a `finalized` flag
+template <class Engine>
+int set_param(Engine* m, const char* who, const char* name, const float* host, size_t count) {
+    AP_REQUIRE(m && name && host, "%s_set_param: null argument", who);
+    const int rc = m->params.set(who, name, host, count);
+    if (rc == AP_OK) m->finalized = false;
+    return rc;
+}
+
+template <class Engine>
+int finalize(Engine* m, const char* who) {
+    AP_REQUIRE(m, "%s_finalize: null handle", who);
+    const int rc = m->params.check_all_set(who);
+    if (rc == AP_OK) m->finalized = true;
+    return rc;
+}
+
+inline int check_compute_dtype(const char* who, int dtype) {
+    AP_REQUIRE(dtype == AP_F16 || dtype == AP_BF16 || dtype == AP_F32, "%s_create: compute dtype %d", who, dtype);
+    return AP_OK;
+}
 
 }  // namespace ap

@@ -1,5 +1,6 @@
 // ResNet encoder object behind the C ABI (ap_resnet_*): parameter storage in HBM, workspace carving and the launch sequence
-// of one forward pass.  Host C++ only; every kernel it launches lives in conv.hip.
+// of one forward pass.  Host C++ only; every kernel it launches lives in conv.hip, and the block records, the stage walk, the
+// convolution launch and the four-buffer workspace are resnet_host.h's, shared with clip_resnet.cpp.
 //
 // Forward for n images (T = compute dtype, NHWC everywhere):
 //   preprocess  u8 tiles -> centre crop -> normalised T [n, S, S, 8] (channels 3..7 zero)
@@ -9,28 +10,11 @@
 //   head        global average pool -> f32 [n, C]
 // Workspace: four buffers of the largest activation each (the stem input included), rotated so that a block never writes a
 // buffer it still reads: x (input) -> t1 -> t2 (-> projection) -> out, out becomes the next block's x.
-#include <algorithm>
-#include <string>
-#include <vector>
-#include "engine_host.h"
+#include "resnet_host.h"
 
-namespace {
-
-using ap::DevParam;
+using ap::Block;
+using ap::ConvOp;
 using ap::ScopedTimer;
-
-struct ConvOp {                 // one convolution of the forward, resolved at create
-    DevParam* w = nullptr;      // "<conv>.weight": T [cout][ks][ks][cin_stored]
-    DevParam* b = nullptr;      // "<conv>.bias": f32 [cout]
-    int stride = 1, pad = 0;
-};
-
-struct Block {
-    ConvOp c1, c2, c3;          // c3 unused for basic blocks
-    ConvOp down;                // down.w == nullptr: identity shortcut
-};
-
-}  // namespace
 
 struct ap_resnet {
     ap_resnet_config cfg;
@@ -45,25 +29,11 @@ struct ap_resnet {
 
 namespace {
 
-int add_conv(ap_resnet* m, const std::string& name, int cout, int cin, int ks, int stride, ConvOp* op) {
-    op->stride = stride;
-    op->pad = ks / 2;
-    const int rc = m->params.add(name + ".weight", ap::P_CONV_W, cout, cin, ks, &op->w);
-    return rc != AP_OK ? rc : m->params.add(name + ".bias", ap::P_VEC, cout, 0, 0, &op->b);
+int run_conv(ap_resnet* m, const ConvOp& op, const void* x, int n, int hw, const void* resid, int relu, void* out, hipStream_t s) {
+    const int ks = op.w->ks;
+    const int kind = ks == 7 ? AP_RESNET_PROF_STEM : (ks == 1 ? AP_RESNET_PROF_CONV1X1 : AP_RESNET_PROF_CONV3X3);
+    return ap::run_conv(m->prof, kind, m->cfg.compute_dtype, op, x, n, hw, hw, resid, relu, out, s);
 }
-
-size_t align256(size_t v) { return ap::align_up(v, 256); }
-
-int run_conv(ap_resnet* m, const ConvOp& op, const void* x, int n, int h, int w, const void* resid, int relu, void* out,
-             hipStream_t s) {
-    const DevParam& p = *op.w;
-    const int kind = p.ks == 7 ? AP_RESNET_PROF_STEM : (p.ks == 1 ? AP_RESNET_PROF_CONV1X1 : AP_RESNET_PROF_CONV3X3);
-    ScopedTimer t(m->prof, kind, s);
-    return ap::launch_conv2d_nhwc(m->cfg.compute_dtype, x, n, h, w, p.cin_stored, p.d, (const float*)op.b->d, p.cout, p.ks,
-                                  op.stride, op.pad, resid, relu, out, s);
-}
-
-inline int conv_out(int h, const ConvOp& op) { return (h + 2 * op.pad - op.w->ks) / op.stride + 1; }
 
 }  // namespace
 
@@ -85,47 +55,21 @@ int ap_resnet_create(const ap_resnet_config* cfg, ap_resnet** out) {
     for (int s = 0; s < 4; ++s) AP_REQUIRE(c.depths[s] >= 1 && c.depths[s] <= 64, "resnet_create: depths[%d] = %d", s, c.depths[s]);
     AP_REQUIRE(c.stem_width >= 64 && c.stem_width % 64 == 0 && c.stem_width <= 256, "resnet_create: stem_width %d (a multiple of 64)",
                c.stem_width);
-    AP_REQUIRE(c.compute_dtype == AP_F16 || c.compute_dtype == AP_BF16 || c.compute_dtype == AP_F32,
-               "resnet_create: compute dtype %d", c.compute_dtype);
+    if ((rc = ap::check_compute_dtype("resnet", c.compute_dtype)) != AP_OK) return rc;
     AP_REQUIRE(c.image_size >= 32 && c.image_size <= 1024, "resnet_create: image_size %d", c.image_size);
     ap_resnet* m = new ap_resnet();
     m->cfg = c;
     m->params.dtype = c.compute_dtype;
-    auto add = [&](const std::string& name, int cout, int cin, int ks, int stride, ConvOp* op) {
-        if (rc == AP_OK) rc = add_conv(m, name, cout, cin, ks, stride, op);
-    };
-    const int W = c.stem_width, expansion = c.block == AP_RESNET_BOTTLENECK ? 4 : 1;
-    add("conv1", W, 3, 7, 2, &m->stem);
-    int hw = c.image_size;
-    size_t max_act = (size_t)hw * hw * 8;
-    hw = (hw + 6 - 7) / 2 + 1;
-    max_act = std::max(max_act, (size_t)hw * hw * W);
-    hw = (hw - 1) / 2 + 1;
-    int inplanes = W;
-    for (int s = 0; s < 4; ++s) {
-        const int planes = W << s, outc = planes * expansion;
-        for (int b = 0; b < c.depths[s]; ++b) {
-            const int stride = (s > 0 && b == 0) ? 2 : 1;
-            const std::string pre = "layer" + std::to_string(s + 1) + "." + std::to_string(b) + ".";
-            Block blk{};
-            if (c.block == AP_RESNET_BOTTLENECK) {
-                add(pre + "conv1", planes, inplanes, 1, 1, &blk.c1);
-                add(pre + "conv2", planes, planes, 3, stride, &blk.c2);
-                add(pre + "conv3", outc, planes, 1, 1, &blk.c3);
-                max_act = std::max(max_act, (size_t)hw * hw * planes);
-            } else {
-                add(pre + "conv1", planes, inplanes, 3, stride, &blk.c1);
-                add(pre + "conv2", planes, planes, 3, 1, &blk.c2);
-            }
-            if (stride != 1 || inplanes != outc) add(pre + "downsample", outc, inplanes, 1, stride, &blk.down);
-            hw = (hw - 1) / stride + 1;
-            max_act = std::max(max_act, (size_t)hw * hw * (size_t)std::max(outc, planes));
-            inplanes = outc;
-            m->blocks.push_back(blk);
-        }
-    }
-    m->out_dim = inplanes;
-    m->max_act = max_act;
+    const int W = c.stem_width;
+    m->stem.stride = 2;
+    rc = ap::add_conv(m->params, "conv1", W, 3, 7, &m->stem);
+    const int h1 = (c.image_size + 6 - 7) / 2 + 1;          // the stem convolution's map; the max pool halves it once more
+    ap::Stages st;
+    if (rc == AP_OK)
+        rc = ap::add_stages(m->params, {c.block == AP_RESNET_BOTTLENECK, W, c.depths, false, true}, W, (h1 - 1) / 2 + 1, &st);
+    m->blocks = std::move(st.blocks);
+    m->out_dim = st.channels;
+    m->max_act = std::max({(size_t)c.image_size * c.image_size * 8, (size_t)h1 * h1 * W, st.max_act});
     if (rc != AP_OK) { delete m; return rc; }
     *out = m;
     return AP_OK;
@@ -134,22 +78,13 @@ int ap_resnet_create(const ap_resnet_config* cfg, ap_resnet** out) {
 void ap_resnet_destroy(ap_resnet* m) { delete m; }
 
 int ap_resnet_set_param(ap_resnet* m, const char* name, const float* host, size_t count) {
-    AP_REQUIRE(m && name && host, "resnet_set_param: null argument");
-    const int rc = m->params.set("resnet", name, host, count);
-    if (rc == AP_OK) m->finalized = false;
-    return rc;
+    return ap::set_param(m, "resnet", name, host, count);
 }
 
-int ap_resnet_finalize(ap_resnet* m) {
-    AP_REQUIRE(m, "resnet_finalize: null handle");
-    const int rc = m->params.check_all_set("resnet");
-    if (rc == AP_OK) m->finalized = true;
-    return rc;
-}
+int ap_resnet_finalize(ap_resnet* m) { return ap::finalize(m, "resnet"); }
 
 size_t ap_resnet_workspace_bytes(const ap_resnet* m, int n) {
-    if (!m || n <= 0) return 0;
-    return 4 * align256(m->max_act * (size_t)n * ap::dtype_size(m->cfg.compute_dtype));
+    return m && n > 0 ? ap::Workspace4::bytes(m->max_act, n, m->cfg.compute_dtype) : 0;
 }
 
 int ap_resnet_embed_dim(const ap_resnet* m) { return m ? m->out_dim : 0; }
@@ -169,47 +104,44 @@ int ap_resnet_forward_u8(ap_resnet* m, const uint8_t* patches, int n, int h, int
     AP_REQUIRE(h >= S && w >= S, "resnet_forward_u8: %dx%d tiles smaller than the %d model input", h, w, S);
     hipStream_t s = (hipStream_t)stream;
     const int dt = m->cfg.compute_dtype;
-    const size_t slot = align256(m->max_act * (size_t)n * ap::dtype_size(dt));
-    char* buf[4];
-    for (int i = 0; i < 4; ++i) buf[i] = (char*)workspace + i * slot;
+    ap::Workspace4 ws(workspace, m->max_act, n, dt);
+    char* const* buf = ws.buf;
 
     { ScopedTimer t(m->prof, AP_RESNET_PROF_STEM, s);
       rc = ap::launch_preproc_nhwc8(patches, n, h, w, ap::center_crop_offset(h, S), ap::center_crop_offset(w, S), S, mean, stdv,
                                     buf[0], dt, s); }
     if (rc != AP_OK) return rc;
-    rc = run_conv(m, m->stem, buf[0], n, S, S, nullptr, 1, buf[1], s);
+    rc = run_conv(m, m->stem, buf[0], n, S, nullptr, 1, buf[1], s);
     if (rc != AP_OK) return rc;
-    int hw = conv_out(S, m->stem);
+    int hw = (S + 6 - 7) / 2 + 1;
     { ScopedTimer t(m->prof, AP_RESNET_PROF_POOL, s);
       rc = ap::launch_maxpool3x3s2_nhwc(dt, buf[1], n, hw, hw, m->stem.w->cout, buf[2], s); }
     if (rc != AP_OK) return rc;
     hw = (hw - 1) / 2 + 1;
     int xi = 2;                                     // buffer holding the current activation
     for (const Block& b : m->blocks) {
-        int f[3], k = 0;
-        for (int i = 0; i < 4; ++i) if (i != xi) f[k++] = i;
+        ws.others(xi);
+        const int* f = ws.f;
         const void* x = buf[xi];
-        const ConvOp& last = m->cfg.block == AP_RESNET_BOTTLENECK ? b.c3 : b.c2;
-        const int stride = m->cfg.block == AP_RESNET_BOTTLENECK ? b.c2.stride : b.c1.stride;
-        const int ho = (hw - 1) / stride + 1;
+        const int ho = (hw - 1) / b.stride + 1;
         const void* sc = x;
         if (b.down.w) {
-            rc = run_conv(m, b.down, x, n, hw, hw, nullptr, 0, buf[f[2]], s);
+            rc = run_conv(m, b.down, x, n, hw, nullptr, 0, buf[f[2]], s);
             if (rc != AP_OK) return rc;
             sc = buf[f[2]];
         }
         int oi;
-        if (m->cfg.block == AP_RESNET_BOTTLENECK) {
+        if (b.c3.w) {
             // x -> t1 (f0) -> t2 (f1) -> out (f0, t1 is dead once t2 exists); shortcut in f2 or x
-            if ((rc = run_conv(m, b.c1, x, n, hw, hw, nullptr, 1, buf[f[0]], s)) != AP_OK) return rc;
-            if ((rc = run_conv(m, b.c2, buf[f[0]], n, hw, hw, nullptr, 1, buf[f[1]], s)) != AP_OK) return rc;
+            if ((rc = run_conv(m, b.c1, x, n, hw, nullptr, 1, buf[f[0]], s)) != AP_OK) return rc;
+            if ((rc = run_conv(m, b.c2, buf[f[0]], n, hw, nullptr, 1, buf[f[1]], s)) != AP_OK) return rc;
             oi = f[0];
-            if ((rc = run_conv(m, last, buf[f[1]], n, ho, ho, sc, 1, buf[oi], s)) != AP_OK) return rc;
+            if ((rc = run_conv(m, b.c3, buf[f[1]], n, ho, sc, 1, buf[oi], s)) != AP_OK) return rc;
         } else {
             // x -> t1 (f0) -> out (f1); shortcut in f2 or x
-            if ((rc = run_conv(m, b.c1, x, n, hw, hw, nullptr, 1, buf[f[0]], s)) != AP_OK) return rc;
+            if ((rc = run_conv(m, b.c1, x, n, hw, nullptr, 1, buf[f[0]], s)) != AP_OK) return rc;
             oi = f[1];
-            if ((rc = run_conv(m, last, buf[f[0]], n, ho, ho, sc, 1, buf[oi], s)) != AP_OK) return rc;
+            if ((rc = run_conv(m, b.c2, buf[f[0]], n, ho, sc, 1, buf[oi], s)) != AP_OK) return rc;
         }
         xi = oi;
         hw = ho;

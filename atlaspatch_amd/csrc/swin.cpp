@@ -6,8 +6,9 @@
 // Forward for n images (T = compute dtype, NHWC everywhere, C_s = embed_dim 2^s, H_0 = S / 4):
 //   preprocess  u8 tiles -> centre crop -> normalised T [n, S, S, 8] (channels 3..7 zero)
 //   stem        conv 3x3 s2 p1 + ReLU -> [n, S/2, S/2, 32]; conv 3x3 s2 p1 + ReLU -> [n, H_0, H_0, 32]; conv 1x1 -> C_0;
-//               LayerNorm.  BatchNorm is folded by the caller; the 12 / 24 output channels are padded to 32 with zero weights
-//               and zero bias here (the padded channels stay exactly 0 through the ReLU), so all three run on the implicit GEMM
+//               LayerNorm.  BatchNorm is folded by the caller; the 12 / 24 output channels are stored padded to 32 with zero
+//               weights and zero bias (ParamStore::add_padded; the padded channels stay exactly 0 through the ReLU), so all
+//               three run on the implicit GEMM
 //   stage s     (s > 0: patch merging = 2x2 gather + LayerNorm(4 C_{s-1}) in one kernel, then the bias-free reduction as a
 //               1x1 convolution against a zero bias), then depths[s] blocks, block j with shift 0 (j even, or the map is one
 //               window) or 3:
@@ -27,16 +28,12 @@ namespace {
 constexpr float LN_EPS = 1e-5f;
 constexpr int WINDOW = 7, HEAD_DIM = 32, BIAS_TABLE = 169;
 
+using ap::Conv;
 using ap::DevParam;
 using ap::ParamKind;
 using ap::P_CONV_W;
 using ap::P_VEC;
 using ap::ScopedTimer;
-
-struct Conv {                   // a convolution / linear layer: weight and bias (null: the engine's zero bias)
-    DevParam* w = nullptr;
-    DevParam* b = nullptr;
-};
 
 struct Norm {
     DevParam *w = nullptr, *b = nullptr;
@@ -55,10 +52,6 @@ struct Stage {
     std::vector<Block> blocks;
 };
 
-struct Pad {                        // a stem parameter the caller gives unpadded: [cout, cin, ks, ks] -> [cout_p, cin_p, ks, ks]
-    int cout, cin, ks, cout_p, cin_p;
-};
-
 }  // namespace
 
 struct ap_swin {
@@ -67,7 +60,6 @@ struct ap_swin {
     Conv stem[3];
     Norm stem_ln, final_ln;
     Stage stages[4];
-    std::map<std::string, Pad> padded;          // stem weights and biases: zero-padded on upload
     std::map<std::string, int> bias_tables;     // relative_position_bias_table name -> heads: expanded on upload
     float* zero_bias = nullptr;                 // f32 [C_3] zeros: the reduction layers have no bias
     size_t small_elems = 0;     // elements per image of the largest [H, H, C] activation
@@ -83,11 +75,12 @@ namespace {
 
 size_t align256(size_t v) { return ap::align_up(v, 256); }
 
+// a bias-free layer (c.b null) runs against the engine's zero bias
 int run_conv(ap_swin* m, const Conv& c, const void* x, int n, int h, int stride, int pad, const void* resid, int act, void* out,
              hipStream_t s) {
     const DevParam& w = *c.w;
     return ap::launch_conv2d_nhwc_ex(m->cfg.compute_dtype, x, n, h, h, w.cin_stored, w.d, c.b ? (const float*)c.b->d : m->zero_bias,
-                                     w.cout, w.ks, stride, pad, resid, act, out, s);
+                                     w.cout_stored, w.ks, stride, pad, resid, act, out, s);
 }
 
 int run_ln(ap_swin* m, const Norm& ln, const void* x, int rows, int c, void* out, hipStream_t s) {
@@ -118,8 +111,7 @@ int ap_swin_create(const ap_swin_config* cfg, ap_swin** out) {
         AP_REQUIRE(c.heads[s] >= 1 && (c.embed_dim << s) == c.heads[s] * HEAD_DIM,
                    "swin_create: stage %d has width %d and %d heads (the head dimension must be 32)", s, c.embed_dim << s, c.heads[s]);
     }
-    AP_REQUIRE(c.compute_dtype == AP_F16 || c.compute_dtype == AP_BF16 || c.compute_dtype == AP_F32,
-               "swin_create: compute dtype %d", c.compute_dtype);
+    if ((rc = ap::check_compute_dtype("swin", c.compute_dtype)) != AP_OK) return rc;
     AP_REQUIRE(c.image_size >= 224 && c.image_size <= 896 && c.image_size % 224 == 0,
                "swin_create: image_size %d (a multiple of 224: every stage's map is whole 7x7 windows)", c.image_size);
     ap_swin* m = new ap_swin();
@@ -133,21 +125,17 @@ int ap_swin_create(const ap_swin_config* cfg, ap_swin** out) {
         add(pre + ".bias", P_VEC, width, 0, 0, &ln->b);
     };
     auto add_linear = [&](const std::string& pre, int cout, int cin, Conv* l) {
-        add(pre + ".weight", P_CONV_W, cout, cin, 1, &l->w);
-        add(pre + ".bias", P_VEC, cout, 0, 0, &l->b);
+        if (rc == AP_OK) rc = ap::add_conv(m->params, pre, cout, cin, 1, l);
     };
-    auto add_padded = [&](const std::string& pre, int cout, int cin, int ks, int cin_p, Conv* l) {
-        const int cout_p = (int)ap::align_up((size_t)cout, 32);
-        add(pre + ".weight", P_CONV_W, cout_p, cin_p, ks, &l->w);
-        add(pre + ".bias", P_VEC, cout_p, 0, 0, &l->b);
-        m->padded[pre + ".weight"] = Pad{cout, cin, ks, cout_p, cin_p};
-        m->padded[pre + ".bias"] = Pad{cout, 0, 0, cout_p, 0};
+    // the stem: Cout stored as the next multiple of 32, Cin as the producing map's stored channels (the image: 8)
+    auto add_stem = [&](const std::string& pre, int cout, int cin, int ks, int cin_p, Conv* l) {
+        if (rc == AP_OK) rc = ap::add_conv(m->params, pre, cout, cin, ks, (int)ap::align_up((size_t)cout, 32), cin_p, l);
     };
     const int S = c.image_size, E = c.embed_dim;
     const int c1 = E / 8, c2 = E / 4, c1p = (int)ap::align_up((size_t)c1, 32), c2p = (int)ap::align_up((size_t)c2, 32);
-    add_padded("patch_embed.proj.0", c1, 3, 3, 3, &m->stem[0]);
-    add_padded("patch_embed.proj.3", c2, c1, 3, c1p, &m->stem[1]);
-    add_padded("patch_embed.proj.6", E, c2, 1, c2p, &m->stem[2]);
+    add_stem("patch_embed.proj.0", c1, 3, 3, 8, &m->stem[0]);
+    add_stem("patch_embed.proj.3", c2, c1, 3, c1p, &m->stem[1]);
+    add_stem("patch_embed.proj.6", E, c2, 1, c2p, &m->stem[2]);
     add_norm("patch_embed.norm", E, &m->stem_ln);
     size_t small = 0, big = (size_t)S * S * 8 + (size_t)(S / 2) * (S / 2) * c1p + 128;   // + the 256-byte alignment slack
     small = (size_t)(S / 4) * (S / 4) * c2p;
@@ -197,50 +185,22 @@ int ap_swin_create(const ap_swin_config* cfg, ap_swin** out) {
 void ap_swin_destroy(ap_swin* m) { delete m; }
 
 int ap_swin_set_param(ap_swin* m, const char* name, const float* host, size_t count) {
-    AP_REQUIRE(m && name && host, "swin_set_param: null argument");
-    int rc;
-    auto pad = m->padded.find(name);
-    auto table = m->bias_tables.find(name);
-    if (pad != m->padded.end()) {
-        // the stem as the checkpoint has it -> zero-padded output (and input) channels
-        const Pad& p = pad->second;
-        const size_t per_in = p.cin ? (size_t)p.ks * p.ks : 1, given = p.cin ? (size_t)p.cout * p.cin * per_in : (size_t)p.cout;
-        AP_REQUIRE(count == given, "swin_set_param: %s has %zu values, expected %zu", name, count, given);
-        std::vector<float> t(p.cin ? (size_t)p.cout_p * p.cin_p * per_in : (size_t)p.cout_p, 0.f);
-        if (p.cin) {
-            for (int o = 0; o < p.cout; ++o)
-                for (int ci = 0; ci < p.cin; ++ci)
-                    for (size_t k = 0; k < per_in; ++k) t[((size_t)o * p.cin_p + ci) * per_in + k] = host[((size_t)o * p.cin + ci) * per_in + k];
-        } else {
-            std::copy(host, host + p.cout, t.begin());
-        }
-        rc = m->params.set("swin", name, t.data(), t.size());
-    } else if (table != m->bias_tables.end()) {
-        // timm's relative_position_bias_table [169, heads] -> f32 [heads][49][49]: B_h[i, j] = table[(yi - yj + 6) 13 + (xi - xj + 6), h]
-        const int heads = table->second;
-        AP_REQUIRE(count == (size_t)BIAS_TABLE * heads, "swin_set_param: %s has %zu values, expected %zu", name, count,
-                   (size_t)BIAS_TABLE * heads);
-        std::vector<float> t((size_t)heads * 49 * 49);
-        for (int h = 0; h < heads; ++h)
-            for (int i = 0; i < 49; ++i)
-                for (int j = 0; j < 49; ++j) {
-                    const int idx = (i / 7 - j / 7 + 6) * 13 + (i % 7 - j % 7 + 6);
-                    t[((size_t)h * 49 + i) * 49 + j] = host[(size_t)idx * heads + h];
-                }
-        rc = m->params.set("swin", name, t.data(), t.size());
-    } else {
-        rc = m->params.set("swin", name, host, count);
-    }
-    if (rc == AP_OK) m->finalized = false;
-    return rc;
+    if (!m || !name || !host || !m->bias_tables.count(name)) return ap::set_param(m, "swin", name, host, count);
+    // timm's relative_position_bias_table [169, heads] -> f32 [heads][49][49]: B_h[i, j] = table[(yi - yj + 6) 13 + (xi - xj + 6), h]
+    const int heads = m->bias_tables[name];
+    AP_REQUIRE(count == (size_t)BIAS_TABLE * heads, "swin_set_param: %s has %zu values, expected %zu", name, count,
+               (size_t)BIAS_TABLE * heads);
+    std::vector<float> t((size_t)heads * 49 * 49);
+    for (int h = 0; h < heads; ++h)
+        for (int i = 0; i < 49; ++i)
+            for (int j = 0; j < 49; ++j) {
+                const int idx = (i / 7 - j / 7 + 6) * 13 + (i % 7 - j % 7 + 6);
+                t[((size_t)h * 49 + i) * 49 + j] = host[(size_t)idx * heads + h];
+            }
+    return ap::set_param(m, "swin", name, t.data(), t.size());
 }
 
-int ap_swin_finalize(ap_swin* m) {
-    AP_REQUIRE(m, "swin_finalize: null handle");
-    const int rc = m->params.check_all_set("swin");
-    if (rc == AP_OK) m->finalized = true;
-    return rc;
-}
+int ap_swin_finalize(ap_swin* m) { return ap::finalize(m, "swin"); }
 
 size_t ap_swin_workspace_bytes(const ap_swin* m, int n) {
     if (!m || n <= 0) return 0;

@@ -18,18 +18,18 @@ These names are not in ``build_default_registry``: they are registered by ``regi
 from __future__ import annotations
 
 import ctypes as C
-import re
+import functools
 from typing import Optional
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
 from .. import _lib
+from . import convbn
 from .base import HipViTFeatureExtractor, NativeEncoder
-from .vit import OPENAI_CLIP_MEAN, OPENAI_CLIP_STD, _env_seed, check_canonical, resolve_weights
+from .checkpoints import OPENAI_CLIP_MEAN, OPENAI_CLIP_STD, _env_seed, check_canonical, resolve_weights
 
-BN_EPS = 1e-5
+BN_EPS = convbn.BN_EPS
 HEAD_DIM = 64
 
 ARCHS = {
@@ -63,41 +63,14 @@ def conv_layers(arch) -> list:
     average pool, every convolution there has stride 1.  The order is the one ``ap_clip_resnet_create`` allocates."""
     spec = _spec(arch)
     w = int(spec["width"])
-    out = [("conv1", w // 2, 3, 3, 2), ("conv2", w // 2, w // 2, 3, 1), ("conv3", w, w // 2, 3, 1)]
-    inplanes = w
-    for s, depth in enumerate(spec["depths"]):
-        planes = w << s
-        outc = planes * 4
-        for b in range(depth):
-            stride = 2 if (s > 0 and b == 0) else 1
-            pre = f"layer{s + 1}.{b}."
-            out += [(pre + "conv1", planes, inplanes, 1, 1), (pre + "conv2", planes, planes, 3, 1), (pre + "conv3", outc, planes, 1, 1)]
-            if stride != 1 or inplanes != outc:
-                out.append((pre + "downsample", outc, inplanes, 1, stride))
-            inplanes = outc
-    return out
-
-
-def _bn_name(conv: str) -> str:
-    """BatchNorm name of a convolution: conv1 -> bn1, layerX.Y.convK -> layerX.Y.bnK, downsample -> downsample.1"""
-    if conv.endswith("downsample"):
-        return conv + ".1"
-    head, _, last = conv.rpartition(".")
-    return (head + "." if head else "") + "bn" + last[len("conv"):]
-
-
-def _conv_key(conv: str) -> str:
-    return conv + (".0.weight" if conv.endswith("downsample") else ".weight")
+    stem = [("conv1", w // 2, 3, 3, 2), ("conv2", w // 2, w // 2, 3, 1), ("conv3", w, w // 2, 3, 1)]
+    return stem + convbn.stage_layers(w, spec["depths"], bottleneck=True, stride_in_conv=False)
 
 
 def canonical_keys(arch) -> dict:
     """{open_clip key: shape} of the unfolded visual tower (no ``num_batches_tracked``)."""
     spec = _spec(arch)
-    keys = {}
-    for name, cout, cin, k, _ in conv_layers(arch):
-        keys[_conv_key(name)] = (cout, cin, k, k)
-        for p in ("weight", "bias", "running_mean", "running_var"):
-            keys[f"{_bn_name(name)}.{p}"] = (cout,)
+    keys = convbn.conv_bn_keys(conv_layers(arch))
     c, g = embed_width(arch), grid_size(arch)
     keys["attnpool.positional_embedding"] = (g * g + 1, c)
     for proj, rows in (("q_proj", c), ("k_proj", c), ("v_proj", c), ("c_proj", int(spec["output_dim"]))):
@@ -136,19 +109,7 @@ def fold_batchnorm(canonical: dict, *, arch, dtype: torch.dtype = torch.float32,
     """Conv + BatchNorm (eval) -> one conv with bias, in float32 (W' = W g / sqrt(var + eps), b' = beta - mean g / sqrt(var + eps)),
     and the head under the engine's names: ``attnpool.pos``, ``attnpool.q``, ``attnpool.kv`` (k_proj's rows, then v_proj's) and
     ``attnpool.c``.  What ``ap_clip_resnet_set_param`` takes.  A folded weight that is not finite in ``dtype`` is refused."""
-    out = {}
-    for name, *_ in conv_layers(arch):
-        bn = _bn_name(name)
-        g, beta = canonical[f"{bn}.weight"], canonical[f"{bn}.bias"]
-        mean, var = canonical[f"{bn}.running_mean"], canonical[f"{bn}.running_var"]
-        scale = g / torch.sqrt(var + eps)
-        w = canonical[_conv_key(name)] * scale.view(-1, 1, 1, 1)
-        b = beta - mean * scale
-        if not bool(torch.isfinite(w.to(dtype)).all()) or not bool(torch.isfinite(b).all()):
-            raise ValueError(f"{name}: the BatchNorm-folded weights are not finite in {dtype} (max |w'| = "
-                             f"{float(w.abs().max()):.3g}); this checkpoint cannot run in that precision")
-        out[f"{name}.weight"] = w.contiguous()
-        out[f"{name}.bias"] = b.contiguous()
+    out = convbn.fold_layers(canonical, conv_layers(arch), dtype, eps)
     a = "attnpool."
     out["attnpool.pos"] = canonical[a + "positional_embedding"].contiguous()
     out["attnpool.q.weight"] = canonical[a + "q_proj.weight"][:, :, None, None].contiguous()
@@ -186,16 +147,10 @@ def _forward_calibrate(sd: dict, arch, x: torch.Tensor) -> None:
     the batch statistics of its input (rounded to float16 precision so that they do not depend on the host's summation order)."""
     spec = _spec(arch)
 
-    def bn(t, name):
-        mean = t.mean(dim=(0, 2, 3))
-        var = t.var(dim=(0, 2, 3), unbiased=False)
-        sd[f"{name}.running_mean"] = mean.half().float()
-        sd[f"{name}.running_var"] = var.half().float()
-        return F.batch_norm(t, sd[f"{name}.running_mean"], sd[f"{name}.running_var"], sd[f"{name}.weight"], sd[f"{name}.bias"],
-                            False, 0.0, BN_EPS)
+    bn = functools.partial(convbn.calibrate_bn, sd)
 
     def conv(t, name, stride=1):
-        w = sd[_conv_key(name)]
+        w = sd[convbn.conv_key(name)]
         return F.conv2d(t, w, stride=stride, padding=w.shape[-1] // 2)
 
     x = F.relu(bn(conv(x, "conv1", 2), "bn1"))
@@ -212,7 +167,7 @@ def _forward_calibrate(sd: dict, arch, x: torch.Tensor) -> None:
                 y = F.avg_pool2d(y, 2)
             y = bn(conv(y, pre + "conv3"), pre + "bn3")
             sc = x
-            if _conv_key(pre + "downsample") in sd:
+            if convbn.conv_key(pre + "downsample") in sd:
                 sc = bn(conv(F.avg_pool2d(x, 2) if stride == 2 else x, pre + "downsample"), pre + "downsample.1")
             x = F.relu(y + sc)
 
@@ -238,16 +193,7 @@ def random_canonical_state_dict(arch, seed: int = 0) -> dict:
     projections and positional embedding normal with std C^-0.5."""
     spec = _spec(arch)
     g = torch.Generator().manual_seed(int(seed))
-    sd = {}
-    for name, cout, cin, k, _ in conv_layers(arch):
-        sd[_conv_key(name)] = torch.randn(cout, cin, k, k, generator=g) * float(np.sqrt(2.0 / (cin * k * k)))
-        bn = _bn_name(name)
-        gain = 0.8 + 0.4 * torch.rand(cout, generator=g)
-        m = re.match(r"layer(\d+)\.\d+\.conv3$", name)
-        if m:
-            gain = gain / float(np.sqrt(spec["depths"][int(m.group(1)) - 1]))
-        sd[f"{bn}.weight"] = gain
-        sd[f"{bn}.bias"] = 0.1 * torch.randn(cout, generator=g)
+    sd = convbn.random_conv_bn(conv_layers(arch), spec["depths"], 3, g)
     c, grid = embed_width(arch), grid_size(arch)
     std = float(c) ** -0.5
     sd["attnpool.positional_embedding"] = torch.randn(grid * grid + 1, c, generator=g) * std

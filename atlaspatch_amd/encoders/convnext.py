@@ -26,7 +26,7 @@ import torch
 
 from .. import _lib
 from .base import HipViTFeatureExtractor, NativeEncoder
-from .vit import IMAGENET_MEAN, IMAGENET_STD, _env_seed, check_canonical, resolve_weights
+from .checkpoints import IMAGENET_MEAN, IMAGENET_STD, _env_seed, check_canonical, resolve_weights
 
 LN_EPS = 1e-6
 

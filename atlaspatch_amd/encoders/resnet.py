@@ -16,18 +16,19 @@ These names are not in ``build_default_registry``: they are registered by ``regi
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import re
 from typing import Optional
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
 from .. import _lib
+from . import convbn
 from .base import HipViTFeatureExtractor, NativeEncoder
-from .vit import IMAGENET_MEAN, IMAGENET_STD, _env_seed, check_canonical, resolve_weights
+from .checkpoints import IMAGENET_MEAN, IMAGENET_STD, _env_seed, check_canonical, resolve_weights
 
-BN_EPS = 1e-5
+BN_EPS = convbn.BN_EPS
 TRANSFORM_RESIZE = (256, "bilinear")      # ImageClassification(crop_size=224): resize 256 (Pillow BILINEAR), crop 224
 
 ARCHS = {
@@ -52,46 +53,13 @@ def conv_layers(arch) -> list:
     the projection shortcut).  The order is the one ``ap_resnet_create`` allocates."""
     spec = _spec(arch)
     w = int(spec["stem_width"])
-    expansion = 4 if spec["block"] == "bottleneck" else 1
-    out = [("conv1", w, 3, 7, 2)]
-    inplanes = w
-    for s, depth in enumerate(spec["depths"]):
-        planes = w << s
-        outc = planes * expansion
-        for b in range(depth):
-            stride = 2 if (s > 0 and b == 0) else 1
-            pre = f"layer{s + 1}.{b}."
-            if spec["block"] == "bottleneck":
-                out += [(pre + "conv1", planes, inplanes, 1, 1), (pre + "conv2", planes, planes, 3, stride),
-                        (pre + "conv3", outc, planes, 1, 1)]
-            else:
-                out += [(pre + "conv1", planes, inplanes, 3, stride), (pre + "conv2", planes, planes, 3, 1)]
-            if stride != 1 or inplanes != outc:
-                out.append((pre + "downsample", outc, inplanes, 1, stride))
-            inplanes = outc
-    return out
-
-
-def _bn_name(conv: str) -> str:
-    """torchvision BatchNorm name of a convolution: conv1 -> bn1, layerX.Y.convK -> layerX.Y.bnK, downsample -> downsample.1"""
-    if conv.endswith("downsample"):
-        return conv + ".1"
-    head, _, last = conv.rpartition(".")
-    return (head + "." if head else "") + "bn" + last[len("conv"):]
-
-
-def _conv_key(conv: str) -> str:
-    return conv + (".0.weight" if conv.endswith("downsample") else ".weight")
+    return [("conv1", w, 3, 7, 2)] + convbn.stage_layers(w, spec["depths"], bottleneck=spec["block"] == "bottleneck",
+                                                        stride_in_conv=True)
 
 
 def canonical_keys(arch) -> dict:
     """{torchvision key: shape} of the unfolded checkpoint (no ``fc``, no ``num_batches_tracked``)."""
-    keys = {}
-    for name, cout, cin, k, _ in conv_layers(arch):
-        keys[_conv_key(name)] = (cout, cin, k, k)
-        for p in ("weight", "bias", "running_mean", "running_var"):
-            keys[f"{_bn_name(name)}.{p}"] = (cout,)
-    return keys
+    return convbn.conv_bn_keys(conv_layers(arch))
 
 
 _HF_CONV = re.compile(r"^encoder\.stages\.(\d+)\.layers\.(\d+)\.(layer\.(\d+)|shortcut)\.(convolution|normalization)\.(.+)$")
@@ -159,20 +127,7 @@ def fold_batchnorm(canonical: dict, *, arch, dtype: torch.dtype = torch.float32,
     """Conv + BatchNorm (eval) -> one conv with bias, in float32: W' = W g / sqrt(var + eps), b' = beta - mean g / sqrt(var + eps).
     Keys ``<conv>.weight`` / ``<conv>.bias`` (``downsample`` for the projection), what ``ap_resnet_set_param`` takes.  A folded
     weight that is not finite in ``dtype`` (or a bias that is not finite) is refused."""
-    out = {}
-    for name, *_ in conv_layers(arch):
-        bn = _bn_name(name)
-        g, beta = canonical[f"{bn}.weight"], canonical[f"{bn}.bias"]
-        mean, var = canonical[f"{bn}.running_mean"], canonical[f"{bn}.running_var"]
-        scale = g / torch.sqrt(var + eps)
-        w = canonical[_conv_key(name)] * scale.view(-1, 1, 1, 1)
-        b = beta - mean * scale
-        if not bool(torch.isfinite(w.to(dtype)).all()) or not bool(torch.isfinite(b).all()):
-            raise ValueError(f"{name}: the BatchNorm-folded weights are not finite in {dtype} (max |w'| = "
-                             f"{float(w.abs().max()):.3g}); this checkpoint cannot run in that precision")
-        out[f"{name}.weight"] = w.contiguous()
-        out[f"{name}.bias"] = b.contiguous()
-    return out
+    return convbn.fold_layers(canonical, conv_layers(arch), dtype, eps)
 
 
 def _forward_calibrate(sd: dict, arch, x: torch.Tensor) -> None:
@@ -180,19 +135,13 @@ def _forward_calibrate(sd: dict, arch, x: torch.Tensor) -> None:
     its input (rounded to float16 precision so that they do not depend on the host's summation order)."""
     spec = _spec(arch)
 
-    def bn(t, name):
-        mean = t.mean(dim=(0, 2, 3))
-        var = t.var(dim=(0, 2, 3), unbiased=False)
-        sd[f"{name}.running_mean"] = mean.half().float()
-        sd[f"{name}.running_var"] = var.half().float()
-        return F.batch_norm(t, sd[f"{name}.running_mean"], sd[f"{name}.running_var"], sd[f"{name}.weight"], sd[f"{name}.bias"],
-                            False, 0.0, BN_EPS)
+    bn = functools.partial(convbn.calibrate_bn, sd)
 
     layers = {name: (k, stride) for name, _, _, k, stride in conv_layers(arch)}
 
     def conv(t, name):
         k, stride = layers[name]
-        return F.conv2d(t, sd[_conv_key(name)], stride=stride, padding=k // 2)
+        return F.conv2d(t, sd[convbn.conv_key(name)], stride=stride, padding=k // 2)
 
     x = F.relu(bn(conv(x, "conv1"), "bn1"))
     x = F.max_pool2d(x, 3, 2, 1)
@@ -216,17 +165,7 @@ def random_canonical_state_dict(arch, seed: int = 0) -> dict:
     O(1) through all stages, in float16's range with room to spare."""
     spec = _spec(arch)
     g = torch.Generator().manual_seed(int(seed))
-    sd = {}
-    n_conv = 3 if spec["block"] == "bottleneck" else 2
-    for name, cout, cin, k, _ in conv_layers(arch):
-        sd[_conv_key(name)] = torch.randn(cout, cin, k, k, generator=g) * float(np.sqrt(2.0 / (cin * k * k)))
-        bn = _bn_name(name)
-        gain = 0.8 + 0.4 * torch.rand(cout, generator=g)
-        m = re.match(r"layer(\d+)\.\d+\.conv(\d+)$", name)
-        if m and int(m.group(2)) == n_conv:
-            gain = gain / float(np.sqrt(spec["depths"][int(m.group(1)) - 1]))
-        sd[f"{bn}.weight"] = gain
-        sd[f"{bn}.bias"] = 0.1 * torch.randn(cout, generator=g)
+    sd = convbn.random_conv_bn(conv_layers(arch), spec["depths"], 3 if spec["block"] == "bottleneck" else 2, g)
     x = torch.randn(2, 3, 128, 128, generator=g)
     with torch.no_grad():
         _forward_calibrate(sd, arch, x)

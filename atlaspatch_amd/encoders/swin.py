@@ -32,11 +32,12 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import convbn
 from .base import HipViTFeatureExtractor, NativeEncoder
-from .vit import IMAGENET_MEAN, IMAGENET_STD, _env_seed, check_canonical, resolve_weights
+from .checkpoints import IMAGENET_MEAN, IMAGENET_STD, _env_seed, check_canonical, resolve_weights
 
 LN_EPS = 1e-5
-BN_EPS = 1e-5
+BN_EPS = convbn.BN_EPS
 WINDOW = 7
 TRANSFORM_RESIZE = (224, "bilinear")      # transforms.Resize(224) on the PIL tile
 
@@ -46,7 +47,7 @@ ARCHS = {
 DEFAULTS = {"window": WINDOW, "image_size": 224}
 MAX_BATCH = 256         # device batch: the four activation buffers at 256 tiles are 1.1 GB in float16
 
-_BN = ("weight", "bias", "running_mean", "running_var")
+_BN = convbn.BN_PARAMS
 _STEM_BN = {"patch_embed.proj.0": "patch_embed.proj.1", "patch_embed.proj.3": "patch_embed.proj.4"}
 
 
@@ -177,14 +178,7 @@ def fold_batchnorm(canonical: dict, *, arch="chief-ctranspath", dtype: torch.dty
     bn_keys = {f"{bn}.{p}" for bn in _STEM_BN.values() for p in _BN}
     out = {k: canonical[k] for k in canonical_keys(arch) if k not in bn_keys}
     for conv, bn in _STEM_BN.items():
-        scale = canonical[f"{bn}.weight"] / torch.sqrt(canonical[f"{bn}.running_var"] + eps)
-        w = canonical[f"{conv}.weight"] * scale.view(-1, 1, 1, 1)
-        b = canonical[f"{bn}.bias"] - canonical[f"{bn}.running_mean"] * scale
-        if not bool(torch.isfinite(w.to(dtype)).all()) or not bool(torch.isfinite(b).all()):
-            raise ValueError(f"{conv}: the BatchNorm-folded weights are not finite in {dtype} (max |w'| = "
-                             f"{float(w.abs().max()):.3g}); this checkpoint cannot run in that precision")
-        out[f"{conv}.weight"] = w.contiguous()
-        out[f"{conv}.bias"] = b.contiguous()
+        out[f"{conv}.weight"], out[f"{conv}.bias"] = convbn.fold_conv_bn(canonical, conv, bn, dtype, eps)
     return out
 
 

@@ -242,6 +242,14 @@ def test_swin_engine_through_the_c_abi_alone():
         for k, a in arrs.items():
             if k != last:
                 lib.check(L.ap_swin_set_param(handle, k.encode(), a.ctypes.data, a.size), k)
+        # the padded stem takes the checkpoint's shape (E/8 = 12 channels of 3 x 3 x 3), never the stored one (32 of 8 x 3 x 3)
+        stem_w, stem_b = arrs["patch_embed.proj.0.weight"], arrs["patch_embed.proj.0.bias"]
+        assert stem_w.size == 96 // 8 * 3 * 9 and stem_b.size == 96 // 8
+        stored_w, stored_b = np.zeros(32 * 8 * 9, np.float32), np.zeros(32, np.float32)
+        assert L.ap_swin_set_param(handle, b"patch_embed.proj.0.weight", stored_w.ctypes.data, stored_w.size) == lib.AP_ERR_INVALID
+        assert L.ap_swin_set_param(handle, b"patch_embed.proj.0.bias", stored_b.ctypes.data, stored_b.size) == lib.AP_ERR_INVALID
+        lib.check(L.ap_swin_set_param(handle, b"patch_embed.proj.0.weight", stem_w.ctypes.data, stem_w.size), "stem weight")
+        lib.check(L.ap_swin_set_param(handle, b"patch_embed.proj.0.bias", stem_b.ctypes.data, stem_b.size), "stem bias")
         assert L.ap_swin_finalize(handle) != lib.AP_OK                                       # a parameter was never set
         assert L.ap_swin_set_param(handle, last.encode(), arrs[last].ctypes.data, 7) == lib.AP_ERR_INVALID
         assert L.ap_swin_set_param(handle, b"layers.0.downsample.norm.bias", arrs[last].ctypes.data, 768) == lib.AP_ERR_INVALID
