@@ -297,10 +297,26 @@ int ap_layernorm(int out_dtype, const float* x, long stride, int rows, int dim, 
     return ap::launch_layernorm(out_dtype, x, stride, rows, dim, gamma, beta, eps, out, (hipStream_t)stream);
 }
 
+// What ap_attention and ap_attention_scaled refuse before anything is launched: the launchers assume all of it.  Both kernels
+// move 16 bytes per lane (LDS-DMA and fragment loads of q / k / v, row-wise stores of out; the float32 strip kernel's widest
+// access is one f32x4), and every row and head offset is a multiple of 16 bytes, so 16-byte alignment of the two pointers
+// is the whole rule, in float32 as well.
+static int attention_args_ok(const char* who, int dtype, const void* qkv, const void* out, int n, int tokens, int heads, int head_dim) {
+    AP_REQUIRE(qkv && out, "%s: null pointer", who);
+    AP_REQUIRE(known_dtype(dtype), "%s: unknown dtype %d", who, dtype);
+    AP_REQUIRE(n >= 0 && tokens > 0 && heads > 0, "%s: bad shape (n %d, %d tokens, %d heads)", who, n, tokens, heads);
+    AP_REQUIRE(head_dim == 64 || ((head_dim == 96 || head_dim == 128) && dtype != AP_F32),
+               "%s: head_dim %d unsupported (64; 96 / 128 in f16 / bf16)", who, head_dim);
+    AP_REQUIRE((uintptr_t)qkv % 16 == 0 && (uintptr_t)out % 16 == 0, "%s: qkv / out must be 16-byte aligned", who);
+    // the tiled kernel addresses a key row by a 32-bit byte offset inside its image
+    AP_REQUIRE(dtype == AP_F32 || (size_t)tokens * 3 * heads * head_dim * 2 < 0xffffffffull,
+               "%s: %d tokens x %d heads x %d: an image's qkv rows exceed 4 GiB", who, tokens, heads, head_dim);
+    return AP_OK;
+}
+
 int ap_attention(int dtype, const void* qkv, void* out, int n, int tokens, int heads, int head_dim,
                  ap_stream_t stream) {
-    AP_REQUIRE(qkv && out, "ap_attention: null pointer");
-    AP_REQUIRE(head_dim > 0, "ap_attention: head_dim %d", head_dim);
+    if (int rc = attention_args_ok("ap_attention", dtype, qkv, out, n, tokens, heads, head_dim)) return rc;
     return ap::launch_attention(dtype, qkv, out, n, tokens, heads, head_dim, 1.0f / sqrtf((float)head_dim), (hipStream_t)stream);
 }
 
@@ -308,11 +324,7 @@ int ap_attention(int dtype, const void* qkv, void* out, int n, int tokens, int h
 // without checking (a refusal launches nothing) and forwards; the launchers' own checks follow.
 int ap_attention_scaled(int dtype, const void* qkv, void* out, int n, int tokens, int heads, int head_dim, float scale,
                         ap_stream_t stream) {
-    AP_REQUIRE(qkv && out, "ap_attention_scaled: null pointer");
-    AP_REQUIRE(known_dtype(dtype), "ap_attention_scaled: unknown dtype %d", dtype);
-    AP_REQUIRE(n >= 0 && tokens > 0 && heads > 0, "ap_attention_scaled: bad shape (n %d, %d tokens, %d heads)", n, tokens, heads);
-    AP_REQUIRE(head_dim == 64 || ((head_dim == 96 || head_dim == 128) && dtype != AP_F32),
-               "ap_attention_scaled: head_dim %d unsupported (64; 96 / 128 in f16 / bf16)", head_dim);
+    if (int rc = attention_args_ok("ap_attention_scaled", dtype, qkv, out, n, tokens, heads, head_dim)) return rc;
     AP_REQUIRE(std::isfinite(scale) && scale > 0.f, "ap_attention_scaled: scale must be positive and finite");
     return ap::launch_attention(dtype, qkv, out, n, tokens, heads, head_dim, scale, (hipStream_t)stream);
 }

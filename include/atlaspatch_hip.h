@@ -487,7 +487,12 @@ int ap_layernorm(int out_dtype, const float* x, long stride, int rows, int dim,
 
 /* Multi-head self-attention on packed projections: qkv T [n * tokens, 3 * heads * head_dim]
  * (q | k | v), out T [n * tokens, heads * head_dim]; softmax(q k^T / sqrt(head_dim)) v in f32
- * (F.scaled_dot_product_attention without mask / dropout).  head_dim: 64 (any dtype), 96 or 128 (float16 / bfloat16). */
+ * (F.scaled_dot_product_attention without mask / dropout).  head_dim: 64 (any dtype), 96 or 128 (float16 / bfloat16).
+ * qkv and out are 16-byte aligned (the kernels move 16 bytes per lane; float32 needs no more).  Refused with
+ * AP_ERR_INVALID and text in ap_last_error() before anything is launched, as by ap_attention_scaled: a null or
+ * misaligned pointer, an unknown dtype, n < 0, tokens <= 0, heads <= 0, a head_dim the type does not serve, and in
+ * float16 / bfloat16 an image whose qkv rows reach 4 GiB (tokens * 3 * heads * head_dim * 2 bytes: rows are addressed by a
+ * 32-bit offset).  float32: at most 288 tokens (AP_ERR_UNSUPPORTED beyond, nothing launched).  n = 0 is an empty launch. */
 int ap_attention(int dtype, const void* qkv, void* out, int n, int tokens, int heads, int head_dim,
                  ap_stream_t stream);
 
@@ -498,7 +503,8 @@ int ap_attention(int dtype, const void* qkv, void* out, int n, int tokens, int h
  * address; n = 0 or rows = 0 is an empty launch.  Pointers are 16-byte aligned unless stated.
  *
  * ap_attention_scaled: ap_attention with the softmax scale given (head widths stored zero-padded to 96: scale =
- *   1 / sqrt(true width)); scale > 0.  float32: 64-wide heads, at most 288 tokens (AP_ERR_UNSUPPORTED beyond).
+ *   1 / sqrt(true width)); scale > 0 and finite; alignment and refusals as ap_attention.  float32: 64-wide heads, at most
+ *   288 tokens (AP_ERR_UNSUPPORTED beyond).
  * ap_attention_cls: one query row per (image, head) -- the class row of the last block.  q T [n, heads * head_dim]
  *   packed; k and v inside rows of kv T [n * tokens, ld] at columns koff + head * head_dim and voff + head * head_dim;
  *   out T [n, heads * head_dim] = softmax_t(scale * q . k_t) v_t, f32 arithmetic, the maximum subtracted before the

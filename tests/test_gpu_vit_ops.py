@@ -5,11 +5,16 @@ against the float64 restatements of tests/vit_ops_reference.py, under that modul
 
     |got - ref64| <= u(T) |ref64| + floor(T) + k_op 2^-24 A
 
-(k_op measured on the CPU, see there) and bit for bit wherever the contract is exact.  The inputs are the ones
+(k_op measured on the CPU, see there; full attention -- ap_attention and ap_attention_scaled, tiled and register-strip
+kernels -- adds u(T) B for its softmax weights rounded to T) and bit for bit wherever the contract is exact.  The inputs are the ones
 tests/test_vit_ops_reference.py shows to refuse every listed mistake.  Every output and in-place buffer lies between two guard
 bands filled with a NaN pattern, which are compared bit for bit afterwards."""
+import functools
 import itertools
 import math
+import os
+import subprocess
+import sys
 
 import pytest
 import torch
@@ -18,6 +23,7 @@ from tests import vit_ops_reference as R
 from tests.helpers import PATTERN, Guarded
 
 pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -43,7 +49,7 @@ def _verify(op, case_results):
             k = R.k_of(op, o)
             bad = R.failures(got[name], o, k)
             if o.A is not None:
-                tol = R.U[o.dtype] * o.value.abs() + R.FLOOR[o.dtype] + k * 2.0 ** -24 * o.A.double()
+                tol = R.tolerance(o, k)
                 live = ~o.exact if o.exact is not None else torch.ones_like(tol, dtype=torch.bool)
                 if bool(live.any()):
                     ratio = ((got[name].double() - o.value).abs() / tol)[live]
@@ -113,6 +119,69 @@ def test_attention_scaled(env, dt, hd, width, factor):
         worst = max(worst, err if err == err else float("inf"))
         assert err <= R.ATTENTION_SCALED_TOL[dt], (tokens, n, heads, err)
     print(f"attention_scaled {dt} hd {hd}: worst |out - ref64| = {worst:.3e} (bound {R.ATTENTION_SCALED_TOL[dt]})")
+
+
+FULL_COMBOS = [(dt, hd) for dt in R.HALF for hd in (64, 96, 128)] + [(torch.float32, 64)]
+
+
+@pytest.mark.parametrize("dt,hd", FULL_COMBOS, ids=str)
+def test_attention_per_element(env, dt, hd):
+    """ap_attention / ap_attention_scaled per element against float64, on inputs whose every query is dominated by chosen
+    keys (at the ends, the tile / 32-key / 16-key seams, the last valid key) at the token counts that reach every last-tile
+    body, ring depth, staging wrap and deal of query blocks of the tiled kernel, with (1, 1) and nine (image, head) units, plus
+    the rescale staircases; float32 is the register-strip kernel (<= 288 tokens).  The bound carries u(T) B for the weights
+    rounded to T (tests/vit_ops_reference.py, ref_attention)."""
+    from tests.attention_strip_child import run_case
+    _lib, lib, dev, stream = env
+    results = [(case.id, {"out": run_case(_lib, lib, dev, stream, case.args)}, R.ref_attention(case.args))
+               for case in R.cases("attention", dtypes=(dt,), widths=(hd,))]
+    assert len(results) == (45 if dt == torch.float32 else 55)
+    _verify("attention", results)
+
+
+@functools.lru_cache(maxsize=None)
+def _strip_references():
+    from tests.attention_strip_child import strip_cases
+    return {case.id: R.ref_attention(case.args) for case in strip_cases()}
+
+
+@pytest.mark.parametrize("waves", [4, 8])
+def test_attention_strip_kernel_16bit(env, tmp_path, waves):
+    """The register-strip kernel in float16 / bfloat16 (AP_ATTN_IMPL=strip, its 8-wave form with AP_ATTN_WAVES=8; both are read
+    once per process, hence one fresh child): the width-64 cases of at most 288 tokens under the strip kernel's bound,
+    B = sum p |v| (it sums the unrounded weights).  That the switch took effect shows in the bits: the tiled kernel's differ."""
+    from tests.attention_strip_child import run_case, strip_cases
+    _lib, lib, dev, stream = env
+    path = tmp_path / "strip.pt"
+    child_env = dict(os.environ, AP_ATTN_IMPL="strip")
+    child_env.pop("AP_ATTN_WAVES", None)
+    if waves == 8:
+        child_env["AP_ATTN_WAVES"] = "8"
+    res = subprocess.run([sys.executable, "-m", "tests.attention_strip_child", str(path)], capture_output=True, text=True, env=child_env,
+                         cwd=ROOT, timeout=600)
+    assert res.returncode == 0 and "ok" in res.stdout, res.stdout[-1500:] + res.stderr[-3000:]
+    got = torch.load(path)
+    refs = _strip_references()
+    assert set(got) == set(refs) and len(refs) == 90
+    _verify("attention", [(cid, {"out": got[cid]}, refs[cid]) for cid in refs])
+    if "AP_ATTN_IMPL" not in os.environ:
+        differ = sum(not R.same_bits(got[case.id], run_case(_lib, lib, dev, stream, case.args)) for case in strip_cases() if case.args["tokens"] == 197)
+        assert differ > 0, "the child's outputs equal the tiled kernel's bit for bit: the strip kernel did not run"
+
+
+@pytest.mark.parametrize("dt,hd,tokens", [(torch.float16, 64, 257), (torch.bfloat16, 96, 385), (torch.float16, 128, 513)], ids=str)
+def test_attention_bits_do_not_depend_on_the_batch(env, dt, hd, tokens):
+    """With more than one workgroup per (image, head): a head alone (n = 1, heads = 1) gives bit for bit what it gives as any of
+    the nine units of (3, 3) -- the tiled kernel's arithmetic per query depends on neither n, heads nor the unit's place."""
+    from tests.attention_strip_child import run_case
+    _lib, lib, dev, stream = env
+    case = next(c for c in R.cases("attention", dtypes=(dt,), widths=(hd,)) if c.args["tokens"] == tokens and c.args["n"] == 3)
+    a = case.args
+    whole = run_case(_lib, lib, dev, stream, a).view(3, tokens, 3, hd)
+    qkv = a["qkv"].view(3, tokens, 3, 3, hd)
+    for img, head in ((0, 0), (1, 2), (2, 1), (2, 2)):
+        alone = dict(a, n=1, heads=1, qkv=qkv[img, :, :, head].reshape(tokens, 3 * hd).contiguous())
+        assert R.same_bits(run_case(_lib, lib, dev, stream, alone), whole[img, :, head].contiguous()), (case.id, img, head)
 
 
 # ----------------------------------------------------------------------------- rope, swiglu
@@ -369,6 +438,36 @@ def test_attention_scaled_error_paths(env):
                  (1, x.data_ptr(), out.ptr(), 1, 4, 1, 64, 0.0), (1, x.data_ptr(), out.ptr(), 1, 4, 1, 64, -1.0),
                  (1, x.data_ptr(), out.ptr(), 1, 4, 1, 64, float("nan")), (1, x.data_ptr(), out.ptr(), 1, 4, 1, 64, float("inf"))):
         _refused(lib, "ap_attention_scaled", call(*args), out)
+
+
+def test_attention_abi_refusals(env):
+    """What ap_attention and ap_attention_scaled share: both refuse, before any launch, a pointer that is not 16-byte aligned
+    (float32 needs no more: the strip kernel's widest access is 16 bytes), an unknown dtype, n < 0, tokens or heads that are
+    not positive, and a 16-bit image whose rows a 32-bit offset cannot address; float32 beyond 288 tokens is
+    AP_ERR_UNSUPPORTED; n = 0 is an empty launch.  Nothing of it touches the output."""
+    _lib, lib, dev, stream = env
+    x = torch.zeros(8192, device=dev, dtype=torch.float16)
+    out = Guarded((4, 128), torch.float16, dev)
+    p, o = x.data_ptr(), out.ptr()
+    entries = (("ap_attention", lambda *a: lib.ap_attention(*a, stream)),
+               ("ap_attention_scaled", lambda *a: lib.ap_attention_scaled(*a, 0.125, stream)))
+    for name, call in entries:
+        #            dtype qkv out n tokens heads head_dim
+        for args in ((1, None, o, 1, 4, 1, 64), (1, p, None, 1, 4, 1, 64), (1, p + 2, o, 1, 4, 1, 64), (1, p + 8, o, 1, 4, 1, 64),
+                     (1, p, o + 2, 1, 4, 1, 64), (1, p, o + 8, 1, 4, 1, 64), (2, p + 8, o, 1, 4, 1, 128), (0, p + 8, o, 1, 4, 1, 64),
+                     (0, p + 4, o, 1, 4, 1, 64), (0, p, o + 8, 1, 4, 1, 64), (3, p, o, 1, 4, 1, 64), (-1, p, o, 1, 4, 1, 64),
+                     (1, p, o, -1, 4, 1, 64), (0, p, o, -1, 4, 1, 64), (1, p, o, 1, 0, 1, 64), (1, p, o, 1, -4, 1, 64), (1, p, o, 1, 4, 0, 64),
+                     (1, p, o, 1, 4, -1, 64), (1, p, o, 1, 4, 1, 32), (1, p, o, 1, 4, 1, 80), (0, p, o, 1, 4, 1, 96), (0, p, o, 1, 4, 1, 128),
+                     (1, p, o, 1, 65536, 128, 128), (2, p, o, 1, 65536, 128, 128), (1, p, o, 0, 65536, 128, 128)):    # rows past 4 GiB
+            _refused(lib, name, call(*args), out)
+        for tokens in (289, 12000):                                        # float32: the strip kernel holds 288 tokens
+            assert call(0, p, o, 1, tokens, 1, 64) == -4 and b"288" in lib.ap_last_error(), (name, tokens)
+            torch.cuda.synchronize()
+            assert out.untouched(), name
+        for dtype in (0, 1, 2):                                            # n = 0: nothing to do, nothing written
+            assert call(dtype, p, o, 0, 4, 1, 64) == 0, (name, dtype)
+        torch.cuda.synchronize()
+        assert out.untouched(), name
 
 
 def test_attention_cls_error_paths(env):

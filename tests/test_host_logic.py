@@ -397,6 +397,26 @@ def test_transform_resize_table():
     assert TRANSFORM_RESIZE["uni_v1"] == (224, "bicubic") and TRANSFORM_RESIZE["conch_v1"] == (448, "bicubic")
 
 
+# ----------------------------------------------------------------------------- attention: what the host refuses
+def test_attention_entry_points_refuse_on_the_host_before_any_launch():
+    """ap_attention and ap_attention_scaled decide every refusal on the host, in front of the first HIP call: on a machine
+    without a GPU each bad call returns AP_ERR_INVALID with the entry point's name (a launch would have come back as
+    AP_ERR_HIP), float32 beyond 288 tokens AP_ERR_UNSUPPORTED, and n = 0 AP_OK.  The pointers are made up: nothing reads them."""
+    from atlaspatch_amd import _lib
+    lib = _lib.load()
+    p, o = 0x10000, 0x20000
+    for name, call in (("ap_attention", lambda *a: lib.ap_attention(*a, None)), ("ap_attention_scaled", lambda *a: lib.ap_attention_scaled(*a, 0.125, None))):
+        #            dtype qkv out n tokens heads head_dim
+        for args in ((1, None, o, 1, 4, 1, 64), (1, p, None, 1, 4, 1, 64), (1, p + 2, o, 1, 4, 1, 64), (2, p + 8, o, 1, 4, 1, 96), (0, p + 8, o, 1, 4, 1, 64),
+                     (1, p, o + 8, 1, 4, 1, 128), (0, p, o + 4, 1, 4, 1, 64), (3, p, o, 1, 4, 1, 64), (-1, p, o, 1, 4, 1, 64), (1, p, o, -1, 4, 1, 64),
+                     (0, p, o, -1, 4, 1, 64), (1, p, o, 1, 0, 1, 64), (1, p, o, 1, 4, 0, 64), (1, p, o, 1, 4, 1, 80), (0, p, o, 1, 4, 1, 128),
+                     (1, p, o, 1, 65536, 128, 128), (2, p, o, 0, 65536, 128, 128)):
+            assert call(*args) == -1 and name.encode() in lib.ap_last_error(), (name, args, lib.ap_last_error())
+        assert call(0, p, o, 1, 289, 1, 64) == -4 and b"288" in lib.ap_last_error()
+        for dtype in (0, 1, 2):
+            assert call(dtype, p, o, 0, 4, 1, 64) == 0
+
+
 # ----------------------------------------------------------------------------- native host tile sources of the ring
 def test_host_synth_tiles_equal_the_numpy_renderer():
     """ap_host_synth_tiles (the synthetic slide's native 'decoder' behind read_tiles_into) == render_region bit for bit,

@@ -9,7 +9,7 @@ import torch
 
 from tests import vit_ops_reference as R
 
-MUTATIONS = {"attention_cls": R.ATTN_MUTATIONS, "attn_pool": R.ATTN_MUTATIONS, "rope": R.ROPE_MUTATIONS, "swiglu": R.SWIGLU_MUTATIONS,
+MUTATIONS = {"attention": R.FULL_MUTATIONS, "attention_cls": R.ATTN_MUTATIONS, "attn_pool": R.ATTN_MUTATIONS, "rope": R.ROPE_MUTATIONS, "swiglu": R.SWIGLU_MUTATIONS,
              "add2_layernorm": R.LN_MUTATIONS, "fold_ln": R.FOLD_LN_MUTATIONS, "fold_ls": (), "cls_stream": R.CLS_MUTATIONS,
              "cls_exact_update": R.CLS_MUTATIONS, "rowstats_finalize_cls": R.FIN_MUTATIONS}
 
@@ -47,6 +47,49 @@ def test_float32_evaluation_passes_and_every_mutation_is_rejected(op):
             # that a constant cannot stay loose after the inputs changed
             assert 0.67 * recorded <= value <= 1.5 * recorded, f"{key}: the float32 evaluation measures {value:.3f}: record it"
     assert (op + "_hot" in R.K_OP) == (measured_hot > 0)
+
+
+@pytest.mark.parametrize("kernel", ["tiled", "strip"])
+def test_attention_rounded_weights_model_fits_the_bound(kernel):
+    """A correct 16-bit kernel fits: float32 scores, keys walked in tiles of 64, weights rounded to T, row sums of the rounded
+    weights (tiled kernel) or of the unrounded ones (register-strip kernel) -- with the coefficient of u(T) B at 1.  Without
+    the B term the same model is refused: the term is needed, and it is not slack.  Under the strip kernel's B every listed
+    mistake is refused as well (the parametrised test above holds the tiled kernel's)."""
+    worst, without, count = 0.0, 0.0, 0
+    for case in R.cases("attention", dtypes=R.HALF, **({"kernel": "strip", "widths": (64,)} if kernel == "strip" else {})):
+        count += 1
+        o = R.ref_attention(case.args)["out"]
+        got = R.model_attention(case.args)
+        k = R.k_of("attention", o)
+        bad = R.failures(got, o, k)
+        err = (got.double() - o.value).abs()
+        worst = max(worst, float((err / R.tolerance(o, k)).max()))
+        without = max(without, float((err / (R.tolerance(o, k) - o.weight_rounding)).max()))
+        assert bad == 0, f"{case.id}: the rounded-weights model fails the check ({bad} elements)"
+        if kernel == "strip":
+            for m in case.mutations:
+                wrong = R.ref_attention(case.args, torch.float64, m)["out"].value.to(o.dtype)
+                assert R.failures(wrong, o, k) > 0, f"{case.id}: mutation {m} passes under the strip kernel's bound"
+    print(f"attention, {kernel} model: {count} cases, worst |model - ref64| / bound = {worst:.3f}; without the B term {without:.1f}")
+    assert count > 0 and worst <= 1.0 < without
+
+
+def test_attention_cases_reach_every_branch():
+    """The shapes name every last-tile body, ring depth, staging wrap and deal of query blocks the tiled kernel has, both
+    shapes of the unit walk, and a rescale staircase at each width that defers, rescales and rescales on a partial last tile."""
+    tokens = set(R.FULL_TOKENS)
+    left = {T - (T - 1) // 64 * 64 for T in tokens}
+    assert {1, 16, 17, 32, 33, 63, 64} <= left                             # NS = 1 / 2 / 4 at their limits
+    assert {1, 2, 3, 4} <= {(T + 63) // 64 for T in tokens} and {T for T in tokens if (T + 63) // 64 % 4 == 3} >= {129, 191, 192, 385, 448}
+    assert {((T + 31) // 32 + 7) // 8 for T in tokens} == {1, 2, 3, 4}
+    assert [R.full_last_part_row0(T) // 32 for T in (257, 513, 785)] == [5, 12, 19]      # 5 + 4, 6 + 6 + 5, 7 + 6 + 6 + 6
+    for hd in (64, 96, 128):
+        ids = [c.id for c in R.cases("attention", dtypes=(torch.bfloat16,), widths=(hd,), max_tokens=160)]
+        assert any("stair5.0+6.0" in i for i in ids) and any(i.endswith("stair5.0") for i in ids) and any("-n3-h3" in i for i in ids)
+        if hd == 96:
+            assert any("-w80" in i for i in ids) and any("-w80" not in i for i in ids)
+    scales = {(c.args["hd"], round(c.args["scale"] * math.sqrt(c.args["hd"]), 3)) for c in R.cases("attention", dtypes=(torch.float16,), max_tokens=33)}
+    assert {(64, 1.0), (64, 0.8), (128, 1.0), (128, 1.25)} <= scales
 
 
 def test_add2_layernorm_strides_are_tied_to_nothing():

@@ -20,6 +20,12 @@ The softmax operators carry two constants: the float32 error of a score s is ~|s
 so the one head per case whose scores reach 95 (it proves the maximum is subtracted before the exponential) is measured on
 its own ("<op>_hot", the elements under ``Out.hot``) and every other head keeps the bound of ordinary scores.
 
+Full attention ("attention": ap_attention / ap_attention_scaled) rounds its softmax weights to T in front of the P V MFMA and
+adds ``Out.weight_rounding`` = u(T) B (+ tokens 2^-25 A in float16) to the bound.  Which B: the tiled kernel sums the ROUNDED weights
+(attention_flash.hip, ``l_run = psum8<T>(l_run, pf)``), so its output is a convex combination of the v rows and
+B = sum_t p_t |v_t - ref64|; the 16-bit register-strip kernel sums the UNROUNDED ones (attention.hip, ``sum += p``), so
+B = sum_t p_t |v_t|; the float32 strip kernel rounds nothing and has neither.  The derivation stands in front of ref_attention.
+
 K_OP holds, per operator, (measured, constant): `measured` is max |ref32 - ref64| / (2^-24 A) over the operator's cases with the
 formula evaluated in torch float32 on the CPU, `constant` = 4 x measured rounded up (the GPU's summation order and fast
 exponential are not torch's).  tests/test_vit_ops_reference.py re-measures and holds the table to that rule; the constants were
@@ -41,6 +47,8 @@ ALL = (torch.float16, torch.bfloat16, torch.float32)
 K_OP = {
     "attention_cls": (33.515, 135.0),           # scores up to ~10, up to 1370 terms
     "attention_cls_hot": (188.109, 753.0),      # the heads whose scores reach 95: the float32 error of a score is ~95 x 2^-24
+    "attention": (64.820, 260.0),               # full attention: scores up to ~30 on the rescale staircases, up to 785 terms
+    "attention_hot": (287.858, 1152.0),
     "attn_pool": (15.240, 61.0),
     "attn_pool_hot": (195.601, 783.0),
     "rope": (1.977, 8.0),
@@ -60,6 +68,7 @@ class Out:
     A: object = None             # tensor like value, or None: the whole output is exact
     exact: object = None         # bool mask of the elements that must equal T(value) bit for bit
     hot: object = None           # bool mask of the elements bounded with K_OP["<op>_hot"] instead of K_OP["<op>"]
+    weight_rounding: object = None   # tensor like value: a further absolute term of the bound (full attention: u(T) B, see there)
 
 
 @dataclass
@@ -79,6 +88,12 @@ def same_bits(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and torch.equal(bits(a), bits(b))
 
 
+def tolerance(out, k):
+    """The bound of every element of the float64 evaluation `out` (A is not None) with the constant(s) k."""
+    tol = U[out.dtype] * out.value.abs() + FLOOR[out.dtype] + k * 2.0 ** -24 * out.A.double()
+    return tol if out.weight_rounding is None else tol + out.weight_rounding.double()
+
+
 def failures(got, out, k):
     """Number of elements of `got` (of type out.dtype) the check refuses against the float64 evaluation `out`."""
     assert got.dtype == out.dtype and got.shape == out.value.shape, (got.dtype, out.dtype, got.shape, out.value.shape)
@@ -87,7 +102,7 @@ def failures(got, out, k):
         return int((bits(got) != bits(want_exact)).sum())
     assert out.value.dtype == torch.float64
     ref = out.value
-    tol = U[out.dtype] * ref.abs() + FLOOR[out.dtype] + k * 2.0 ** -24 * out.A.double()
+    tol = tolerance(out, k)
     bad = ~((got.double() - ref).abs() <= tol)                      # a NaN in `got` is a failure
     if out.exact is not None:
         bad = torch.where(out.exact, bits(got) != bits(want_exact), bad)
@@ -263,6 +278,284 @@ def ref_attention_scaled(qkv, n, tokens, heads, hd, width, scale, fd=torch.float
 
 
 ATTENTION_SCALED_TOL = {torch.float16: 4e-3, torch.bfloat16: 3e-2, torch.float32: 2e-5}     # test_attention_vs_torch's, |out| <= 6
+
+
+# ----------------------------------------------------------------------------- full self-attention, per element
+# ap_attention / ap_attention_scaled: out = softmax(scale q k^T) v per (image, head) on packed q | k | v rows.
+#
+# Both 16-bit kernels round the softmax weights to T before the P V MFMA, which no other softmax operator here does, so the
+# bound carries one more term per element (Out.weight_rounding):
+#
+#     |got - ref64| <= u(T) |ref64| + floor(T) + u(T) B + k_op 2^-24 A   (+ tokens 2^-25 A for float16)
+#
+# With p~_t = p_t (1 + d_t), |d_t| <= u(T), the rounded weights, and p normalised in float64:
+#   * tiled kernel (attention_flash.hip): the row sum is taken from the ROUNDED weights -- `l_run = psum8<T>(l_run, pf)` in
+#     pv_step, pf being the very fragment the MFMA multiplies -- so out = sum p~ v / sum p~ is a convex combination of the v rows
+#     and out - ref = sum p d (v - ref) / sum p~: to first order B = sum_t p_t |v_t - ref64|.  A deferred rescale changes
+#     nothing in this: the weights are then taken against an older maximum, up to 2^8 as operands, with the same relative
+#     rounding, and numerator and row sum are scaled alike afterwards.
+#   * 16-bit register-strip kernel (attention.hip): `sum += p` adds the UNROUNDED float32 weights while `pf[e] = (T)st[kt][..]`
+#     feeds the rounded ones to the MFMA: out - ref = sum p d v / sum p, B = sum_t p_t |v_t|.
+#   * float32 strip kernel: rounds nothing; no B and no u term.
+# float16 only: a weight below 2^-14 is subnormal as an operand and has an absolute error of up to 2^-25 instead; the final
+# row sum is >= 1 (the key that last set the running maximum has weight exactly 1), hence tokens 2^-25 A.
+# The coefficient of u(T) B is 1 by this derivation; model_attention (the "rounded-weights model": float32 scores, keys
+# walked in tiles of 64 with the kernel's deferred rescale, weights rounded to T) has to fit under it on every case.
+#
+# Inputs: unstructured noise cannot tell a dropped key from rounding, so every query is dominated by chosen keys.  Per (image,
+# head) a unit direction e; q_i = a_i e / sqrt(scale) + 0.3 noise, k_t = c_t e / sqrt(scale) + 0.3 noise with the noise
+# orthogonal to e (score = a_i c_t + small noise, so a staircase's steps are what the table says), v = 1.5 noise.  a_i in
+# [1, 1.25] differs per query: a neighbour's query row moves the output.  c_t = 8 / 7 on two "leader" keys whose placement
+# differs per (image, head) and case (FULL placements below), 0 elsewhere.  Staircase cases: tile j's first and last valid
+# key lead with 8 + b_j / 7 + b_j, b rising by the given steps in natural-log units, a_i = 1 (mixed: a_i in [1, 1.25], so
+# that only some rows of a 32-query block grow by more than the kernel's deferral threshold 8 ln 2 = 5.545).  The last
+# (image, head) of a case with more than one reaches scores of 95.
+FULL_TOKENS = (1, 16, 17, 32, 33, 63, 64, 65, 128, 129, 191, 192, 193, 197, 224, 225, 256, 257, 288, 289, 385, 448, 513, 785)
+FULL_F32_MAX = 288
+#              tokens, steps from tile to tile, mixed, tile whose rescale `rescale_skipped_upper_blocks` skips (0: none), stale
+FULL_STAIRS = ((128, (5.0,), False, 0, False),                 # deferred: weights up to e^5 as 16-bit operands
+               (128, (6.0,), False, 1, False),                 # rescaled
+               (192, (5.0, 5.0), False, 2, True),              # the second step rescales against the max that was NOT raised
+               (140, (5.0, 6.0), False, 2, False),             # the rescale falls on the last tile, 12 keys: NS = 1
+               (152, (5.0, 6.0), False, 2, False),             # ... 24 keys: NS = 2
+               (256, (4.8, 4.8, 4.8), True, 2, False),         # only some rows of a wave cross the threshold
+               (257, (6.0, 5.0, 5.0, 6.0), False, 4, False))   # two parts; rescale, deferral, rescale, rescale on a 1-key tile
+FULL_MUTATIONS = ("first_key_dropped", "last_key_dropped", "seam_key_dropped", "seam_key_doubled", "padding_counted", "query_row_plus_1",
+                  "neighbour_head_v", "neighbour_image_k", "wrong_scale", "octet0", "rescale_skipped_upper_blocks",
+                  "stale_max_after_deferral", "last_part_rows_zero")
+
+
+def full_last_part_row0(tokens):
+    """First query row of the last of the workgroups that share an (image, head): 32-query blocks dealt evenly, 8 per part."""
+    nqb = (tokens + 31) // 32
+    parts = (nqb + 7) // 8
+    return ((parts - 1) * (nqb // parts) + min(parts - 1, nqb % parts)) * 32
+
+
+def _full_placements(T):
+    """Where the two leader keys may sit: the ends, the tile seams, the 32-key and 16-key seams, the last valid keys."""
+    if T == 1:
+        return [(0,)]
+    m = (T - 1) // 64
+    want = [(0, T - 1), (63, 64), (64 * m - 1, 64 * m), (31, 32), (15, 16), (47, 48), (T - 2, T - 1)]
+    got = []
+    for lo, hi in want:
+        if 0 <= lo < hi < T and (lo, hi) not in got:
+            got.append((lo, hi))
+    return got
+
+
+def _full_inputs(g, dt, n, T, H, hd, width, scale, ci, stair, mixed):
+    """-> qkv [n * T, 3 * H * hd] in dt, c [n, T, H] (the leaders' coefficients, 0 elsewhere)."""
+    e = _randn(g, n, 1, H, hd)
+    e[..., width:] = 0
+    e = e / e.norm(dim=-1, keepdim=True)
+
+    def noise():
+        x = _randn(g, n, T, H, hd)
+        x[..., width:] = 0
+        return 0.3 * (x - (x * e).sum(-1, keepdim=True) * e)
+
+    a = 1.0 + 0.25 * torch.rand(n, T, H, generator=g)
+    if stair is not None and not mixed:
+        a = torch.ones(n, T, H)
+    c = torch.zeros(n, T, H)
+    P = _full_placements(T)
+    for img in range(n):
+        for h in range(H):
+            hot = img == n - 1 and h == H - 1 and n * H > 1
+            big = (76.0, 75.0) if hot else (8.0, 7.0)            # a_i <= 1.25: scores up to 95
+            if stair is None or hot:
+                keys = P[(ci + img * H + h) % len(P)]
+                order = big if (img + h) % 2 == 0 else big[::-1]
+                for key, val in zip(keys, order):
+                    c[img, key, h] = val
+            else:
+                b = 0.0
+                for j in range((T + 63) // 64):
+                    b += stair[j - 1] if j else 0.0
+                    lo, hi_ = 64 * j, min(64 * j + 63, T - 1)
+                    c[img, hi_, h] = 7.0 + b
+                    c[img, lo, h] = 8.0 + b
+    q = a[..., None] * e / math.sqrt(scale) + noise()
+    k = c[..., None] * e / math.sqrt(scale) + noise()
+    v = 1.5 * _randn(g, n, T, H, hd)
+    v[..., width:] = 0
+    return torch.stack([q, k, v], 2).reshape(n * T, 3 * H * hd).to(dt), c
+
+
+def _full_seam_mask(c):
+    """[n, H, T]: per (image, head) the first leader that sits on a tile seam (key 64 j - 1 or 64 j)."""
+    n, T, H = c.shape
+    t = torch.arange(T)
+    seam = (c.permute(0, 2, 1) > 0) & (((t % 64 == 63) & (t < T - 1)) | ((t % 64 == 0) & (t > 0)))
+    first = seam & (seam.int().cumsum(-1) == 1)
+    return first
+
+
+def _full_applicable(n, T, H, c, stair, mixed, step_tile, stale):
+    lead = c.permute(0, 2, 1) > 0
+    m = ["octet0", "last_part_rows_zero"]
+    if T >= 2:
+        m.append("wrong_scale")
+        if stair is None and bool(lead[..., 0].any()):           # (a staircase's lower leaders weigh e^-5 and less)
+            m.append("first_key_dropped")
+        if bool(lead[..., T - 1].any()):
+            m.append("last_key_dropped")
+            if T % 64:
+                m.append("padding_counted")
+        if stair is None and bool(_full_seam_mask(c).any()):
+            m += ["seam_key_dropped", "seam_key_doubled"]
+        if stair is None or mixed:
+            m.append("query_row_plus_1")
+        if n >= 2:
+            m.append("neighbour_image_k")
+    if H >= 2:
+        m.append("neighbour_head_v")
+    if step_tile:
+        m.append("rescale_skipped_upper_blocks")
+    if stale:
+        m.append("stale_max_after_deferral")
+    return tuple(m)
+
+
+def _full_qkv(a, fd):
+    n, T, H, hd, width = a["n"], a["tokens"], a["heads"], a["hd"], a["width"]
+    x = a["qkv"].to(fd).view(n, T, 3, H, hd)[..., :width]
+    return (x[:, :, i].transpose(1, 2) for i in range(3))               # each [n, H, T, width]
+
+
+def _full_pack(out, a, fd):
+    """[n, H, T, width] -> [n * T, H * hd], the channels >= width zero."""
+    n, T, H, hd, width = a["n"], a["tokens"], a["heads"], a["hd"], a["width"]
+    full = torch.zeros(n, T, H, hd, dtype=fd)
+    full[..., :width] = out.transpose(1, 2)
+    return full.reshape(n * T, H * hd)
+
+
+def ref_attention(a, fd=torch.float64, mutate=None, kernel=None):
+    """kernel: "tiled", "strip" (16-bit) or "strip32" -- which B the bound carries; default: the one the case was built for."""
+    dt, n, T, H, hd, width = a["dtype"], a["n"], a["tokens"], a["heads"], a["hd"], a["width"]
+    kernel = kernel or a["kernel"]
+    scale = float(np.float32(a["scale"]))
+    q, k, v = _full_qkv(a, fd)
+    w = torch.ones(n, H, 1, T, dtype=fd)                                # how often each key counts
+    if mutate == "first_key_dropped":
+        w[..., 0] = 0
+    elif mutate == "last_key_dropped":
+        w[..., T - 1] = 0
+    elif mutate in ("seam_key_dropped", "seam_key_doubled"):
+        w[:, :, 0][_full_seam_mask(a["c"])] = 0.0 if mutate == "seam_key_dropped" else 2.0
+    elif mutate == "padding_counted":
+        w[..., T - 1] += (-T) % 64                                      # the masked slots of the last tile hold the last valid row
+    elif mutate == "query_row_plus_1":
+        q = torch.roll(q, -1, 2)
+    elif mutate == "neighbour_head_v":
+        v = torch.roll(v, -1, 1)
+    elif mutate == "neighbour_image_k":
+        k = torch.roll(k, -1, 0)
+    elif mutate == "wrong_scale":
+        scale = float(np.float32(1.0 / math.sqrt(80.0 if abs(scale - 1.0 / math.sqrt(hd)) < 1e-6 else hd)))
+    elif mutate == "octet0":
+        k, v = k.clone(), v.clone()
+        k[..., 8:16] = k[..., 0:8]
+        v[..., 8:16] = v[..., 0:8]
+    s = q @ k.transpose(-1, -2) * torch.tensor(scale, dtype=fd)         # [n, H, T, T]
+    p = torch.exp(s - s.amax(-1, keepdim=True))
+    pw = p * w
+    if mutate == "stale_max_after_deferral":
+        # tile 1 was deferred: the accumulators still stand against tile 0's maximum when tile 2 raises it; rescaling them as if
+        # they stood against tile 1's leaves tiles 0 and 1 too heavy by the deferred step = tile 2 too light by it
+        pw = pw.clone()
+        pw[..., 128:] *= torch.exp(s[..., :64].amax(-1, keepdim=True) - s[..., :128].amax(-1, keepdim=True))
+    den = pw.sum(-1, keepdim=True)
+    num = pw @ v
+    if mutate == "rescale_skipped_upper_blocks":
+        k0 = 64 * a["step_tile"]
+        alpha = torch.exp(s[..., :k0].amax(-1, keepdim=True) - s[..., :k0 + 64].amax(-1, keepdim=True))
+        old = pw[..., :k0] @ v[:, :, :k0]
+        num[..., 32:] += old[..., 32:] * (1.0 / alpha - 1.0)            # the output blocks it >= 1 keep their old weight
+    out = num / den
+    if mutate == "last_part_rows_zero":
+        out = out.clone()
+        out[:, :, full_last_part_row0(T):] = 0
+    A = v.abs().amax(dim=(2, 3))[:, None, :, None].expand(n, T, H, hd).reshape(n * T, H * hd).double()
+    hot = (s.abs().amax(dim=(2, 3)) > ATTN_HOT_SCORE)[:, None, :, None].expand(n, T, H, hd).reshape(n * T, H * hd)
+    assert (kernel == "strip32") == (dt == torch.float32)
+    rounding = None                                                     # only the yardstick carries the term
+    if mutate is None and fd == torch.float64 and dt in HALF:
+        pn = p / den
+        if kernel == "tiled":
+            B = torch.empty_like(out)
+            blk = max(1, 2_000_000 // (n * H * T * width))
+            for i0 in range(0, T, blk):                                 # no T x T x width tensor
+                i1 = min(T, i0 + blk)
+                B[:, :, i0:i1] = (pn[:, :, i0:i1, :, None] * (v[:, :, None] - out[:, :, i0:i1, None]).abs()).sum(3)
+        else:
+            assert kernel == "strip"
+            B = pn @ v.abs()
+        rounding = U[dt] * _full_pack(B, a, fd)
+        if dt == torch.float16:
+            rounding = rounding + T * 2.0 ** -25 * A
+    return {"out": Out(_full_pack(out, a, fd), dt, A, hot=hot, weight_rounding=rounding)}
+
+
+def model_attention(a, kernel=None):
+    """The rounded-weights model, a CPU stand-in for a correct 16-bit kernel: float32 scores, the keys walked in tiles of 64
+    with the running maximum raised only when a row of the 32-query block grew by more than 2^8 (tiled) or the whole strip
+    at once (strip), weights rounded to T for the product, row sums of the rounded (tiled) or unrounded (strip) weights."""
+    dt, T = a["dtype"], a["tokens"]
+    kernel = kernel or a["kernel"]
+    q, k, v = _full_qkv(a, torch.float32)
+    c = torch.tensor(float(np.float32(a["scale"])) * 1.4426950408889634, dtype=torch.float32)
+    s = q @ k.transpose(-1, -2)
+    if kernel == "strip":
+        p = torch.exp2(s * c - s.amax(-1, keepdim=True) * c)
+        return _full_pack((p.to(dt).float() @ v) * (1.0 / p.sum(-1, keepdim=True)), a, torch.float32).to(dt)
+    m_run = torch.full_like(s[..., :1], -math.inf)
+    l_run = torch.zeros_like(m_run)
+    O = torch.zeros_like(q)
+    block = torch.arange(T) // 32
+    for j0 in range(0, T, 64):
+        sj = s[..., j0:j0 + 64]
+        mx = sj.amax(-1, keepdim=True)
+        grew = (mx - m_run) * c > 8.0
+        raise_ = torch.stack([grew[:, :, b0:b0 + 32].any(2) for b0 in range(0, T, 32)], 2)[:, :, block]
+        m_new = torch.where(raise_, torch.maximum(m_run, mx), m_run)
+        alpha = torch.exp2((m_run - m_new) * c)
+        m_run, l_run, O = m_new, l_run * alpha, O * alpha
+        pj = torch.exp2(sj * c - m_run * c).to(dt).float()
+        l_run = l_run + pj.sum(-1, keepdim=True)
+        O = O + pj @ v[:, :, j0:j0 + 64]
+    return _full_pack(O * (1.0 / l_run), a, torch.float32).to(dt)
+
+
+def _cases_attention(dtypes=ALL, widths=(64, 96, 128), kernel=None, max_tokens=None):
+    """kernel "strip": the cases the 16-bit register-strip kernel takes (width 64, <= 288 tokens), bounded with its B."""
+    for dt, hd in itertools.product(dtypes, widths):
+        if dt == torch.float32 and hd != 64:
+            continue
+        kern = kernel or ("strip32" if dt == torch.float32 else "tiled")
+        limit = max_tokens or (FULL_F32_MAX if kern != "tiled" else 10 ** 9)
+        plain = [(T, shape, None, False, 0, False) for T, shape in itertools.product(FULL_TOKENS, ((1, 1), (3, 3)))]
+        stairs = [(T, (2, 2), steps, mixed, tile, stale) for T, steps, mixed, tile, stale in FULL_STAIRS]
+        for ci, (T, (n, heads), stair, mixed, step_tile, stale) in enumerate(plain + stairs):
+            if T > limit:
+                continue
+            if T == 785 and n == 3:
+                n = 2
+            if hd == 96:                                                  # two cases in three: 80-wide heads stored 96 wide
+                width = 96 if ci % 3 == 0 else 80
+                scale = 1.0 / math.sqrt(width)
+            else:                                                         # every other case: a scale that is not 1 / sqrt(hd)
+                width, scale = hd, (1.0 if ci % 2 else (0.8 if hd == 64 else 1.25)) / math.sqrt(hd)
+            g = _seed("attention", dt, hd, T, n, heads, stair)
+            qkv, c = _full_inputs(g, dt, n, T, heads, hd, width, scale, ci, stair, mixed)
+            name = f"{dt}-hd{hd}-t{T}-n{n}-h{heads}" + ("-w80" if width != hd else "") + \
+                   ("" if stair is None else "-stair" + "+".join(str(s) for s in stair))
+            yield Case("attention", name, dict(dtype=dt, qkv=qkv, c=c, n=n, tokens=T, heads=heads, hd=hd, width=width, scale=scale,
+                                               kernel=kern, step_tile=step_tile),
+                       _full_applicable(n, T, heads, c, stair, mixed, step_tile, stale))
 
 
 # ----------------------------------------------------------------------------- rotary embedding
@@ -688,10 +981,10 @@ def _cases_rowstats_finalize_cls():
             yield Case("rowstats_finalize_cls", f"{dt}-d{dim}-n{n}-t{T}-r{rows}", a, FIN_MUTATIONS if n else ())
 
 
-REFS = {"attention_cls": ref_attention_cls, "attn_pool": ref_attn_pool, "rope": ref_rope, "swiglu": ref_swiglu,
+REFS = {"attention": ref_attention, "attention_cls": ref_attention_cls, "attn_pool": ref_attn_pool, "rope": ref_rope, "swiglu": ref_swiglu,
         "add2_layernorm": ref_add2_layernorm, "fold_ln": ref_fold_ln, "fold_ls": ref_fold_ls, "cls_stream": ref_cls_stream,
         "cls_exact_update": ref_cls_exact_update, "rowstats_finalize_cls": ref_rowstats_finalize_cls}
-CASES = {"attention_cls": _cases_attention_cls, "attn_pool": _cases_attn_pool, "rope": _cases_rope, "swiglu": _cases_swiglu,
+CASES = {"attention": _cases_attention, "attention_cls": _cases_attention_cls, "attn_pool": _cases_attn_pool, "rope": _cases_rope, "swiglu": _cases_swiglu,
          "add2_layernorm": _cases_add2_layernorm, "fold_ln": _cases_fold_ln, "fold_ls": _cases_fold_ls,
          "cls_mean_pool": _cases_cls_mean_pool, "cls_stream": _cases_cls_stream, "cls_exact_update": _cases_cls_exact_update,
          "rowstats_finalize_cls": _cases_rowstats_finalize_cls}
