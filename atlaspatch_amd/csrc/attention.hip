@@ -24,7 +24,7 @@
 // Roofline: MFMA for the two contractions (4*T*T*64 flop per head); HBM traffic = read
 // q,k,v once + write o once = 4 * T * 64 * sizeof(T) bytes per head.
 #include <cstdlib>
-#include "ap_common.h"
+#include "kernel_util.h"
 
 namespace ap {
 namespace {
@@ -47,21 +47,6 @@ template <> __device__ __forceinline__ uint32_t pack2<f16>(f16 a, f16 b) {
 }
 template <> __device__ __forceinline__ uint32_t pack2<bf16>(bf16 a, bf16 b) {
     return (uint32_t)__builtin_bit_cast(uint16_t, a) | ((uint32_t)__builtin_bit_cast(uint16_t, b) << 16);
-}
-
-template <typename T> struct Vec8;
-template <> struct Vec8<f16> { using type = f16x8; using half = f16x4; };
-template <> struct Vec8<bf16> { using type = bf16x8; using half = bf16x4; };
-
-template <typename T>
-__device__ __forceinline__ f32x16 mma16(typename Vec8<T>::type a, typename Vec8<T>::type b, f32x16 c);
-template <>
-__device__ __forceinline__ f32x16 mma16<f16>(f16x8 a, f16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x16 mma16<bf16>(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
 template <typename T, int NKT, int NW>
@@ -94,11 +79,11 @@ void attention_kernel(const T* __restrict__ qkv, T* __restrict__ out, int tokens
         for (int idx = tid; idx < (S::TP / 2) * 8; idx += NT) {
             const int tp = idx >> 3, c = idx & 7;
             const int t0 = tp * 2;
-            typename Vec8<T>::type v0, v1;
+            typename Vec16<T>::type v0, v1;
 #pragma unroll
             for (int e = 0; e < 8; ++e) { v0[e] = (T)0.0f; v1[e] = (T)0.0f; }
-            if (t0 < tokens) v0 = *(const typename Vec8<T>::type*)(Vg + (size_t)t0 * ld + c * 8);
-            if (t0 + 1 < tokens) v1 = *(const typename Vec8<T>::type*)(Vg + (size_t)(t0 + 1) * ld + c * 8);
+            if (t0 < tokens) v0 = *(const typename Vec16<T>::type*)(Vg + (size_t)t0 * ld + c * 8);
+            if (t0 + 1 < tokens) v1 = *(const typename Vec16<T>::type*)(Vg + (size_t)(t0 + 1) * ld + c * 8);
 #pragma unroll
             for (int e = 0; e < 8; ++e)
                 *(uint32_t*)(Vt + (c * 8 + e) * S::vRowB + tp * 4) = pack2<T>(v0[e], v1[e]);
@@ -128,7 +113,7 @@ void attention_kernel(const T* __restrict__ qkv, T* __restrict__ out, int tokens
 
         f32x16 st[NKT];
         if constexpr (sizeof(T) == 2) {
-            using V8 = typename Vec8<T>::type;
+            using V8 = typename Vec16<T>::type;
             V8 qf[4];
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) qf[kk] = *(const V8*)(qp + kk * 16 + hi * 8);
@@ -150,7 +135,7 @@ void attention_kernel(const T* __restrict__ qkv, T* __restrict__ out, int tokens
                 }
                 asm volatile("" ::: "memory");
 #pragma unroll
-                for (int kk = 0; kk < 4; ++kk) st[kt] = mma16<T>(kcur[kk], qf[kk], st[kt]);
+                for (int kk = 0; kk < 4; ++kk) st[kt] = Mma32x32<T>::run(kcur[kk], qf[kk], st[kt]);
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) kcur[kk] = knext[kk];
             }
@@ -211,8 +196,8 @@ void attention_kernel(const T* __restrict__ qkv, T* __restrict__ out, int tokens
             for (int e = 0; e < 16; ++e) ot[it][e] = 0.f;
 
         if constexpr (sizeof(T) == 2) {
-            using V8 = typename Vec8<T>::type;
-            using V4 = typename Vec8<T>::half;
+            using V8 = typename Vec16<T>::type;
+            using V4 = typename Vec16<T>::half;
             auto load_v = [&](int s, int it) {
                 const int kt = s >> 1, hf = s & 1;
                 const char* vrow = Vt + (it * 32 + l31) * S::vRowB + (kt * 32 + hf * 16 + hi * 4) * 2;
@@ -230,8 +215,8 @@ void attention_kernel(const T* __restrict__ qkv, T* __restrict__ out, int tokens
                 V8 pf;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) pf[e] = (T)st[kt][hf * 8 + e];
-                ot[0] = mma16<T>(vcur0, pf, ot[0]);
-                ot[1] = mma16<T>(vcur1, pf, ot[1]);
+                ot[0] = Mma32x32<T>::run(vcur0, pf, ot[0]);
+                ot[1] = Mma32x32<T>::run(vcur1, pf, ot[1]);
                 vcur0 = vnext0; vcur1 = vnext1;
             }
         } else {
@@ -259,10 +244,10 @@ void attention_kernel(const T* __restrict__ qkv, T* __restrict__ out, int tokens
                 for (int g4 = 0; g4 < 4; ++g4) {
                     T* dst = op + it * 32 + g4 * 8 + hi * 4;
                     if constexpr (sizeof(T) == 2) {
-                        typename Vec8<T>::half o;
+                        typename Vec16<T>::half o;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] = (T)(ot[it][g4 * 4 + e] * inv);
-                        *(typename Vec8<T>::half*)dst = o;
+                        *(typename Vec16<T>::half*)dst = o;
                     } else {
                         f32x4 o;
 #pragma unroll
@@ -321,13 +306,9 @@ int launch_attention(int dtype, const void* qkv, void* out, int n, int tokens, i
         static const bool strip = [] { const char* e = getenv("AP_ATTN_IMPL"); return e && e[0] == 's'; }();
         if (!strip || tokens > 288 || head_dim != kHD) return launch_attention_flash(dtype, qkv, out, n, tokens, heads, head_dim, scale, stream);
     }
-    switch (dtype) {
-        case AP_F16: return launch_by_len<f16>(qkv, out, n, tokens, heads, scale, stream);
-        case AP_BF16: return launch_by_len<bf16>(qkv, out, n, tokens, heads, scale, stream);
-        case AP_F32: return launch_by_len<float>(qkv, out, n, tokens, heads, scale, stream);
-    }
-    set_error("attention: unknown dtype %d", dtype);
-    return AP_ERR_INVALID;
+    return dispatch_dtype("attention", dtype, [&](auto tag) {
+        return launch_by_len<typename decltype(tag)::type>(qkv, out, n, tokens, heads, scale, stream);
+    });
 }
 
 }  // namespace ap

@@ -40,7 +40,7 @@
 //
 // Roofline: MFMA (4 * T * T * 64 flop per head; padded to 32-query x 64-key tiles);
 // HBM traffic = q, k, v read once + o written once.
-#include "ap_common.h"
+#include "kernel_util.h"
 
 namespace ap {
 namespace {
@@ -51,20 +51,6 @@ constexpr int kNW = 8;                  // waves per workgroup (round 6: five-, 
                                         //   tokens: profiles/r06c_attention.txt -- the eighth wave's share of the staging is worth more
                                         //   than its slot)
 constexpr int kNB = 4;                  // K/V ring buffers (prefetch distance kNB - 1); >= 3 (the epilogue stages through two idle ones)
-
-template <typename T> struct FMma;
-template <> struct FMma<f16> {
-    using Frag = f16x8;
-    static __device__ __forceinline__ f32x16 run(Frag a, Frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct FMma<bf16> {
-    using Frag = bf16x8;
-    static __device__ __forceinline__ f32x16 run(Frag a, Frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-};
 
 // one LDS-DMA load (16 B per lane): LDS[lds_dst + lane * 16] <- base[off]; only s_mov / s_nop besides
 // the load, so SCC is untouched; M0 saved and restored (compiler-reserved)
@@ -112,7 +98,7 @@ __device__ __forceinline__ float half_swap_sum(float v) {
 }
 
 // row sums of P from the ROUNDED operand values (what the P V product multiplies): sum of 8 packed values into f32
-template <typename T> __device__ __forceinline__ float psum8(float acc, typename FMma<T>::Frag pf);
+template <typename T> __device__ __forceinline__ float psum8(float acc, typename Mma32x32<T>::Frag pf);
 template <> __device__ __forceinline__ float psum8<f16>(float acc, f16x8 pf) {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     const u32x4 w = __builtin_bit_cast(u32x4, pf);
@@ -145,7 +131,7 @@ void attention_flash_kernel(const T* __restrict__ qkv, T* __restrict__ out, int 
     constexpr int CPR = RB / 16;                     // 16-byte chunks per row (8, 12 or 16)
     constexpr int kChunks = kTileBytes / 16;         // chunks of one operand tile
     __shared__ __attribute__((aligned(16))) char smem[kNB * 2 * kTileBytes];     // [buf][K | V]
-    using Frag = typename FMma<T>::Frag;
+    using Frag = typename Mma32x32<T>::Frag;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -272,7 +258,7 @@ void attention_flash_kernel(const T* __restrict__ qkv, T* __restrict__ out, int 
 #pragma unroll
             for (int kk = 0; kk < NKK; ++kk) {
                 const Frag kf = *(const Frag*)(buf + kb * 32 * RB + ka[kk]);
-                st[kb] = FMma<T>::run(kf, qf[kk], kk == 0 ? zero16 : st[kb]);
+                st[kb] = Mma32x32<T>::run(kf, qf[kk], kk == 0 ? zero16 : st[kb]);
             }
         }
         if (kLast && (j + 1) * kKV > tokens) {                            // mask keys past the end
@@ -335,7 +321,7 @@ void attention_flash_kernel(const T* __restrict__ qkv, T* __restrict__ out, int 
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
                 const u32x4 f = {va_[it][0], va_[it][1], vb_[it][0], vb_[it][1]};
-                ot[it] = FMma<T>::run(__builtin_bit_cast(Frag, f), pf, ot[it]);
+                ot[it] = Mma32x32<T>::run(__builtin_bit_cast(Frag, f), pf, ot[it]);
             }
         };
         pv_step(IntC<0>{});
@@ -416,13 +402,11 @@ int launch_attention_flash(int dtype, const void* qkv, void* out, int n, int tok
     const int nqb = (tokens + 31) / 32;
     const int parts = (nqb + kNW - 1) / kNW, units = n * heads;
     dim3 grid((unsigned)((units + 7) / 8 * 8 * parts)), block(kNW * 64);
-#define AP_FLASH(T, HD) attention_flash_kernel<T, HD><<<grid, block, 0, stream>>>((const T*)qkv, (T*)out, tokens, heads, parts, units, scale)
-    if (head_dim == 64) { if (dtype == AP_F16) AP_FLASH(f16, 64); else AP_FLASH(bf16, 64); }
-    else if (head_dim == 96) { if (dtype == AP_F16) AP_FLASH(f16, 96); else AP_FLASH(bf16, 96); }
-    else { if (dtype == AP_F16) AP_FLASH(f16, 128); else AP_FLASH(bf16, 128); }
-#undef AP_FLASH
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_half("attention_flash", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        const auto kernel = head_dim == 64 ? attention_flash_kernel<T, 64> : head_dim == 96 ? attention_flash_kernel<T, 96> : attention_flash_kernel<T, 128>;
+        kernel<<<grid, block, 0, stream>>>((const T*)qkv, (T*)out, tokens, heads, parts, units, scale);
+    });
 }
 
 }  // namespace ap

@@ -9,28 +9,10 @@
 // token group of 4), so a wave reads one 128-byte V row per step; the four groups are reduced through LDS.
 // HBM-bound: k and v are read once (2 * tokens * 128 B per head).
 #include <type_traits>
-#include "ap_common.h"
+#include "kernel_util.h"
 
 namespace ap {
 namespace {
-
-template <typename T> struct PoolVec;
-template <> struct PoolVec<f16> { using v8 = f16x8; };
-template <> struct PoolVec<bf16> { using v8 = bf16x8; };
-
-__device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float o = __shfl_xor(v, off, 64);
-        v = is_max ? fmaxf(v, o) : v + o;
-    }
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    const float a = red[0], b = red[1], c = red[2], d = red[3];
-    return is_max ? fmaxf(fmaxf(a, b), fmaxf(c, d)) : (a + b) + (c + d);
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void attn_pool_kernel(const T* __restrict__ kv, const float* __restrict__ q,
@@ -39,7 +21,7 @@ __global__ __launch_bounds__(256) void attn_pool_kernel(const T* __restrict__ kv
     float* scores = sm;
     float* red = sm + ((tokens + 3) & ~3);
     float* part = red + 4;
-    using V8 = typename PoolVec<T>::v8;
+    using V8 = typename Vec16<T>::oct;
     const int img = blockIdx.x / heads, head = blockIdx.x - img * heads;
     const int P = heads * 64;
     const size_t ld = (size_t)2 * P;
@@ -95,9 +77,6 @@ __global__ __launch_bounds__(256) void attn_pool_kernel(const T* __restrict__ kv
 // the probe's projected query is input independent, the host computes it once).  Everything after the query load is the same code.
 // HBM-bound: k and v are read once, 2 * tokens * HD * sizeof(T) bytes per (image, head) (the real model: 1024 tokens, 16 heads
 // stored 96 wide, f16 = 6.3 MB per image; the scores and the query stay in LDS / registers); out adds HD * sizeof(T).
-template <typename T> struct RowVec { using v8 = typename PoolVec<T>::v8; };
-template <> struct RowVec<float> { typedef float v8 __attribute__((ext_vector_type(8))); };
-
 template <typename T, int HD, bool PROBE = false>
 __global__ __launch_bounds__(256) void attn_cls_kernel(const std::conditional_t<PROBE, float, T>* __restrict__ q, const T* __restrict__ kv,
                                                        int ld, int koff, int voff, T* __restrict__ out, int tokens, int heads,
@@ -110,7 +89,7 @@ __global__ __launch_bounds__(256) void attn_cls_kernel(const std::conditional_t<
     float* scores = sm;
     float* red = sm + ((tokens + 3) & ~3);
     float* part = red + 4;
-    using V8 = typename RowVec<T>::v8;
+    using V8 = typename Vec16<T>::oct;
     const int img = blockIdx.x / heads, head = blockIdx.x - img * heads;
     const int P = heads * HD;
     const int sub = threadIdx.x & (kSub - 1), r = threadIdx.x / kSub;
@@ -181,10 +160,10 @@ int launch_attn_pool(int dtype, const void* kv, const float* q, void* out, int n
     if (n <= 0) return AP_OK;
     const size_t lds = ((size_t)((tokens + 3) & ~3) + 4 + 256) * sizeof(float);
     dim3 grid(n * heads), block(256);
-    if (dtype == AP_F16) attn_pool_kernel<f16><<<grid, block, lds, stream>>>((const f16*)kv, q, (f16*)out, tokens, heads);
-    else attn_pool_kernel<bf16><<<grid, block, lds, stream>>>((const bf16*)kv, q, (bf16*)out, tokens, heads);
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_half("attn_pool", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        attn_pool_kernel<T><<<grid, block, lds, stream>>>((const T*)kv, q, (T*)out, tokens, heads);
+    });
 }
 
 int launch_attention_cls(int dtype, const void* q, const void* kv, int ld, int koff, int voff, void* out, int n,
@@ -195,16 +174,11 @@ int launch_attention_cls(int dtype, const void* q, const void* kv, int ld, int k
     if (n <= 0) return AP_OK;
     const size_t lds = ((size_t)((tokens + 3) & ~3) + 4 + 32 * 64) * sizeof(float);       // part: kRows * HD = 2048 floats either way
     dim3 grid(n * heads), block(256);
-#define AP_CLS(T, HD) attn_cls_kernel<T, HD><<<grid, block, lds, stream>>>((const T*)q, (const T*)kv, ld, koff, voff, (T*)out, tokens, heads, scale)
-#define AP_CLS_HD(T) do { if (head_dim == 64) AP_CLS(T, 64); else if (head_dim == 96) AP_CLS(T, 96); else AP_CLS(T, 128); } while (0)
-    if (dtype == AP_F16) AP_CLS_HD(f16);
-    else if (dtype == AP_BF16) AP_CLS_HD(bf16);
-    else if (dtype == AP_F32) AP_CLS_HD(float);
-    else { set_error("attention_cls: unsupported dtype %d", dtype); return AP_ERR_INVALID; }
-#undef AP_CLS_HD
-#undef AP_CLS
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_dtype("attention_cls", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        const auto kernel = head_dim == 64 ? attn_cls_kernel<T, 64> : head_dim == 96 ? attn_cls_kernel<T, 96> : attn_cls_kernel<T, 128>;
+        kernel<<<grid, block, lds, stream>>>((const T*)q, (const T*)kv, ld, koff, voff, (T*)out, tokens, heads, scale);
+    });
 }
 
 int launch_attention_probe(int dtype, const float* q, const void* kv, int ld, int koff, int voff, void* out, int n,
@@ -215,16 +189,11 @@ int launch_attention_probe(int dtype, const float* q, const void* kv, int ld, in
     if (n <= 0) return AP_OK;
     const size_t lds = ((size_t)((tokens + 3) & ~3) + 4 + 32 * 64) * sizeof(float);       // as launch_attention_cls
     dim3 grid(n * heads), block(256);
-#define AP_PROBE(T, HD) attn_cls_kernel<T, HD, true><<<grid, block, lds, stream>>>(q, (const T*)kv, ld, koff, voff, (T*)out, tokens, heads, scale)
-#define AP_PROBE_HD(T) do { if (head_dim == 64) AP_PROBE(T, 64); else if (head_dim == 96) AP_PROBE(T, 96); else AP_PROBE(T, 128); } while (0)
-    if (dtype == AP_F16) AP_PROBE_HD(f16);
-    else if (dtype == AP_BF16) AP_PROBE_HD(bf16);
-    else if (dtype == AP_F32) AP_PROBE_HD(float);
-    else { set_error("attention_probe: unsupported dtype %d", dtype); return AP_ERR_INVALID; }
-#undef AP_PROBE_HD
-#undef AP_PROBE
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_dtype("attention_probe", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        const auto kernel = head_dim == 64 ? attn_cls_kernel<T, 64, true> : head_dim == 96 ? attn_cls_kernel<T, 96, true> : attn_cls_kernel<T, 128, true>;
+        kernel<<<grid, block, lds, stream>>>(q, (const T*)kv, ld, koff, voff, (T*)out, tokens, heads, scale);
+    });
 }
 
 }  // namespace ap

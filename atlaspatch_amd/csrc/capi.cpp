@@ -8,7 +8,7 @@
 #include <vector>
 #include <zlib.h>
 #include <cmath>
-#include "ap_common.h"
+#include "kernel_util.h"
 #include "gemm_epilogue.h"
 
 namespace ap {
@@ -157,9 +157,9 @@ int ap_tile_content_counts(const uint8_t* tiles, int n, int h, int w, int black_
                                    (unsigned*)counts, (hipStream_t)stream);
 }
 
-static inline bool known_dtype(int dt) { return dt == AP_F32 || dt == AP_F16 || dt == AP_BF16; }
-static inline bool half_dtype(int dt) { return dt == AP_F16 || dt == AP_BF16; }
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+using ap::aligned16;
+using ap::half_dtype;
+using ap::known_dtype;
 static inline bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
 
 // The layout rule of ap_gemm / ap_gemm_fused (include/atlaspatch_hip.h states it): what the two MFMA kernels assume of a call
@@ -173,11 +173,11 @@ static int gemm_contract(const char* fn, int dtype, int epilogue, const ap::Gemm
     AP_REQUIRE(g.N % 128 == 0 && g.K % kt == 0, "%s: N = %d must be a multiple of 128 and K = %d of %d", fn, g.N, g.K, kt);
     AP_REQUIRE(g.lda >= g.K && g.ldw >= g.K && g.ldo >= ocols, "%s: row strides (lda %d, ldw %d, ldo %d) smaller than the rows (K = %d, %d output columns)",
                fn, g.lda, g.ldw, g.ldo, g.K, ocols);
-    AP_REQUIRE(((size_t)g.lda * es) % 16 == 0 && ((size_t)g.ldw * es) % 16 == 0 && aligned16(g.A) && aligned16(g.W),
+    AP_REQUIRE(((size_t)g.lda * es) % 16 == 0 && ((size_t)g.ldw * es) % 16 == 0 && aligned16(g.A, g.W),
                "%s: A and W need 16-byte aligned pointers and row strides", fn);
     AP_REQUIRE(g.ldo % 4 == 0 && ((uintptr_t)g.out % (4 * oes)) == 0, "%s: out needs ldo %% 4 == 0 and a pointer aligned to four elements (%zu bytes)",
                fn, 4 * oes);
-    AP_REQUIRE(aligned16(g.bias) && aligned16(g.gamma) && aligned16(g.colsum) && aligned16(g.rowstats) && aligned8(g.partial),
+    AP_REQUIRE(aligned16(g.bias, g.gamma, g.colsum, g.rowstats) && aligned8(g.partial),
                "%s: bias / gamma / colsum / rowstats need 16-byte aligned pointers, partial an 8-byte aligned one", fn);
     AP_REQUIRE((impl != 256 && impl != 257) || ap::gemm256_supports(dtype, epilogue, g),
                "%s: impl %d (the 256 x 256 kernel) takes f16 / bf16, N %% 256 == 0, K %% 128 == 0, K >= 128, 16-byte aligned output rows", fn, impl);
@@ -218,7 +218,7 @@ static int gemm_split_f16(const float* A, int lda, const void* w_split, int M, i
     AP_REQUIRE(act == 0 || act == 1, "ap_gemm_split_f16: act %d (0 none, 1 GELU)", act);
     AP_REQUIRE(M > 0 && N > 0 && N % 32 == 0 && K > 0 && K % 32 == 0, "ap_gemm_split_f16: %d x %d x %d (N and K multiples of 32)", M, N, K);
     AP_REQUIRE(lda >= K && lda % 4 == 0 && ldo >= N && ldo % 4 == 0 && (!resid || (ldr >= N && ldr % 4 == 0)), "ap_gemm_split_f16: strides");
-    AP_REQUIRE(((uintptr_t)A | (uintptr_t)w_split | (uintptr_t)out | (uintptr_t)resid | (uintptr_t)bias) % 16 == 0, "ap_gemm_split_f16: 16-byte aligned pointers");
+    AP_REQUIRE(aligned16(A, w_split, out, resid, bias), "ap_gemm_split_f16: 16-byte aligned pointers");
     ap::GemmArgs g{};
     g.A = A; g.lda = lda; g.W = w_split; g.ldw = K; g.M = M; g.N = N; g.K = K;
     g.bias = bias; g.out = out; g.ldo = ldo; g.resid = resid; g.ldr = ldr; g.split = 1;
@@ -307,7 +307,7 @@ static int attention_args_ok(const char* who, int dtype, const void* qkv, const 
     AP_REQUIRE(n >= 0 && tokens > 0 && heads > 0, "%s: bad shape (n %d, %d tokens, %d heads)", who, n, tokens, heads);
     AP_REQUIRE(head_dim == 64 || ((head_dim == 96 || head_dim == 128) && dtype != AP_F32),
                "%s: head_dim %d unsupported (64; 96 / 128 in f16 / bf16)", who, head_dim);
-    AP_REQUIRE((uintptr_t)qkv % 16 == 0 && (uintptr_t)out % 16 == 0, "%s: qkv / out must be 16-byte aligned", who);
+    AP_REQUIRE(aligned16(qkv, out), "%s: qkv / out must be 16-byte aligned", who);
     // the tiled kernel addresses a key row by a 32-bit byte offset inside its image
     AP_REQUIRE(dtype == AP_F32 || (size_t)tokens * 3 * heads * head_dim * 2 < 0xffffffffull,
                "%s: %d tokens x %d heads x %d: an image's qkv rows exceed 4 GiB", who, tokens, heads, head_dim);
@@ -339,7 +339,7 @@ int ap_attention_cls(int dtype, const void* q, const void* kv, int ld, int koff,
     const long width = (long)heads * head_dim;
     AP_REQUIRE(ld > 0 && ld % 8 == 0 && koff >= 0 && voff >= 0 && koff % 8 == 0 && voff % 8 == 0 && koff + width <= ld && voff + width <= ld,
                "ap_attention_cls: k / v (offsets %d / %d, %ld wide) must lie inside rows of %d elements, all multiples of 8", koff, voff, width, ld);
-    AP_REQUIRE(aligned16(q) && aligned16(kv) && (dtype != AP_F32 || (((uintptr_t)q | (uintptr_t)kv) & 31) == 0),
+    AP_REQUIRE(aligned16(q, kv) && (dtype != AP_F32 || (((uintptr_t)q | (uintptr_t)kv) & 31) == 0),
                "ap_attention_cls: q / kv must be aligned to 8 elements");
     AP_REQUIRE(std::isfinite(scale), "ap_attention_cls: scale must be finite");
     return ap::launch_attention_cls(dtype, q, kv, ld, koff, voff, out, n, tokens, heads, head_dim, scale, (hipStream_t)stream);
@@ -355,7 +355,7 @@ int ap_attention_probe(int dtype, const float* q, const void* kv, int ld, int ko
     const long width = (long)heads * head_dim;
     AP_REQUIRE(ld > 0 && ld % 8 == 0 && koff >= 0 && voff >= 0 && koff % 8 == 0 && voff % 8 == 0 && koff + width <= ld && voff + width <= ld,
                "ap_attention_probe: k / v (offsets %d / %d, %ld wide) must lie inside rows of %d elements, all multiples of 8", koff, voff, width, ld);
-    AP_REQUIRE(aligned16(q) && aligned16(kv) && (dtype != AP_F32 || ((uintptr_t)kv & 31) == 0),
+    AP_REQUIRE(aligned16(q, kv) && (dtype != AP_F32 || ((uintptr_t)kv & 31) == 0),
                "ap_attention_probe: q must be 16-byte aligned and kv aligned to 8 elements");
     AP_REQUIRE(std::isfinite(scale), "ap_attention_probe: scale must be finite");
     return ap::launch_attention_probe(dtype, q, kv, ld, koff, voff, out, n, tokens, heads, head_dim, scale, (hipStream_t)stream);
@@ -386,7 +386,7 @@ int ap_swiglu(int dtype, const void* x, int rows, int h, void* out, ap_stream_t 
     AP_REQUIRE(x && out, "ap_swiglu: null pointer");
     AP_REQUIRE(known_dtype(dtype), "ap_swiglu: unknown dtype %d", dtype);
     AP_REQUIRE(rows >= 0 && h > 0 && h % 8 == 0, "ap_swiglu: bad shape (%d rows, h %d: a positive multiple of 8)", rows, h);
-    AP_REQUIRE(aligned16(x) && aligned16(out), "ap_swiglu: x / out must be 16-byte aligned");
+    AP_REQUIRE(aligned16(x, out), "ap_swiglu: x / out must be 16-byte aligned");
     return ap::launch_swiglu(dtype, x, rows, h, out, (hipStream_t)stream);
 }
 
@@ -406,8 +406,7 @@ int ap_add2_layernorm(int delta_dtype, int out_dtype, float* x, long stride, con
     AP_REQUIRE(stride >= dim && stride % 4 == 0 && (!delta0 || (dstride0 >= dim && dstride0 % dmul == 0)) &&
                    (!delta1 || (dstride1 >= dim && dstride1 % dmul == 0)),
                "ap_add2_layernorm: row strides must be at least dim and multiples of 4 (16-bit delta at dim 768 / 1024: of 8)");
-    AP_REQUIRE(aligned16(x) && aligned16(gamma) && aligned16(beta) && aligned16(out) && aligned16(delta0) && aligned16(delta1) && aligned16(ls0) &&
-                   aligned16(ls1),
+    AP_REQUIRE(aligned16(x, gamma, beta, out, delta0, delta1, ls0, ls1),
                "ap_add2_layernorm: every buffer must be 16-byte aligned");
     AP_REQUIRE(std::isfinite(eps) && eps >= 0.f, "ap_add2_layernorm: eps must be finite and non-negative");
     return ap::launch_add2_layernorm(delta_dtype, out_dtype, x, stride, delta0, dstride0, ls0, delta1, dstride1, ls1, store, rows, dim, gamma,

@@ -10,20 +10,15 @@
 //   tokens[img][1 + p] = T(x[img][p] + pos[1 + p])
 //   One workgroup per (image, 64 chunks of channels): 4 row groups x 64 chunk lanes.  Row group g streams rows g, g + 4, ..,
 //   writes their token rows and keeps its column sums in registers; the four partial sums meet in LDS in a fixed order.
-#include "ap_common.h"
+#include "kernel_util.h"
 
 namespace ap {
 namespace {
 
-template <typename T> struct Chunk;                        // the 16-byte vector of T
-template <> struct Chunk<f16> { using type = f16x8; };
-template <> struct Chunk<bf16> { using type = bf16x8; };
-template <> struct Chunk<float> { using type = f32x4; };
-
 template <typename T>
 __global__ __launch_bounds__(256) void avgpool2x2_kernel(const T* __restrict__ x, int n, int H, int W, int C, T* __restrict__ out) {
     constexpr int CH = 16 / sizeof(T);
-    using V = typename Chunk<T>::type;
+    using V = typename Vec16<T>::type;
     const int chunks = C / CH, Ho = H / 2, Wo = W / 2;
     const size_t total = (size_t)n * Ho * Wo * chunks;
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
@@ -48,7 +43,7 @@ __global__ __launch_bounds__(TOK_LANES * TOK_GROUPS) void clip_attnpool_tokens_k
                                                                                         int hw, int C, T* __restrict__ tokens,
                                                                                         T* __restrict__ q_rows) {
     constexpr int CH = 16 / sizeof(T);
-    using V = typename Chunk<T>::type;
+    using V = typename Vec16<T>::type;
     __shared__ float part[TOK_GROUPS][TOK_LANES][CH];
     const int lane = threadIdx.x & (TOK_LANES - 1), grp = threadIdx.x / TOK_LANES;
     const int chunk = blockIdx.x * TOK_LANES + lane;
@@ -100,19 +95,14 @@ int launch_avgpool2x2_nhwc(int dtype, const void* x, int n, int h, int w, int c,
     AP_REQUIRE(dtype == AP_F16 || dtype == AP_BF16 || dtype == AP_F32, "avgpool2x2_nhwc: dtype %d", dtype);
     AP_REQUIRE(n >= 0 && h > 0 && w > 0 && h % 2 == 0 && w % 2 == 0 && c > 0 && c % 8 == 0,
                "avgpool2x2_nhwc: n %d h %d w %d c %d (h, w even, c %% 8 == 0)", n, h, w, c);
-    AP_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 15) == 0, "avgpool2x2_nhwc: pointers must be 16-byte aligned");
+    AP_REQUIRE(aligned16(x, out), "avgpool2x2_nhwc: pointers must be 16-byte aligned");
     AP_REQUIRE(x != out, "avgpool2x2_nhwc: out must not alias x");
     if (n == 0) return AP_OK;
     const size_t work = (size_t)n * (h / 2) * (w / 2) * ((size_t)c * dtype_size(dtype) / 16);
-    const size_t b = (work + 255) / 256;
-    const int g = (int)(b < 65536 ? b : 65536);
-    switch (dtype) {
-        case AP_F16: avgpool2x2_kernel<f16><<<g, 256, 0, stream>>>((const f16*)x, n, h, w, c, (f16*)out); break;
-        case AP_BF16: avgpool2x2_kernel<bf16><<<g, 256, 0, stream>>>((const bf16*)x, n, h, w, c, (bf16*)out); break;
-        default: avgpool2x2_kernel<float><<<g, 256, 0, stream>>>((const float*)x, n, h, w, c, (float*)out); break;
-    }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_dtype("avgpool2x2_nhwc", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        avgpool2x2_kernel<T><<<grid_1d(work, 65536), 256, 0, stream>>>((const T*)x, n, h, w, c, (T*)out);
+    });
 }
 
 int launch_clip_attnpool_tokens(int dtype, const void* x, const float* pos, int n, int hw, int c, void* tokens_out, void* q_rows_out,
@@ -121,18 +111,14 @@ int launch_clip_attnpool_tokens(int dtype, const void* x, const float* pos, int 
     AP_REQUIRE(dtype == AP_F16 || dtype == AP_BF16 || dtype == AP_F32, "clip_attnpool_tokens: dtype %d", dtype);
     AP_REQUIRE(n >= 0 && n <= 65535 && hw > 0 && hw <= 4096 && c > 0 && c % 8 == 0 && c <= 65536,
                "clip_attnpool_tokens: n %d hw %d c %d (n <= 65535, hw <= 4096, c %% 8 == 0, c <= 65536)", n, hw, c);
-    AP_REQUIRE((((uintptr_t)x | (uintptr_t)pos | (uintptr_t)tokens_out | (uintptr_t)q_rows_out) & 15) == 0,
-               "clip_attnpool_tokens: pointers must be 16-byte aligned");
+    AP_REQUIRE(aligned16(x, pos, tokens_out, q_rows_out), "clip_attnpool_tokens: pointers must be 16-byte aligned");
     if (n == 0) return AP_OK;
     const int chunks = (int)((size_t)c * dtype_size(dtype) / 16);
     dim3 grid((chunks + TOK_LANES - 1) / TOK_LANES, n), block(TOK_LANES * TOK_GROUPS);
-    switch (dtype) {
-        case AP_F16: clip_attnpool_tokens_kernel<f16><<<grid, block, 0, stream>>>((const f16*)x, pos, hw, c, (f16*)tokens_out, (f16*)q_rows_out); break;
-        case AP_BF16: clip_attnpool_tokens_kernel<bf16><<<grid, block, 0, stream>>>((const bf16*)x, pos, hw, c, (bf16*)tokens_out, (bf16*)q_rows_out); break;
-        default: clip_attnpool_tokens_kernel<float><<<grid, block, 0, stream>>>((const float*)x, pos, hw, c, (float*)tokens_out, (float*)q_rows_out); break;
-    }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_dtype("clip_attnpool_tokens", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        clip_attnpool_tokens_kernel<T><<<grid, block, 0, stream>>>((const T*)x, pos, hw, c, (T*)tokens_out, (T*)q_rows_out);
+    });
 }
 
 }  // namespace ap

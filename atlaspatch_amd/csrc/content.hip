@@ -10,7 +10,7 @@
 //
 // One workgroup per (tile, slice): a lane takes 16 pixels as three 16-byte loads (48 contiguous bytes),
 // predicates are counted with wave ballots + popcount, one atomicAdd per wave.  HBM-bound (3 B / pixel).
-#include "ap_common.h"
+#include "kernel_util.h"
 
 namespace ap {
 namespace {
@@ -40,11 +40,8 @@ __global__ __launch_bounds__(256) void tile_content_kernel(const uint8_t* __rest
             nwhite += (sat < sat_thresh && vmax >= value_thresh) ? 1u : 0u;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        nblack += __shfl_xor(nblack, off, 64);
-        nwhite += __shfl_xor(nwhite, off, 64);
-    }
+    nblack = wave_sum(nblack);
+    nwhite = wave_sum(nwhite);
     if ((threadIdx.x & 63) == 0) {
         atomicAdd(&counts[tile * 2], nblack);
         atomicAdd(&counts[tile * 2 + 1], nwhite);
@@ -58,7 +55,7 @@ int tile_content_counts(const uint8_t* tiles, int n, int h, int w, int black_thr
     AP_REQUIRE(tiles && counts, "tile_content: null pointer");
     AP_REQUIRE(n >= 0 && h > 0 && w > 0 && ((size_t)h * w) % 16 == 0, "tile_content: %d x %d tiles (pixels per tile "
                "must be a multiple of 16)", h, w);
-    AP_REQUIRE(((uintptr_t)tiles & 15) == 0, "tile_content: tiles must be 16-byte aligned");
+    AP_REQUIRE(aligned16(tiles), "tile_content: tiles must be 16-byte aligned");
     if (n == 0) return AP_OK;
     AP_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)n * 2 * sizeof(unsigned), stream));
     const int groups = (int)((size_t)h * w / 16);

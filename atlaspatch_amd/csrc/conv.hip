@@ -18,7 +18,7 @@
 // conv_implicit_gemm<T, EXT = true> is the ConvNeXt instantiation (ap_conv2d_nhwc_ex): Cout % 32 == 0, the last N tile's
 // upper 32 columns masked (no weight row read, no store), and a GELU (erf) epilogue beside ReLU.  EXT = false is the ResNet
 // kernel behind ap_conv2d_nhwc; its instruction stream is the one it had before EXT existed.
-#include "ap_common.h"
+#include "kernel_util.h"
 
 namespace ap {
 namespace {
@@ -39,25 +39,10 @@ struct ConvArgs {
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2 };
 
-template <typename T> struct ConvMma;
-template <> struct ConvMma<f16> {
-    static constexpr int KSTEP = 16;
-    static __device__ __forceinline__ f32x16 run(const char* a, const char* b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const f16x8*)a, *(const f16x8*)b, c, 0, 0, 0);
-    }
-};
-template <> struct ConvMma<bf16> {
-    static constexpr int KSTEP = 16;
-    static __device__ __forceinline__ f32x16 run(const char* a, const char* b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)a, *(const bf16x8*)b, c, 0, 0, 0);
-    }
-};
-template <> struct ConvMma<float> {
-    static constexpr int KSTEP = 2;
-    static __device__ __forceinline__ f32x16 run(const char* a, const char* b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x2f32(*(const float*)a, *(const float*)b, c, 0, 0, 0);
-    }
-};
+// Mma32x32 on fragments read at LDS byte addresses
+template <typename T> __device__ __forceinline__ f32x16 mma_at(const char* a, const char* b, f32x16 c) {
+    return Mma32x32<T>::run(*(const typename Mma32x32<T>::Frag*)a, *(const typename Mma32x32<T>::Frag*)b, c);
+}
 
 template <typename T> __device__ __forceinline__ float to_f32(T v) { return (float)v; }
 
@@ -65,7 +50,7 @@ template <typename T, bool EXT>
 __global__ __launch_bounds__(CTHREADS) void conv_implicit_gemm(ConvArgs a) {
     constexpr int CH = 16 / sizeof(T);                 // elements per 16-byte chunk
     constexpr int KT = KBYTES / sizeof(T);             // K elements per step
-    constexpr int KSTEP = ConvMma<T>::KSTEP;
+    constexpr int KSTEP = Mma32x32<T>::K;
     __shared__ __attribute__((aligned(16))) char As[CBM * LDS_ROW];
     __shared__ __attribute__((aligned(16))) char Bs[CBN * LDS_ROW];
 
@@ -150,8 +135,8 @@ __global__ __launch_bounds__(CTHREADS) void conv_implicit_gemm(ConvArgs a) {
 #pragma unroll
         for (int s = 0; s < KT / KSTEP; ++s) {
             const int off = s * KSTEP * (int)sizeof(T);
-            acc[0] = ConvMma<T>::run(pa0 + off, pb + off, acc[0]);
-            acc[1] = ConvMma<T>::run(pa1 + off, pb + off, acc[1]);
+            acc[0] = mma_at<T>(pa0 + off, pb + off, acc[0]);
+            acc[1] = mma_at<T>(pa1 + off, pb + off, acc[1]);
         }
     }
 
@@ -250,11 +235,6 @@ __global__ __launch_bounds__(256) void avgpool_nhwc(const T* x, int n, int HW, i
     }
 }
 
-inline int grid_for(size_t work) {
-    const size_t b = (work + 255) / 256;
-    return (int)(b < 65536 ? (b > 0 ? b : 1) : 65536);
-}
-
 // The implicit GEMM's launcher.  EXT = false: ap_conv2d_nhwc (ResNet; Cout % 64, act = ReLU flag); EXT = true: ap_conv2d_nhwc_ex
 // (ConvNeXt; Cout % 32 through the masked N tail, act 0 none / 1 ReLU / 2 GELU).
 template <bool EXT>
@@ -270,8 +250,7 @@ int launch_conv2d(int dtype, const void* x, int n, int h, int w, int cin, const 
     AP_REQUIRE(ksize >= 1 && ksize <= 7 && stride >= 1 && stride <= 4 && pad >= 0 && pad < ksize,
                "%s: kernel %d stride %d pad %d", who, ksize, stride, pad);
     AP_REQUIRE(h + 2 * pad >= ksize && w + 2 * pad >= ksize, "%s: %dx%d input smaller than the %d kernel", who, h, w, ksize);
-    AP_REQUIRE((((uintptr_t)x | (uintptr_t)weight | (uintptr_t)out | (uintptr_t)resid) & 15) == 0,
-               "%s: pointers must be 16-byte aligned", who);
+    AP_REQUIRE(aligned16(x, weight, out, resid), "%s: pointers must be 16-byte aligned", who);
     if (EXT) {
         AP_REQUIRE(act == ACT_NONE || act == ACT_RELU || act == ACT_GELU, "%s: activation %d (0 none, 1 ReLU, 2 GELU)", who, act);
     } else {
@@ -284,13 +263,9 @@ int launch_conv2d(int dtype, const void* x, int n, int h, int w, int cin, const 
     ConvArgs a{x, weight, bias, resid, out, h, w, cin, ho, wo, cout, ksize, stride, pad, ksize * ksize * cin, (int)M, act};
     const size_t blocks = (M + CBM - 1) / CBM * (size_t)((cout + CBN - 1) / CBN);
     AP_REQUIRE(blocks < (size_t)1 << 31, "%s: grid too large", who);
-    switch (dtype) {
-        case AP_F16: conv_implicit_gemm<f16, EXT><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
-        case AP_BF16: conv_implicit_gemm<bf16, EXT><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
-        default: conv_implicit_gemm<float, EXT><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a); break;
-    }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_dtype(who, dtype, [&](auto tag) {
+        conv_implicit_gemm<typename decltype(tag)::type, EXT><<<(unsigned)blocks, CTHREADS, 0, stream>>>(a);
+    });
 }
 
 }  // namespace
@@ -313,47 +288,32 @@ int launch_preproc_nhwc8(const uint8_t* src, int n, int h, int w, int top, int l
     const void* lut = nullptr;
     int rc = get_norm_lut(mean, stdv, dtype, stream, &lut);
     if (rc != AP_OK) return rc;
-    const int g = grid_for((size_t)n * S * S);
-    switch (dtype) {
-        case AP_F16: preproc_nhwc8<f16><<<g, 256, 0, stream>>>(src, n, h, w, top, left, S, (const f16*)lut, (f16*)dst); break;
-        case AP_BF16: preproc_nhwc8<bf16><<<g, 256, 0, stream>>>(src, n, h, w, top, left, S, (const bf16*)lut, (bf16*)dst); break;
-        case AP_F32: preproc_nhwc8<float><<<g, 256, 0, stream>>>(src, n, h, w, top, left, S, (const float*)lut, (float*)dst); break;
-        default: set_error("preproc_nhwc8: dtype %d", dtype); return AP_ERR_INVALID;
-    }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_dtype("preproc_nhwc8", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        preproc_nhwc8<T><<<grid_1d((size_t)n * S * S, 65536), 256, 0, stream>>>(src, n, h, w, top, left, S, (const T*)lut, (T*)dst);
+    });
 }
 
 int launch_maxpool3x3s2_nhwc(int dtype, const void* x, int n, int h, int w, int c, void* out, hipStream_t stream) {
     AP_REQUIRE(x && out && n >= 0 && h > 0 && w > 0 && c > 0 && c % 8 == 0, "maxpool3x3s2_nhwc: n %d h %d w %d c %d (c %% 8 == 0)",
                n, h, w, c);
-    AP_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 15) == 0, "maxpool3x3s2_nhwc: pointers must be 16-byte aligned");
+    AP_REQUIRE(aligned16(x, out), "maxpool3x3s2_nhwc: pointers must be 16-byte aligned");
     const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
     if (n == 0) return AP_OK;
     const size_t work = (size_t)n * ho * wo * c / (16 / dtype_size(dtype));
-    const int g = grid_for(work);
-    switch (dtype) {
-        case AP_F16: maxpool3x3s2<f16><<<g, 256, 0, stream>>>((const f16*)x, n, h, w, c, ho, wo, (f16*)out); break;
-        case AP_BF16: maxpool3x3s2<bf16><<<g, 256, 0, stream>>>((const bf16*)x, n, h, w, c, ho, wo, (bf16*)out); break;
-        case AP_F32: maxpool3x3s2<float><<<g, 256, 0, stream>>>((const float*)x, n, h, w, c, ho, wo, (float*)out); break;
-        default: set_error("maxpool3x3s2_nhwc: dtype %d", dtype); return AP_ERR_INVALID;
-    }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_dtype("maxpool3x3s2_nhwc", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        maxpool3x3s2<T><<<grid_1d(work, 65536), 256, 0, stream>>>((const T*)x, n, h, w, c, ho, wo, (T*)out);
+    });
 }
 
 int launch_avgpool_nhwc(int dtype, const void* x, int n, int hw, int c, float* out, hipStream_t stream) {
     AP_REQUIRE(x && out && n >= 0 && hw > 0 && c > 0, "avgpool_nhwc: n %d hw %d c %d", n, hw, c);
     if (n == 0) return AP_OK;
-    const int g = grid_for((size_t)n * c);
-    switch (dtype) {
-        case AP_F16: avgpool_nhwc<f16><<<g, 256, 0, stream>>>((const f16*)x, n, hw, c, out); break;
-        case AP_BF16: avgpool_nhwc<bf16><<<g, 256, 0, stream>>>((const bf16*)x, n, hw, c, out); break;
-        case AP_F32: avgpool_nhwc<float><<<g, 256, 0, stream>>>((const float*)x, n, hw, c, out); break;
-        default: set_error("avgpool_nhwc: dtype %d", dtype); return AP_ERR_INVALID;
-    }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_dtype("avgpool_nhwc", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        avgpool_nhwc<T><<<grid_1d((size_t)n * c, 65536), 256, 0, stream>>>((const T*)x, n, hw, c, out);
+    });
 }
 
 }  // namespace ap

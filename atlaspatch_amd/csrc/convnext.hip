@@ -15,7 +15,7 @@
 // Weights are f32, tap-major [49][C] (dw_weight[(ky * 7 + kx) * C + c]); bias, LayerNorm gain and shift f32 [C].
 //
 // layernorm_rows: one wave per row of C (% 8) channels, the same two-pass f32 statistics, 16-byte loads and stores.
-#include "ap_common.h"
+#include "kernel_util.h"
 
 namespace ap {
 namespace {
@@ -23,40 +23,6 @@ namespace {
 constexpr int DW_THREADS = 256;
 constexpr int DW_RUN = 4;                      // output pixels per phase-1 work item
 constexpr int DW_MAX_LDS = 64 * 1024;          // bytes of LDS a workgroup may stage (the four networks use <= 43 008)
-
-template <typename T> __device__ __forceinline__ void load8(const T* p, float v[8]) {
-    if constexpr (sizeof(T) == 2) {
-        const u32x4 r = *(const u32x4*)p;
-        T e[8];
-        __builtin_memcpy(e, &r, 16);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = (float)e[i];
-    } else {
-        const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { v[i] = a[i]; v[4 + i] = b[i]; }
-    }
-}
-
-template <typename T> __device__ __forceinline__ void store8(T* p, const float v[8]) {
-    if constexpr (sizeof(T) == 2) {
-        T e[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) e[i] = from_f32<T>(v[i]);
-        u32x4 r;
-        __builtin_memcpy(&r, e, 16);
-        *(u32x4*)p = r;
-    } else {
-        *(f32x4*)p = f32x4{v[0], v[1], v[2], v[3]};
-        *(f32x4*)(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
-    }
-}
-
-__device__ __forceinline__ void load8f(const float* p, float v[8]) {
-    const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[i] = a[i]; v[4 + i] = b[i]; }
-}
 
 struct DwArgs {
     const void* x;              // T [n, H, W, C]
@@ -94,7 +60,7 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv7_ln(DwArgs a) {
             if (iy < 0 || iy >= a.H) continue;
             float wv[7][8];
 #pragma unroll
-            for (int kx = 0; kx < 7; ++kx) load8f(a.w + (size_t)(ky * 7 + kx) * C + c8 * 8, wv[kx]);
+            for (int kx = 0; kx < 7; ++kx) load8(a.w + (size_t)(ky * 7 + kx) * C + c8 * 8, wv[kx]);
             const T* xrow = x + ((size_t)img * a.H + iy) * a.W * C + c8 * 8;
 #pragma unroll
             for (int j = 0; j < DW_RUN + 6; ++j) {
@@ -112,7 +78,7 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv7_ln(DwArgs a) {
             }
         }
         float bv[8];
-        load8f(a.bias + c8 * 8, bv);
+        load8(a.bias + c8 * 8, bv);
 #pragma unroll
         for (int p = 0; p < DW_RUN; ++p) {
             if (px + p >= xe) break;
@@ -151,8 +117,8 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv7_ln(DwArgs a) {
         for (int k = l; k < nch; k += tpp) {
             float v[8], gv[8], bv[8], o[8];
             load8(y + k * 8, v);
-            load8f(a.g + k * 8, gv);
-            load8f(a.b + k * 8, bv);
+            load8(a.g + k * 8, gv);
+            load8(a.b + k * 8, bv);
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (v[e] - mean) * rstd * gv[e] + bv[e];
             store8(dst + k * 8, o);
@@ -163,42 +129,11 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv7_ln(DwArgs a) {
 template <typename T>
 __global__ __launch_bounds__(256) void layernorm_rows(const T* x, int rows, int C, const float* g, const float* b, float eps,
                                                       T* out) {
-    const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;                                 // a whole wave
-    const int nch = C / 8;
     const T* y = x + (size_t)r * C;
-    float s = 0.f;
-    for (int k = lane; k < nch; k += 64) {
-        float v[8];
-        load8(y + k * 8, v);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += v[e];
-    }
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-    const float mean = s / (float)C;
-    float ss = 0.f;
-    for (int k = lane; k < nch; k += 64) {
-        float v[8];
-        load8(y + k * 8, v);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { const float d = v[e] - mean; ss = fmaf(d, d, ss); }
-    }
-    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o, 64);
-    const float rstd = 1.0f / sqrtf(ss / (float)C + eps);
-    T* dst = out + (size_t)r * C;
-    for (int k = lane; k < nch; k += 64) {
-        float v[8], gv[8], bv[8], o[8];
-        load8(y + k * 8, v);
-        load8f(g + k * 8, gv);
-        load8f(b + k * 8, bv);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (v[e] - mean) * rstd * gv[e] + bv[e];
-        store8(dst + k * 8, o);
-    }
+    wave_layernorm8([&](int k) { return y + k * 8; }, C / 8, C, g, b, eps, out + (size_t)r * C);
 }
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -208,8 +143,7 @@ int launch_dwconv7_ln_nhwc(int dtype, const void* x, int n, int h, int w, int c,
     AP_REQUIRE(dtype == AP_F16 || dtype == AP_BF16 || dtype == AP_F32, "dwconv7_ln_nhwc: dtype %d", dtype);
     AP_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0 && c % 8 == 0, "dwconv7_ln_nhwc: n %d h %d w %d c %d (c %% 8 == 0)", n, h, w, c);
     AP_REQUIRE(eps > 0.f, "dwconv7_ln_nhwc: eps %g", (double)eps);
-    AP_REQUIRE(aligned16(x) && aligned16(dw_weight) && aligned16(dw_bias) && aligned16(ln_weight) && aligned16(ln_bias) &&
-                   aligned16(out), "dwconv7_ln_nhwc: pointers must be 16-byte aligned");
+    AP_REQUIRE(aligned16(x, dw_weight, dw_bias, ln_weight, ln_bias, out), "dwconv7_ln_nhwc: pointers must be 16-byte aligned");
     AP_REQUIRE(x != out, "dwconv7_ln_nhwc: in place is not supported (a workgroup reads the rows of its neighbours)");
     const size_t row_bytes = (size_t)c * dtype_size(dtype);
     AP_REQUIRE(DW_RUN * row_bytes <= DW_MAX_LDS, "dwconv7_ln_nhwc: c %d too wide", c);
@@ -223,13 +157,10 @@ int launch_dwconv7_ln_nhwc(int dtype, const void* x, int n, int h, int w, int c,
     AP_REQUIRE(blocks < (size_t)1 << 31, "dwconv7_ln_nhwc: grid too large");
     DwArgs a{x, dw_weight, dw_bias, ln_weight, ln_bias, out, h, w, c, xt, nseg, tpp, eps};
     const size_t lds = (size_t)xt * row_bytes;
-    switch (dtype) {
-        case AP_F16: dwconv7_ln<f16><<<(unsigned)blocks, DW_THREADS, lds, stream>>>(a); break;
-        case AP_BF16: dwconv7_ln<bf16><<<(unsigned)blocks, DW_THREADS, lds, stream>>>(a); break;
-        default: dwconv7_ln<float><<<(unsigned)blocks, DW_THREADS, lds, stream>>>(a); break;
-    }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_dtype("dwconv7_ln_nhwc", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        dwconv7_ln<T><<<(unsigned)blocks, DW_THREADS, lds, stream>>>(a);
+    });
 }
 
 int launch_layernorm_rows(int dtype, const void* x, int rows, int c, const float* weight, const float* bias, float eps, void* out,
@@ -238,17 +169,13 @@ int launch_layernorm_rows(int dtype, const void* x, int rows, int c, const float
     AP_REQUIRE(dtype == AP_F16 || dtype == AP_BF16 || dtype == AP_F32, "layernorm_rows: dtype %d", dtype);
     AP_REQUIRE(rows >= 0 && c > 0 && c % 8 == 0, "layernorm_rows: rows %d c %d (c %% 8 == 0)", rows, c);
     AP_REQUIRE(eps > 0.f, "layernorm_rows: eps %g", (double)eps);
-    AP_REQUIRE(aligned16(x) && aligned16(weight) && aligned16(bias) && aligned16(out),
-               "layernorm_rows: pointers must be 16-byte aligned");
+    AP_REQUIRE(aligned16(x, weight, bias, out), "layernorm_rows: pointers must be 16-byte aligned");
     if (rows == 0) return AP_OK;
     const unsigned blocks = (unsigned)((rows + 3) / 4);
-    switch (dtype) {
-        case AP_F16: layernorm_rows<f16><<<blocks, 256, 0, stream>>>((const f16*)x, rows, c, weight, bias, eps, (f16*)out); break;
-        case AP_BF16: layernorm_rows<bf16><<<blocks, 256, 0, stream>>>((const bf16*)x, rows, c, weight, bias, eps, (bf16*)out); break;
-        default: layernorm_rows<float><<<blocks, 256, 0, stream>>>((const float*)x, rows, c, weight, bias, eps, (float*)out); break;
-    }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_dtype("layernorm_rows", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        layernorm_rows<T><<<blocks, 256, 0, stream>>>((const T*)x, rows, c, weight, bias, eps, (T*)out);
+    });
 }
 
 }  // namespace ap

@@ -4,39 +4,10 @@
 //
 // Algorithmic bytes per row: LayerNorm reads 4*dim and writes sizeof(T)*dim; with the fused residual
 // add it also reads sizeof(T)*dim (delta) and writes 4*dim (the updated stream).
-#include "ap_common.h"
-#include <type_traits>
+#include "kernel_util.h"
 
 namespace ap {
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-template <typename T> __device__ __forceinline__ void store_vec4(T* p, f32x4 v);
-template <> __device__ __forceinline__ void store_vec4<float>(float* p, f32x4 v) { *(f32x4*)p = v; }
-template <> __device__ __forceinline__ void store_vec4<f16>(f16* p, f32x4 v) {
-    f16x4 h = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
-    *(f16x4*)p = h;
-}
-template <> __device__ __forceinline__ void store_vec4<bf16>(bf16* p, f32x4 v) {
-    bf16x4 h = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-    *(bf16x4*)p = h;
-}
-
-template <typename T> __device__ __forceinline__ f32x4 load_vec4(const T* p);
-template <> __device__ __forceinline__ f32x4 load_vec4<float>(const float* p) { return *(const f32x4*)p; }
-template <> __device__ __forceinline__ f32x4 load_vec4<f16>(const f16* p) {
-    const f16x4 h = *(const f16x4*)p;
-    return f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
-}
-template <> __device__ __forceinline__ f32x4 load_vec4<bf16>(const bf16* p) {
-    const bf16x4 h = *(const bf16x4*)p;
-    return f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
-}
 
 // ---- (residual add +) LayerNorm.  x: f32 rows (the residual stream); when `delta` is given the
 // row is first updated, x += delta * ls (the branch output a GEMM stored in TD, times the optional
@@ -57,41 +28,9 @@ struct LnAdds {
 // Main kernel: 16 lanes per row, 4 rows per wave: reductions stay inside a DPP row (no LDS
 // permutes) and four rows in flight per wave hide the HBM latency.  dim = 64 * NV.
 
-
-__device__ __forceinline__ float row16_sum(float v) {
-    // xor-1, xor-2 (quad permutes), then mirror within 8 and within 16 lanes: all VALU + DPP
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-    return v;
-}
-
 // WIDE: a lane owns 8 consecutive elements per step (two adjacent f32x4 of the stream, ONE 16-byte load of a 16-bit
 // branch output, ONE 16-byte store of the normalised row) instead of 4: half as many memory instructions on the
 // 16-bit operands and 256-byte instead of 128-byte segments per 16-lane row.
-template <typename T> __device__ __forceinline__ void load_vec8(const T* p, f32x4& a, f32x4& b) {
-    if constexpr (sizeof(T) == 2) {
-        typedef T Tx8 __attribute__((ext_vector_type(8)));
-        const Tx8 h = *(const Tx8*)p;
-        a = f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
-        b = f32x4{(float)h[4], (float)h[5], (float)h[6], (float)h[7]};
-    } else {
-        a = *(const f32x4*)p;
-        b = *(const f32x4*)(p + 4);
-    }
-}
-template <typename T> __device__ __forceinline__ void store_vec8(T* p, f32x4 a, f32x4 b) {
-    if constexpr (sizeof(T) == 2) {
-        typedef T Tx8 __attribute__((ext_vector_type(8)));
-        Tx8 h = {(T)a[0], (T)a[1], (T)a[2], (T)a[3], (T)b[0], (T)b[1], (T)b[2], (T)b[3]};
-        *(Tx8*)p = h;
-    } else {
-        *(f32x4*)p = a;
-        *(f32x4*)(p + 4) = b;
-    }
-}
-
 // The per-column parameters (gamma, beta and the LayerScale vectors) are staged once per workgroup in LDS (one
 // coalesced 16-byte load per thread and vector): read from global memory per row they cost 2-4 extra 16-byte loads
 // per lane and vector (uni_v1's two LayerScale vectors made add+LN 26 % slower than vit_l_16's: 50.0 -> 39.7 ms).
@@ -154,7 +93,7 @@ __global__ __launch_bounds__(256) void layernorm16_kernel(float* __restrict__ x,
         }
 #pragma unroll
         for (int i = 0; i < NV; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-        const float mean = row16_sum(s) / (float)dim;
+        const float mean = sum16(s) / (float)dim;
         float q = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i)
@@ -163,7 +102,7 @@ __global__ __launch_bounds__(256) void layernorm16_kernel(float* __restrict__ x,
                 const float d = v[i][e] - mean;
                 q += d * d;
             }
-        const float rstd = 1.0f / sqrtf(row16_sum(q) / (float)dim + eps);
+        const float rstd = 1.0f / sqrtf(sum16(q) / (float)dim + eps);
         if (!live) continue;
         TO* dst = out + (size_t)row * dim;
 #pragma unroll
@@ -351,11 +290,8 @@ __global__ __launch_bounds__(256) void rowstats_finalize_kernel(const float* __r
         s += v[0] + v[2];
         q += v[1] + v[3];
     }
-#define AP_DPP8(V, CTRL) __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, (V)), (CTRL), 0xF, 0xF, true))
-    s += AP_DPP8(s, 0xB1); q += AP_DPP8(q, 0xB1);
-    s += AP_DPP8(s, 0x4E); q += AP_DPP8(q, 0x4E);
-    s += AP_DPP8(s, 0x141); q += AP_DPP8(q, 0x141);
-#undef AP_DPP8
+    s = sum8(s);
+    q = sum8(q);
     if (!live || l8 != 0) return;
     const double mean = (double)s / dim;
     double var = (double)q / dim - mean * mean;
@@ -538,7 +474,7 @@ int launch_ln_typed(float* x, long stride, const LnAdds& add, int rows, int dim,
         if constexpr (std::is_same<TD, float>::value && std::is_same<TO, float>::value) {
             // the narrow kernel moves 16 bytes per lane: any pointer or row stride the C ABI hands over that is not
             // 16-byte aligned takes the general kernel (equal to f32 rounding; the SAM2 path, the only caller at these widths, is always aligned)
-            const bool vec_ok = ((((uintptr_t)x | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0) && stride % 4 == 0;
+            const bool vec_ok = aligned16(x, out, gamma, beta) && stride % 4 == 0;
             if (!add.d[0] && !add.d[1] && vec_ok) {
 #define AP_LN_NARROW(DIM, LPR, NV)                                                                                       \
                 if (dim == DIM) {                                                                                        \
@@ -663,45 +599,6 @@ __global__ void chw_to_patchrows_any_kernel(const TI* __restrict__ x, int n, int
 // DINOv3 rotary embedding, in place on q / k of the packed qkv (see ap_common.h).  One thread = 8 consecutive channels j .. j + 7 of
 // the first half of one head together with their partners j + h .. in the second half (two 16-byte accesses each way for the
 // 16-bit types); unit index = ((row * parts + part) * heads + head) * (h / 8) + chunk.
-template <typename T> struct Rope8 { };
-template <> struct Rope8<float> {
-    static __device__ __forceinline__ void load(const float* p, float* v) {
-        const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { v[e] = a[e]; v[4 + e] = b[e]; }
-    }
-    static __device__ __forceinline__ void store(float* p, const float* v) {
-        *(f32x4*)p = f32x4{v[0], v[1], v[2], v[3]};
-        *(f32x4*)(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
-    }
-};
-template <> struct Rope8<f16> {
-    static __device__ __forceinline__ void load(const f16* p, float* v) {
-        const f16x8 a = *(const f16x8*)p;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (float)a[e];
-    }
-    static __device__ __forceinline__ void store(f16* p, const float* v) {
-        f16x8 a;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) a[e] = (f16)v[e];
-        *(f16x8*)p = a;
-    }
-};
-template <> struct Rope8<bf16> {
-    static __device__ __forceinline__ void load(const bf16* p, float* v) {
-        const bf16x8 a = *(const bf16x8*)p;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (float)a[e];
-    }
-    static __device__ __forceinline__ void store(bf16* p, const float* v) {
-        bf16x8 a;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) a[e] = (bf16)v[e];
-        *(bf16x8*)p = a;
-    }
-};
-
 template <typename T>
 __global__ __launch_bounds__(256) void rope_kernel(T* __restrict__ qkv, long units, int tokens, int prefix, int heads, int hd,
                                                    const float* __restrict__ cosv, const float* __restrict__ sinv, int part0, int parts) {
@@ -720,15 +617,15 @@ __global__ __launch_bounds__(256) void rope_kernel(T* __restrict__ qkv, long uni
     const float* c = cosv + (long)pidx * hd + chunk * 8;
     const float* s = sinv + (long)pidx * hd + chunk * 8;
     float a[8], b[8], o1[8], o2[8];
-    Rope8<T>::load(x, a);
-    Rope8<T>::load(x + h, b);
+    load8(x, a);
+    load8(x + h, b);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         o1[e] = a[e] * c[e] - b[e] * s[e];
         o2[e] = b[e] * c[h + e] + a[e] * s[h + e];
     }
-    Rope8<T>::store(x, o1);
-    Rope8<T>::store(x + h, o2);
+    store8(x, o1);
+    store8(x + h, o2);
 }
 
 // AP_POOL_CLS_MEAN (midnight.py:58-61, virchow.py:58-61): one thread per (image, channel); the patch rows are summed in row
@@ -757,15 +654,17 @@ int launch_add2_layernorm(int delta_dtype, int out_dtype, float* x, long stride,
     if (rows <= 0) return AP_OK;
     if (!delta0 && !delta1) delta_dtype = out_dtype;
     const LnAdds add{{delta0, delta1}, {dstride0, dstride1}, {ls0, ls1}, store};
-#define AP_LN(TD, TO) return launch_ln_typed<TD, TO>(x, stride, add, rows, dim, gamma, beta, eps, out, stream)
-    if (delta_dtype == AP_F16 && out_dtype == AP_F16) AP_LN(f16, f16);
-    if (delta_dtype == AP_BF16 && out_dtype == AP_BF16) AP_LN(bf16, bf16);
-    if (delta_dtype == AP_F32 && out_dtype == AP_F32) AP_LN(float, float);
-    if (delta_dtype == AP_F16 && out_dtype == AP_F32) AP_LN(f16, float);
-    if (delta_dtype == AP_BF16 && out_dtype == AP_F32) AP_LN(bf16, float);
-#undef AP_LN
-    set_error("layernorm: unsupported dtype pair (delta %d, out %d)", delta_dtype, out_dtype);
-    return AP_ERR_INVALID;
+    // (T, T), (T, f32) and (f32, f32)
+    AP_REQUIRE(out_dtype == AP_F32 ? known_dtype(delta_dtype) : half_dtype(out_dtype) && delta_dtype == out_dtype,
+               "layernorm: unsupported dtype pair (delta %d, out %d)", delta_dtype, out_dtype);
+    if (out_dtype == AP_F32)
+        return dispatch_dtype("layernorm", delta_dtype, [&](auto tag) {
+            return launch_ln_typed<typename decltype(tag)::type, float>(x, stride, add, rows, dim, gamma, beta, eps, out, stream);
+        });
+    return dispatch_half("layernorm", delta_dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        return launch_ln_typed<T, T>(x, stride, add, rows, dim, gamma, beta, eps, out, stream);
+    });
 }
 
 int launch_add_layernorm(int delta_dtype, int out_dtype, float* x, long stride, const void* delta,
@@ -792,13 +691,11 @@ int launch_stream_init(int dtype, const float* tok, int rows, int dim, float eps
     if (rows <= 0) return AP_OK;
     dim3 grid((rows + 3) / 4), block(256);
     const bool wide = dim > 64 * 4 * kMaxVec;
-    if (dtype == AP_F16 && !wide) stream_init_kernel<f16, kMaxVec><<<grid, block, 0, stream>>>(tok, rows, dim, eps, (f16*)x, rowstats);
-    else if (dtype == AP_F16) stream_init_kernel<f16, kMaxVecWide><<<grid, block, 0, stream>>>(tok, rows, dim, eps, (f16*)x, rowstats);
-    else if (dtype == AP_BF16 && !wide) stream_init_kernel<bf16, kMaxVec><<<grid, block, 0, stream>>>(tok, rows, dim, eps, (bf16*)x, rowstats);
-    else if (dtype == AP_BF16) stream_init_kernel<bf16, kMaxVecWide><<<grid, block, 0, stream>>>(tok, rows, dim, eps, (bf16*)x, rowstats);
-    else { set_error("stream_init: dtype %d (f16 / bf16 only)", dtype); return AP_ERR_INVALID; }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_half("stream_init", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        const auto kernel = wide ? stream_init_kernel<T, kMaxVecWide> : stream_init_kernel<T, kMaxVec>;
+        kernel<<<grid, block, 0, stream>>>(tok, rows, dim, eps, (T*)x, rowstats);
+    });
 }
 
 int launch_cls_stream(int dtype, const float* prefix, int prefix_rows, int img_rows, int n, int tokens, int dim, void* x, float* partial,
@@ -806,11 +703,10 @@ int launch_cls_stream(int dtype, const float* prefix, int prefix_rows, int img_r
     AP_REQUIRE(dim % 64 == 0 && prefix_rows > 0, "cls_stream: dim %d must be a multiple of 64", dim);
     if (n <= 0) return AP_OK;
     dim3 grid(n * prefix_rows, dim / 64), block(64);
-    if (dtype == AP_F16) cls_stream_kernel<f16><<<grid, block, 0, stream>>>(prefix, prefix_rows, img_rows, tokens, dim, (f16*)x, partial);
-    else if (dtype == AP_BF16) cls_stream_kernel<bf16><<<grid, block, 0, stream>>>(prefix, prefix_rows, img_rows, tokens, dim, (bf16*)x, partial);
-    else { set_error("cls_stream: dtype %d (f16 / bf16 only)", dtype); return AP_ERR_INVALID; }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_half("cls_stream", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        cls_stream_kernel<T><<<grid, block, 0, stream>>>(prefix, prefix_rows, img_rows, tokens, dim, (T*)x, partial);
+    });
 }
 
 int launch_cls_exact_update(int dtype, float* cls32, const float* branch, int n, int tokens, int dim, void* x, float* partial,
@@ -818,11 +714,10 @@ int launch_cls_exact_update(int dtype, float* cls32, const float* branch, int n,
     AP_REQUIRE(dim % 64 == 0, "cls_exact_update: dim %d must be a multiple of 64", dim);
     if (n <= 0) return AP_OK;
     dim3 grid(n, (dim + 255) / 256), block(256);
-    if (dtype == AP_F16) cls_exact_update_kernel<f16><<<grid, block, 0, stream>>>(cls32, branch, tokens, dim, (f16*)x, partial);
-    else if (dtype == AP_BF16) cls_exact_update_kernel<bf16><<<grid, block, 0, stream>>>(cls32, branch, tokens, dim, (bf16*)x, partial);
-    else { set_error("cls_exact_update: dtype %d (f16 / bf16 only)", dtype); return AP_ERR_INVALID; }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_half("cls_exact_update", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        cls_exact_update_kernel<T><<<grid, block, 0, stream>>>(cls32, branch, tokens, dim, (T*)x, partial);
+    });
 }
 
 int launch_rowstats_finalize(const float* partial, int rows, int groups, int dim, float eps, float* rowstats,
@@ -849,12 +744,10 @@ int launch_rope(int dtype, void* qkv, int n, int tokens, int prefix, int heads, 
     if (n <= 0) return AP_OK;
     const int part0 = (which & 1) ? 0 : 1, parts = (which & 3) == 3 ? 2 : 1;
     const long units = (long)n * (tokens - prefix) * parts * heads * (head_dim / 16);
-    dim3 grid((unsigned)((units + 255) / 256)), block(256);
-    if (dtype == AP_F16) rope_kernel<f16><<<grid, block, 0, stream>>>((f16*)qkv, units, tokens, prefix, heads, head_dim, cos, sin, part0, parts);
-    else if (dtype == AP_BF16) rope_kernel<bf16><<<grid, block, 0, stream>>>((bf16*)qkv, units, tokens, prefix, heads, head_dim, cos, sin, part0, parts);
-    else rope_kernel<float><<<grid, block, 0, stream>>>((float*)qkv, units, tokens, prefix, heads, head_dim, cos, sin, part0, parts);
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_dtype("rope", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        rope_kernel<T><<<grid_1d((size_t)units), 256, 0, stream>>>((T*)qkv, units, tokens, prefix, heads, head_dim, cos, sin, part0, parts);
+    });
 }
 
 int launch_cls_mean_pool(const float* y, int n, int tokens, int prefix, int dim, float* out, hipStream_t stream) {
@@ -869,38 +762,33 @@ int launch_cls_mean_pool(const float* y, int n, int tokens, int prefix, int dim,
 int launch_stream_to_f32(int dtype, const void* x, long stride, int rows, int dim, float* dst, hipStream_t stream) {
     AP_REQUIRE(dim % 4 == 0 && stride % 4 == 0, "stream_to_f32: dim / stride must be multiples of 4");
     if (rows <= 0) return AP_OK;
-    const size_t total = (size_t)rows * (dim >> 2);
-    const unsigned blocks = (unsigned)((total + 255) / 256);
-    if (dtype == AP_F16) stream_to_f32_kernel<f16><<<blocks, 256, 0, stream>>>((const f16*)x, stride, rows, dim, dst);
-    else if (dtype == AP_BF16) stream_to_f32_kernel<bf16><<<blocks, 256, 0, stream>>>((const bf16*)x, stride, rows, dim, dst);
-    else { set_error("stream_to_f32: dtype %d (f16 / bf16 only)", dtype); return AP_ERR_INVALID; }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_half("stream_to_f32", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        stream_to_f32_kernel<T><<<grid_1d((size_t)rows * (dim >> 2)), 256, 0, stream>>>((const T*)x, stride, rows, dim, dst);
+    });
 }
 
 int launch_fold_ln(int dtype, const float* w32, int rows, int cols, int ld, const float* gamma, const float* beta,
                    const float* bias_in, void* wout, float* colsum, float* bias_out, hipStream_t stream, int swiglu_h) {
     AP_REQUIRE(swiglu_h == 0 || (rows == 2 * swiglu_h && swiglu_h % 32 == 0), "fold_ln: swiglu row order needs rows = 2 h, h %% 32 == 0");
-    if (dtype == AP_F16) fold_ln_kernel<f16><<<rows, 256, 0, stream>>>(w32, cols, ld, gamma, beta, bias_in, (f16*)wout, colsum, bias_out, swiglu_h);
-    else if (dtype == AP_BF16) fold_ln_kernel<bf16><<<rows, 256, 0, stream>>>(w32, cols, ld, gamma, beta, bias_in, (bf16*)wout, colsum, bias_out, swiglu_h);
-    else { set_error("fold_ln: dtype %d (f16 / bf16 only)", dtype); return AP_ERR_INVALID; }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_half("fold_ln", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        fold_ln_kernel<T><<<rows, 256, 0, stream>>>(w32, cols, ld, gamma, beta, bias_in, (T*)wout, colsum, bias_out, swiglu_h);
+    });
 }
 
 int launch_fold_ls(int dtype, const float* w32, int rows, int cols, int ld, const float* ls, const float* bias_in,
                    void* wout, float* bias_out, hipStream_t stream) {
-    if (dtype == AP_F16) fold_ls_kernel<f16><<<rows, 256, 0, stream>>>(w32, cols, ld, ls, bias_in, (f16*)wout, bias_out);
-    else if (dtype == AP_BF16) fold_ls_kernel<bf16><<<rows, 256, 0, stream>>>(w32, cols, ld, ls, bias_in, (bf16*)wout, bias_out);
-    else { set_error("fold_ls: dtype %d (f16 / bf16 only)", dtype); return AP_ERR_INVALID; }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_half("fold_ls", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        fold_ls_kernel<T><<<rows, 256, 0, stream>>>(w32, cols, ld, ls, bias_in, (T*)wout, bias_out);
+    });
 }
 
 int launch_cls_init(float* tok, const float* prefix, int prefix_rows, int n, int tokens, int dim, hipStream_t stream) {
     if (n <= 0) return AP_OK;
     const int total = n * prefix_rows * dim;
-    cls_init_kernel<<<(total + 255) / 256, 256, 0, stream>>>(tok, prefix, prefix_rows, n, tokens, dim);
+    cls_init_kernel<<<grid_1d(total), 256, 0, stream>>>(tok, prefix, prefix_rows, n, tokens, dim);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }
@@ -908,7 +796,7 @@ int launch_cls_init(float* tok, const float* prefix, int prefix_rows, int n, int
 int launch_prefix_build(const float* cls, const float* reg, int reg_rows, const float* pos, int dim, float* prefix, hipStream_t stream) {
     AP_REQUIRE(cls && prefix && (reg || reg_rows == 0), "prefix_build: null pointer");
     const int total = (1 + reg_rows) * dim;
-    prefix_build_kernel<<<(total + 255) / 256, 256, 0, stream>>>(cls, reg, reg_rows, pos, dim, prefix);
+    prefix_build_kernel<<<grid_1d(total), 256, 0, stream>>>(cls, reg, reg_rows, pos, dim, prefix);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }
@@ -917,33 +805,31 @@ int launch_swiglu(int dtype, const void* x, int rows, int h, void* out, hipStrea
     AP_REQUIRE(x && out && h > 0 && h % 8 == 0, "swiglu: bad arguments (h %d)", h);
     if (rows <= 0) return AP_OK;
     const size_t total = dtype == AP_F32 ? (size_t)rows * h : (size_t)rows * (h >> 3);
-    const unsigned blocks = (unsigned)((total + 255) / 256);
-    if (dtype == AP_F16) swiglu_kernel<f16><<<blocks, 256, 0, stream>>>((const f16*)x, rows, h, (f16*)out);
-    else if (dtype == AP_BF16) swiglu_kernel<bf16><<<blocks, 256, 0, stream>>>((const bf16*)x, rows, h, (bf16*)out);
-    else if (dtype == AP_F32) swiglu_f32_kernel<<<blocks, 256, 0, stream>>>((const float*)x, rows, h, (float*)out);
-    else { set_error("swiglu: dtype %d", dtype); return AP_ERR_INVALID; }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_dtype("swiglu", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if constexpr (std::is_same_v<T, float>) swiglu_f32_kernel<<<grid_1d(total), 256, 0, stream>>>((const float*)x, rows, h, (float*)out);
+        else swiglu_kernel<T><<<grid_1d(total), 256, 0, stream>>>((const T*)x, rows, h, (T*)out);
+    });
 }
 
 int launch_convert(int dtype, const float* src, void* dst, size_t count, hipStream_t stream) {
     if (count == 0) return AP_OK;
-    const int blocks = (int)((count + 255) / 256 < 4096 ? (count + 255) / 256 : 4096);
-    switch (dtype) {
-        case AP_F16: convert_kernel<f16><<<blocks, 256, 0, stream>>>(src, (f16*)dst, count); break;
-        case AP_BF16: convert_kernel<bf16><<<blocks, 256, 0, stream>>>(src, (bf16*)dst, count); break;
-        case AP_F32: AP_HIP_CHECK(hipMemcpyAsync(dst, src, count * 4, hipMemcpyDeviceToDevice, stream)); return AP_OK;
-        default: set_error("convert: unknown dtype %d", dtype); return AP_ERR_INVALID;
-    }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_dtype("convert", dtype, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        if constexpr (std::is_same_v<T, float>) {
+            AP_HIP_CHECK(hipMemcpyAsync(dst, src, count * 4, hipMemcpyDeviceToDevice, stream));
+        } else {
+            convert_kernel<T><<<grid_1d(count, 4096), 256, 0, stream>>>(src, (T*)dst, count);
+            AP_HIP_CHECK(hipGetLastError());
+        }
+        return AP_OK;
+    });
 }
 
 int launch_split_f16_weights(const float* src, void* dst, size_t count, hipStream_t stream) {
     AP_REQUIRE(src && dst && count % 32 == 0 && (const void*)src != dst, "split_f16_weights: count %zu must be a multiple of 32, out of place", count);
     if (count == 0) return AP_OK;
-    const int blocks = (int)((count + 255) / 256 < 4096 ? (count + 255) / 256 : 4096);
-    split_f16_kernel<<<blocks, 256, 0, stream>>>(src, (f16*)dst, count);
+    split_f16_kernel<<<grid_1d(count, 4096), 256, 0, stream>>>(src, (f16*)dst, count);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }
@@ -953,40 +839,26 @@ static int chw_rows_typed(int dtype, const TI* x, int n, int S, int ps, void* ds
                           hipStream_t stream) {
     const int g = S / ps;
     if (ps % 4 != 0) {
-        const size_t total_any = (size_t)n * 3 * S * S;
-        const unsigned blocks_any = (unsigned)((total_any + 255) / 256);
-        switch (dtype) {
-            case AP_F16: chw_to_patchrows_any_kernel<TI, f16><<<blocks_any, 256, 0, stream>>>(x, n, S, ps, (f16*)dst, ld); break;
-            case AP_BF16: chw_to_patchrows_any_kernel<TI, bf16><<<blocks_any, 256, 0, stream>>>(x, n, S, ps, (bf16*)dst, ld); break;
-            case AP_F32: chw_to_patchrows_any_kernel<TI, float><<<blocks_any, 256, 0, stream>>>(x, n, S, ps, (float*)dst, ld); break;
-            default: set_error("chw_to_patchrows: unknown dtype %d", dtype); return AP_ERR_INVALID;
-        }
-        AP_HIP_CHECK(hipGetLastError());
-        return AP_OK;
+        return dispatch_dtype("chw_to_patchrows", dtype, [&](auto tag) {
+            using TO = typename decltype(tag)::type;
+            chw_to_patchrows_any_kernel<TI, TO><<<grid_1d((size_t)n * 3 * S * S), 256, 0, stream>>>(x, n, S, ps, (TO*)dst, ld);
+        });
     }
-    const size_t total = (size_t)n * 3 * S * g * (ps >> 2);
-    const unsigned blocks = (unsigned)((total + 255) / 256);
-    switch (dtype) {
-        case AP_F16: chw_to_patchrows_kernel<TI, f16><<<blocks, 256, 0, stream>>>(x, n, S, ps, (f16*)dst, ld); break;
-        case AP_BF16: chw_to_patchrows_kernel<TI, bf16><<<blocks, 256, 0, stream>>>(x, n, S, ps, (bf16*)dst, ld); break;
-        case AP_F32: chw_to_patchrows_kernel<TI, float><<<blocks, 256, 0, stream>>>(x, n, S, ps, (float*)dst, ld); break;
-        default: set_error("chw_to_patchrows: unknown dtype %d", dtype); return AP_ERR_INVALID;
-    }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_dtype("chw_to_patchrows", dtype, [&](auto tag) {
+        using TO = typename decltype(tag)::type;
+        chw_to_patchrows_kernel<TI, TO><<<grid_1d((size_t)n * 3 * S * g * (ps >> 2)), 256, 0, stream>>>(x, n, S, ps, (TO*)dst, ld);
+    });
 }
 
 int launch_chw_to_patchrows(int x_dtype, int dtype, const void* x, int n, int S, int ps, void* dst,
                             int ld, hipStream_t stream) {
     AP_REQUIRE(S % ps == 0, "chw_to_patchrows: image %d / patch %d unsupported", S, ps);
     if (n <= 0) return AP_OK;
-    switch (x_dtype) {
-        case AP_F32: return chw_rows_typed<float>(dtype, (const float*)x, n, S, ps, dst, ld, stream);
-        case AP_F16: return chw_rows_typed<f16>(dtype, (const f16*)x, n, S, ps, dst, ld, stream);
-        case AP_BF16: return chw_rows_typed<bf16>(dtype, (const bf16*)x, n, S, ps, dst, ld, stream);
-    }
-    set_error("chw_to_patchrows: unknown input dtype %d", x_dtype);
-    return AP_ERR_INVALID;
+    if (!known_dtype(x_dtype)) { set_error("chw_to_patchrows: unknown input dtype %d", x_dtype); return AP_ERR_INVALID; }
+    return dispatch_dtype("chw_to_patchrows", x_dtype, [&](auto tag) {
+        using TI = typename decltype(tag)::type;
+        return chw_rows_typed<TI>(dtype, (const TI*)x, n, S, ps, dst, ld, stream);
+    });
 }
 
 }  // namespace ap

@@ -31,7 +31,6 @@
 //    dispatch) is defined once for this kernel and gemm256.hip in gemm_epilogue.h; the codes: GemmEpilogue in ap_common.h.
 //
 // Roofline: MFMA (2*M*N*K flop); HBM traffic ~ A once + output once (weights L2-resident).
-#include "ap_common.h"
 #include "gemm_mma.h"
 
 namespace ap {
@@ -41,17 +40,6 @@ constexpr int kTile = 128;            // BM = BN
 constexpr int kRowBytes = 128;        // bytes of K per tile row
 constexpr int kTileBytes = kTile * kRowBytes;   // 16 KiB per operand tile
 constexpr int kBufBytes = 2 * kTileBytes;       // W tile + A tile
-
-template <typename T> __device__ __forceinline__ void store4(T* p, f32x4 v);
-template <> __device__ __forceinline__ void store4<float>(float* p, f32x4 v) { *(f32x4*)p = v; }
-template <> __device__ __forceinline__ void store4<f16>(f16* p, f32x4 v) {
-    f16x4 h = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
-    *(f16x4*)p = h;
-}
-template <> __device__ __forceinline__ void store4<bf16>(bf16* p, f32x4 v) {
-    bf16x4 h = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-    *(bf16x4*)p = h;
-}
 
 // ---- fused-LayerNorm epilogues (twins of gemm256.hip's, bit for bit: a problem may be served by either kernel; the
 // arithmetic both call is in gemm_epilogue.h) ----
@@ -279,7 +267,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
                     const f32x2_t a = swiglu2(f32x2_t{y0[0], y0[1]}, f32x2_t{y1[0], y1[1]});
                     const f32x2_t b = swiglu2(f32x2_t{y0[2], y0[3]}, f32x2_t{y1[2], y1[3]});
                     const int nout = ((n0 + wave_n * 64) >> 1) + g4 * 8 + hi * 4;
-                    store4<T>((T*)g.out + (size_t)m * (size_t)g.ldo + nout, f32x4{a[0], a[1], b[0], b[1]});
+                    store_vec4<T>((T*)g.out + (size_t)m * (size_t)g.ldo + nout, f32x4{a[0], a[1], b[0], b[1]});
                 }
             } else {
 #pragma unroll
@@ -287,7 +275,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
 #pragma unroll
                     for (int g4 = 0; g4 < 4; ++g4) {
                         const int n = n0 + wave_n * 64 + nt * 32 + g4 * 8 + hi * 4;
-                        store4<T>((T*)g.out + (size_t)m * (size_t)g.ldo + n, act4<kAct>(norm4(n, acc4(nt, mt, g4))));
+                        store_vec4<T>((T*)g.out + (size_t)m * (size_t)g.ldo + n, act4<kAct>(norm4(n, acc4(nt, mt, g4))));
                     }
             }
         }
@@ -394,7 +382,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[e] *= ga[e];
                     }
-                    store4<T>((T*)g.out + orow + n, v);
+                    store_vec4<T>((T*)g.out + orow + n, v);
                 } else if constexpr (kAct != ACT_NONE && !epi_is_norm(EPI)) {      // EPI_BIAS_<activation>
                     if constexpr (sizeof(T) == 2) {      // the packed routines of gemm256: the two kernels stay bit-identical
                         v = act4<kAct>(v);
@@ -402,7 +390,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[e] = act_f32<kAct>(v[e]);
                     }
-                    store4<T>((T*)g.out + orow + n, v);
+                    store_vec4<T>((T*)g.out + orow + n, v);
                 } else if constexpr (EPI == EPI_BIAS_RESID) {
                     float* dst = (float*)g.out + orow + n;
                     f32x4 r = *(const f32x4*)dst;
@@ -483,13 +471,7 @@ int launch_gemm_impl(int dtype, int epilogue, const GemmArgs& a, int impl, int v
         AP_REQUIRE(dtype == AP_F32, "gemm: the split-f16 product runs on float32 buffers");
         return launch_typed<float, true>(epilogue, a, stream);
     }
-    switch (dtype) {
-        case AP_F16: return launch_typed<f16>(epilogue, a, stream);
-        case AP_BF16: return launch_typed<bf16>(epilogue, a, stream);
-        case AP_F32: return launch_typed<float>(epilogue, a, stream);
-    }
-    set_error("gemm: unknown dtype %d", dtype);
-    return AP_ERR_INVALID;
+    return dispatch_dtype("gemm", dtype, [&](auto tag) { return launch_typed<typename decltype(tag)::type>(epilogue, a, stream); });
 }
 
 }  // namespace ap

@@ -61,7 +61,6 @@
 //    activation panels and weight panels in that XCD's L2.
 //
 // Roofline: MFMA (2*M*N*K flop per launch).
-#include "ap_common.h"
 #include "gemm_mma.h"
 
 // The file is compiled twice: the product build, and (-DAP_G256_ALT) a twin that ap_gemm reaches as impl 257, so a
@@ -848,8 +847,7 @@ int AP_G256_FN(launch_gemm256)(int dtype, int epilogue, const GemmArgs& a, int v
     }
     if ((variant >> 16) & 15) b.walk_cols = (variant >> 16) & 15;
     variant &= 15;
-    return dtype == AP_F16 ? launch_typed<f16>(epilogue, b, num_cu, variant, stream)
-                           : launch_typed<bf16>(epilogue, b, num_cu, variant, stream);
+    return dispatch_half("gemm256", dtype, [&](auto tag) { return launch_typed<typename decltype(tag)::type>(epilogue, b, num_cu, variant, stream); });
 }
 
 }  // namespace ap

@@ -5,39 +5,11 @@
 // accumulators of the two shapes are bit-identical for the same operands in ascending k (same probe), which is why the
 // 128 x 128 kernel (gemm.hip) can stay on 32x32x16 and still agree with this one bit for bit.
 #pragma once
-#include "ap_common.h"
+#include "kernel_util.h"
 #include "gemm_epilogue.h"
 
 namespace ap {
 namespace {
-
-template <typename T> struct Mma32x32;     // gemm.hip
-template <> struct Mma32x32<f16> {
-    using Frag = f16x8;
-    static __device__ __forceinline__ f32x16 run(Frag a, Frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Mma32x32<bf16> {
-    using Frag = bf16x8;
-    static __device__ __forceinline__ f32x16 run(Frag a, Frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-};
-
-template <typename T> struct Mma16x16;   // gemm256.hip
-template <> struct Mma16x16<f16> {
-    using Frag = f16x8;
-    static __device__ __forceinline__ f32x4 run(Frag a, Frag b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Mma16x16<bf16> {
-    using Frag = bf16x8;
-    static __device__ __forceinline__ f32x4 run(Frag a, Frag b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    }
-};
 
 // Operand map of Mma16x16<T>::run(a, b, c): lane l supplies row l & 15 of either operand, k = 8 (l >> 4) + j (j = 0..7 of the Frag), and
 // receives c[e] = C[first-operand row 4 (l >> 4) + e][second-operand row l & 15].
@@ -53,15 +25,6 @@ struct AccMap {
     __device__ __forceinline__ int m(int g) const { return mh(g) * 16 + l15; }
     __device__ __forceinline__ int n(int g) const { return nh(g) * 16 + q * 4; }
 };
-
-#define AP_DPP_F32(V, CTRL) __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, (V)), (CTRL), 0xF, 0xF, true))
-// sum over the 8 lanes that share (lane >> 3): xor-1, xor-2 (quad permutes), mirror within 8 -- every lane gets the total
-__device__ __forceinline__ float sum8(float v) {
-    v += AP_DPP_F32(v, 0xB1);
-    v += AP_DPP_F32(v, 0x4E);
-    v += AP_DPP_F32(v, 0x141);
-    return v;
-}
 
 // EPI_RESID_STATS element step on 8 packed values: y = T(d + r) (d = the branch output already rounded to T, r = the
 // stream), s += sum(y), q += sum(y^2) in f32, ONE chain over the four dwords.

@@ -18,7 +18,7 @@
 // (f16) = 451 584; counting the whole 196 608-byte tile as read: 497 664.
 #include <mutex>
 #include <vector>
-#include "ap_common.h"
+#include "kernel_util.h"
 
 namespace ap {
 namespace {
@@ -35,17 +35,13 @@ struct PreArgs {
     int band;                 // rows per block (= ps for patch rows)
 };
 
-template <typename T> struct Out8;     // 8 consecutive outputs
-template <> struct Out8<f16> { using vec = f16x8; };
-template <> struct Out8<bf16> { using vec = bf16x8; };
-
 template <typename T>
-__device__ __forceinline__ void store8(T* p, const T* v) {
+__device__ __forceinline__ void store8t(T* p, const T* v) {        // 8 consecutive outputs, already in T
     if constexpr (sizeof(T) == 2) {
-        typename Out8<T>::vec o;
+        typename Vec16<T>::type o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = v[e];
-        *(typename Out8<T>::vec*)p = o;
+        *(typename Vec16<T>::type*)p = o;
     } else {
         f32x4 a = {v[0], v[1], v[2], v[3]}, b = {v[4], v[5], v[6], v[7]};
         ((f32x4*)p)[0] = a;
@@ -129,7 +125,7 @@ __global__ __launch_bounds__(256) void preproc_kernel(PreArgs a) {
                 T v[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = lut[c * 256 + b[e * 3 + c]];
-                store8<T>(drow + (c * a.ps + ky) * a.ps + hf * 8, v);
+                store8t<T>(drow + (c * a.ps + ky) * a.ps + hf * 8, v);
             }
         }
     } else {
@@ -144,7 +140,7 @@ __global__ __launch_bounds__(256) void preproc_kernel(PreArgs a) {
                 T v[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = lut[c * 256 + b[e * 3 + c]];
-                store8<T>((T*)a.dst + (((size_t)img * 3 + c) * a.oh + (y0 + r)) * (size_t)a.ow + gx * 8, v);
+                store8t<T>((T*)a.dst + (((size_t)img * 3 + c) * a.oh + (y0 + r)) * (size_t)a.ow + gx * 8, v);
             }
         }
     }
@@ -236,13 +232,7 @@ int preproc_common(int layout, const uint8_t* src, int n, int h, int w, int top,
     }
     int rc = get_norm_lut(mean, stdv, dtype, stream, &a.lut);
     if (rc != AP_OK) return rc;
-    switch (dtype) {
-        case AP_F16: return launch_pre<f16>(layout, a, stream);
-        case AP_BF16: return launch_pre<bf16>(layout, a, stream);
-        case AP_F32: return launch_pre<float>(layout, a, stream);
-    }
-    set_error("preproc: unknown dtype %d", dtype);
-    return AP_ERR_INVALID;
+    return dispatch_dtype("preproc", dtype, [&](auto tag) { return launch_pre<typename decltype(tag)::type>(layout, a, stream); });
 }
 
 }  // namespace

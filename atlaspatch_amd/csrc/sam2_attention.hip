@@ -30,7 +30,7 @@
 // loads, same fragment assignment (a lane's eight k slots of a 16-deep step are two of its 16-byte vectors), same softmax.
 //
 // Roofline: f32 MFMA, 4 * tq * tk * d flop per head (split form: three times that on the f16 MFMA).
-#include "ap_common.h"
+#include "kernel_util.h"
 
 namespace ap {
 namespace {
@@ -251,7 +251,7 @@ int launch_sattention(const float* q, long ldq, const float* k, long ldk, const 
     AP_REQUIRE(q && k && v && out && batch > 0 && batch <= 65535, "sattention: bad arguments");
     AP_REQUIRE(sattention_supports(heads, tq, tk, d, ldq, ldk, ldv, ldo),
                "sattention: unsupported shape (d 32 / 64 / 96, row strides multiples of 4 floats)");
-    AP_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)out) & 15) == 0, "sattention: q / k / out must be 16-byte aligned");
+    AP_REQUIRE(aligned16(q, k, out), "sattention: q / k / out must be 16-byte aligned");
     SAttnArgs a{q, k, v, out, ldq, ldk, ldv, ldo, tq, tk, scale * 1.4426950408889634f};
     dim3 grid((tq + 31) / 32, heads, batch), block(256);
     if (exact) {

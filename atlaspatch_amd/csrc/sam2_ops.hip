@@ -16,7 +16,7 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
-#include "ap_common.h"
+#include "kernel_util.h"
 
 namespace ap {
 namespace {
@@ -277,16 +277,14 @@ __global__ __launch_bounds__(256) void softmax_rows_reg_kernel(float* x, long ld
         v[i] = c < cols ? p[c] : -INFINITY;
         mx = fmaxf(mx, v[i]);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    mx = wave_max(mx);
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         v[i] = expf(v[i] - mx);           // exp(-inf) = 0 for the padding lanes
         s += v[i];
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = wave_sum(s);
     const float inv = 1.0f / s;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -301,16 +299,14 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float* x, long ld, in
     float* p = x + (size_t)row * ld;
     float mx = -INFINITY;
     for (int c = lane; c < cols; c += 64) mx = fmaxf(mx, p[c]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    mx = wave_max(mx);
     float s = 0.f;
     for (int c = lane; c < cols; c += 64) {
         const float e = expf(p[c] - mx);
         p[c] = e;
         s += e;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = wave_sum(s);
     const float inv = 1.0f / s;
     for (int c = lane; c < cols; c += 64) p[c] *= inv;
 }
@@ -437,7 +433,6 @@ __global__ void bilinear_up4_threshold_kernel(const float* lg, int S, float thr,
     mask[i] = v > thr ? 1.0f : 0.0f;
 }
 
-inline dim3 grid1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace
 }  // namespace ap
@@ -457,7 +452,7 @@ static int sgemm_impl(const float* A, long lda, long strideA, const float* W, lo
     AP_REQUIRE(act >= 0 && act <= 2, "ap_sgemm: activation %d", act);
     ap::SgemmArgs g{A, lda, strideA, W, ldw, strideW, w_is_kn, M, N, K, alpha, bias, act, resid, ldr, strideR, out, ldo, strideO,
                     0, 1, K, nullptr};
-    const bool al16 = (((uintptr_t)A | (uintptr_t)W) & 15) == 0 && lda % 4 == 0 && ldw % 4 == 0 && strideA % 4 == 0 && strideW % 4 == 0;
+    const bool al16 = ap::aligned16(A, W) && lda % 4 == 0 && ldw % 4 == 0 && strideA % 4 == 0 && strideW % 4 == 0;
     g.vec = al16 && (w_is_kn || K % 4 == 0) ? 1 : 0;
     // tile (M x N): 128 x 128 when that still gives every CU two workgroups, else 64 x 64.  (A 128 x 64 tile was measured
     // too: M = 4096, N = 1536, K = 384 went from 62.9 to 74.6 us -- two workgroups per CU instead of four cost more than
@@ -514,7 +509,7 @@ static int sgemm_impl(const float* A, long lda, long strideA, const float* W, lo
 #undef AP_SGEMM_TILE
 #undef AP_SGEMM_LAUNCH
     if (splits > 1)
-        ap::splitk_reduce_kernel<<<ap::grid1((size_t)batch * M * N), 256, 0, s>>>(g, batch);
+        ap::splitk_reduce_kernel<<<ap::grid_1d((size_t)batch * M * N), 256, 0, s>>>(g, batch);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }
@@ -558,7 +553,7 @@ int ap_sam2_patchify(const uint8_t* image, int h, int w, const float mean[3], co
                      ap_stream_t stream) {
     AP_REQUIRE(image && out && mean && stdv && h > 0 && w > 0 && h % 4 == 0 && w % 4 == 0, "ap_sam2_patchify: bad arguments");
     const int OH = h / 4, OW = w / 4;
-    ap::patchify_kernel<<<ap::grid1((size_t)OH * OW * 147), 256, 0, (hipStream_t)stream>>>(
+    ap::patchify_kernel<<<ap::grid_1d((size_t)OH * OW * 147), 256, 0, (hipStream_t)stream>>>(
         image, h, w, out, OH, OW, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2]);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
@@ -567,7 +562,7 @@ int ap_sam2_patchify(const uint8_t* image, int h, int w, const float mean[3], co
 int ap_window_partition(const float* x, int b, int h, int w, int c, int ws, float* win, ap_stream_t stream) {
     AP_REQUIRE(x && win && ws > 0, "ap_window_partition: bad arguments");
     const int nwy = (h + ws - 1) / ws, nwx = (w + ws - 1) / ws;
-    ap::window_partition_kernel<<<ap::grid1((size_t)b * nwy * nwx * ws * ws * c), 256, 0, (hipStream_t)stream>>>(
+    ap::window_partition_kernel<<<ap::grid_1d((size_t)b * nwy * nwx * ws * ws * c), 256, 0, (hipStream_t)stream>>>(
         x, b, h, w, c, ws, nwy, nwx, win);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
@@ -576,7 +571,7 @@ int ap_window_partition(const float* x, int b, int h, int w, int c, int ws, floa
 int ap_window_unpartition(const float* win, int b, int h, int w, int c, int ws, float* x, ap_stream_t stream) {
     AP_REQUIRE(x && win && ws > 0, "ap_window_unpartition: bad arguments");
     const int nwy = (h + ws - 1) / ws, nwx = (w + ws - 1) / ws;
-    ap::window_unpartition_kernel<<<ap::grid1((size_t)b * h * w * c), 256, 0, (hipStream_t)stream>>>(
+    ap::window_unpartition_kernel<<<ap::grid_1d((size_t)b * h * w * c), 256, 0, (hipStream_t)stream>>>(
         win, nullptr, b, h, w, c, ws, nwy, nwx, x);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
@@ -586,7 +581,7 @@ int ap_window_unpartition_add(const float* win, const float* resid, int b, int h
                               ap_stream_t stream) {
     AP_REQUIRE(x && win && resid && ws > 0, "ap_window_unpartition_add: bad arguments");
     const int nwy = (h + ws - 1) / ws, nwx = (w + ws - 1) / ws;
-    ap::window_unpartition_kernel<<<ap::grid1((size_t)b * h * w * c), 256, 0, (hipStream_t)stream>>>(
+    ap::window_unpartition_kernel<<<ap::grid_1d((size_t)b * h * w * c), 256, 0, (hipStream_t)stream>>>(
         win, resid, b, h, w, c, ws, nwy, nwx, x);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
@@ -594,35 +589,35 @@ int ap_window_unpartition_add(const float* win, const float* resid, int b, int h
 
 int ap_maxpool2x2(const float* in, long ld_in, int b, int h, int w, int c, float* out, ap_stream_t stream) {
     AP_REQUIRE(in && out && h % 2 == 0 && w % 2 == 0 && ld_in >= c, "ap_maxpool2x2: bad arguments");
-    ap::maxpool2x2_kernel<<<ap::grid1((size_t)b * (h / 2) * (w / 2) * c), 256, 0, (hipStream_t)stream>>>(in, ld_in, b, h, w, c, out);
+    ap::maxpool2x2_kernel<<<ap::grid_1d((size_t)b * (h / 2) * (w / 2) * c), 256, 0, (hipStream_t)stream>>>(in, ld_in, b, h, w, c, out);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }
 
 int ap_add(float* out, const float* a, const float* b, size_t n, ap_stream_t stream) {
     AP_REQUIRE(out && a && b, "ap_add: null pointer");
-    if (n) ap::add_kernel<<<ap::grid1(n), 256, 0, (hipStream_t)stream>>>(out, a, b, n);
+    if (n) ap::add_kernel<<<ap::grid_1d(n), 256, 0, (hipStream_t)stream>>>(out, a, b, n);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }
 
 int ap_add_rowvec(float* out, const float* a, const float* vec, size_t rows, int cols, ap_stream_t stream) {
     AP_REQUIRE(out && a && vec && cols > 0, "ap_add_rowvec: bad arguments");
-    if (rows) ap::add_rowvec_kernel<<<ap::grid1(rows * cols), 256, 0, (hipStream_t)stream>>>(out, a, vec, rows, cols);
+    if (rows) ap::add_rowvec_kernel<<<ap::grid_1d(rows * cols), 256, 0, (hipStream_t)stream>>>(out, a, vec, rows, cols);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }
 
 int ap_gelu(float* x, size_t n, ap_stream_t stream) {
     AP_REQUIRE(x, "ap_gelu: null pointer");
-    if (n) ap::gelu_kernel<<<ap::grid1(n), 256, 0, (hipStream_t)stream>>>(x, n);
+    if (n) ap::gelu_kernel<<<ap::grid_1d(n), 256, 0, (hipStream_t)stream>>>(x, n);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }
 
 int ap_upsample2x_add(float* out, const float* lateral, const float* prev, int h, int w, int c, ap_stream_t stream) {
     AP_REQUIRE(out && lateral && prev, "ap_upsample2x_add: null pointer");
-    ap::upsample2x_add_kernel<<<ap::grid1((size_t)4 * h * w * c), 256, 0, (hipStream_t)stream>>>(out, lateral, prev, h, w, c);
+    ap::upsample2x_add_kernel<<<ap::grid_1d((size_t)4 * h * w * c), 256, 0, (hipStream_t)stream>>>(out, lateral, prev, h, w, c);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }
@@ -630,14 +625,14 @@ int ap_upsample2x_add(float* out, const float* lateral, const float* prev, int h
 int ap_convt2x2_shuffle(const float* g, const float* bias, const float* skip, float* out, int h, int w, int cout,
                         int act, ap_stream_t stream) {
     AP_REQUIRE(g && bias && out, "ap_convt2x2_shuffle: null pointer");
-    ap::convt_shuffle_kernel<<<ap::grid1((size_t)4 * h * w * cout), 256, 0, (hipStream_t)stream>>>(g, bias, skip, out, h, w, cout, act);
+    ap::convt_shuffle_kernel<<<ap::grid_1d((size_t)4 * h * w * cout), 256, 0, (hipStream_t)stream>>>(g, bias, skip, out, h, w, cout, act);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }
 
 int ap_bilinear_up4_threshold(const float* logits, int size, float threshold, float* mask, ap_stream_t stream) {
     AP_REQUIRE(logits && mask && size > 1, "ap_bilinear_up4_threshold: bad arguments");
-    ap::bilinear_up4_threshold_kernel<<<ap::grid1((size_t)16 * size * size), 256, 0, (hipStream_t)stream>>>(logits, size, threshold, mask);
+    ap::bilinear_up4_threshold_kernel<<<ap::grid_1d((size_t)16 * size * size), 256, 0, (hipStream_t)stream>>>(logits, size, threshold, mask);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }
@@ -645,7 +640,7 @@ int ap_bilinear_up4_threshold(const float* logits, int size, float threshold, fl
 int ap_gather2d_f32(const float* src, int src_h, int src_w, const int32_t* yidx, const int32_t* xidx, int oh, int ow, float* dst,
                     ap_stream_t stream) {
     AP_REQUIRE(src && yidx && xidx && dst && src_h > 0 && src_w > 0 && oh > 0 && ow > 0, "ap_gather2d_f32: bad arguments");
-    ap::gather2d_kernel<<<ap::grid1((size_t)oh * ow), 256, 0, (hipStream_t)stream>>>(src, src_w, yidx, xidx, oh, ow, dst);
+    ap::gather2d_kernel<<<ap::grid_1d((size_t)oh * ow), 256, 0, (hipStream_t)stream>>>(src, src_w, yidx, xidx, oh, ow, dst);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }

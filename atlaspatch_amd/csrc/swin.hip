@@ -28,8 +28,8 @@
 // patch_merge_ln: one wave per output pixel; channel chunk k of the 4C row comes from source pixel (2 oy + dy, 2 ox + dx) with
 // quadrant k / (C / 8) = dy + 2 dx (x[0::2,0::2] | x[1::2,0::2] | x[0::2,1::2] | x[1::2,1::2]); two-pass f32 statistics.
 #include <algorithm>
-#include "ap_common.h"
-#include "gemm_mma.h"
+#include "kernel_util.h"
+#include "gemm_epilogue.h"
 
 namespace ap {
 namespace {
@@ -276,38 +276,9 @@ __global__ __launch_bounds__(WA_WAVES * 64) void swin_window_attention_f32(WaArg
 }
 
 // ---- patch merging + LayerNorm
-template <typename T> __device__ __forceinline__ void load8(const T* p, float v[8]) {
-    if constexpr (sizeof(T) == 2) {
-        const u32x4 r = *(const u32x4*)p;
-        T e[8];
-        __builtin_memcpy(e, &r, 16);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = (float)e[i];
-    } else {
-        const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { v[i] = a[i]; v[4 + i] = b[i]; }
-    }
-}
-
-template <typename T> __device__ __forceinline__ void store8(T* p, const float v[8]) {
-    if constexpr (sizeof(T) == 2) {
-        T e[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) e[i] = from_f32<T>(v[i]);
-        u32x4 r;
-        __builtin_memcpy(&r, e, 16);
-        *(u32x4*)p = r;
-    } else {
-        *(f32x4*)p = f32x4{v[0], v[1], v[2], v[3]};
-        *(f32x4*)(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
-    }
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void patch_merge_ln(const T* x, long rows, int H, int W, int C, const float* g, const float* b,
                                                       float eps, T* out) {
-    const int lane = threadIdx.x & 63;
     const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;                                 // a whole wave
     const int Ho = H / 2, Wo = W / 2;
@@ -319,40 +290,8 @@ __global__ __launch_bounds__(256) void patch_merge_ln(const T* x, long rows, int
         const int quad = k / per;
         return base + ((size_t)(quad & 1) * W + (quad >> 1)) * C + (k - quad * per) * 8;
     };
-    float s = 0.f;
-    for (int k = lane; k < nch; k += 64) {
-        float v[8];
-        load8(chunk(k), v);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += v[e];
-    }
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-    const float mean = s / (float)(4 * C);
-    float ss = 0.f;
-    for (int k = lane; k < nch; k += 64) {
-        float v[8];
-        load8(chunk(k), v);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { const float d = v[e] - mean; ss = fmaf(d, d, ss); }
-    }
-    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o, 64);
-    const float rstd = 1.0f / sqrtf(ss / (float)(4 * C) + eps);
-    T* dst = out + (size_t)r * 4 * C;
-    for (int k = lane; k < nch; k += 64) {
-        float v[8], o[8];
-        load8(chunk(k), v);
-        const f32x4 g0 = *(const f32x4*)(g + k * 8), g1 = *(const f32x4*)(g + k * 8 + 4);
-        const f32x4 b0 = *(const f32x4*)(b + k * 8), b1 = *(const f32x4*)(b + k * 8 + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            o[e] = (v[e] - mean) * rstd * g0[e] + b0[e];
-            o[4 + e] = (v[4 + e] - mean) * rstd * g1[e] + b1[e];
-        }
-        store8(dst + k * 8, o);
-    }
+    wave_layernorm8(chunk, nch, 4 * C, g, b, eps, out + (size_t)r * 4 * C);
 }
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -364,7 +303,7 @@ int launch_swin_window_attention(int dtype, const void* qkv, int n, int h, int w
                "swin_window_attention: n %d h %d w %d (h and w multiples of the 7-token window)", n, h, w);
     AP_REQUIRE(heads >= 1 && heads <= 1024, "swin_window_attention: heads %d", heads);
     AP_REQUIRE(shift >= 0 && shift < WIN, "swin_window_attention: shift %d outside [0, 7)", shift);
-    AP_REQUIRE(aligned16(qkv) && aligned16(out), "swin_window_attention: pointers must be 16-byte aligned");
+    AP_REQUIRE(aligned16(qkv, out), "swin_window_attention: pointers must be 16-byte aligned");
     AP_REQUIRE(qkv != out, "swin_window_attention: in place is not supported");
     if (n == 0) return AP_OK;
     WaArgs a{};
@@ -377,17 +316,17 @@ int launch_swin_window_attention(int dtype, const void* qkv, int n, int h, int w
         const long blocks = (items + WA_WAVES - 1) / WA_WAVES;
         AP_REQUIRE(blocks < (long)1 << 31, "swin_window_attention: grid too large");
         swin_window_attention_f32<<<(unsigned)blocks, WA_WAVES * 64, 0, stream>>>(a);
-    } else {
-        // windows per wave: the head's bias table is loaded once per wave; short runs while the grid is small
-        a.wpw = (int)std::max<long>(1, std::min<long>(8, items / 4096));
-        a.ngroups = (a.nwin + a.wpw - 1) / a.wpw;
-        const long blocks = (a.ngroups * heads + WA_WAVES - 1) / WA_WAVES;
-        AP_REQUIRE(blocks < (long)1 << 31, "swin_window_attention: grid too large");
-        if (dtype == AP_F16) swin_window_attention_mma<f16><<<(unsigned)blocks, WA_WAVES * 64, 0, stream>>>(a);
-        else swin_window_attention_mma<bf16><<<(unsigned)blocks, WA_WAVES * 64, 0, stream>>>(a);
+        AP_HIP_CHECK(hipGetLastError());
+        return AP_OK;
     }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    // windows per wave: the head's bias table is loaded once per wave; short runs while the grid is small
+    a.wpw = (int)std::max<long>(1, std::min<long>(8, items / 4096));
+    a.ngroups = (a.nwin + a.wpw - 1) / a.wpw;
+    const long blocks = (a.ngroups * heads + WA_WAVES - 1) / WA_WAVES;
+    AP_REQUIRE(blocks < (long)1 << 31, "swin_window_attention: grid too large");
+    return dispatch_half("swin_window_attention", dtype, [&](auto tag) {
+        swin_window_attention_mma<typename decltype(tag)::type><<<(unsigned)blocks, WA_WAVES * 64, 0, stream>>>(a);
+    });
 }
 
 int launch_patch_merge_ln(int dtype, const void* x, int n, int h, int w, int c, const float* ln_weight, const float* ln_bias,
@@ -397,20 +336,16 @@ int launch_patch_merge_ln(int dtype, const void* x, int n, int h, int w, int c, 
     AP_REQUIRE(n >= 0 && h > 0 && w > 0 && h % 2 == 0 && w % 2 == 0 && c > 0 && c % 8 == 0,
                "patch_merge_ln: n %d h %d w %d c %d (h and w even, c %% 8 == 0)", n, h, w, c);
     AP_REQUIRE(eps > 0.f, "patch_merge_ln: eps %g", (double)eps);
-    AP_REQUIRE(aligned16(x) && aligned16(ln_weight) && aligned16(ln_bias) && aligned16(out),
-               "patch_merge_ln: pointers must be 16-byte aligned");
+    AP_REQUIRE(aligned16(x, ln_weight, ln_bias, out), "patch_merge_ln: pointers must be 16-byte aligned");
     AP_REQUIRE(x != out, "patch_merge_ln: in place is not supported");
     if (n == 0) return AP_OK;
     const long rows = (long)n * (h / 2) * (w / 2);
     const long blocks = (rows + 3) / 4;
     AP_REQUIRE(blocks < (long)1 << 31, "patch_merge_ln: grid too large");
-    switch (dtype) {
-        case AP_F16: patch_merge_ln<f16><<<(unsigned)blocks, 256, 0, stream>>>((const f16*)x, rows, h, w, c, ln_weight, ln_bias, eps, (f16*)out); break;
-        case AP_BF16: patch_merge_ln<bf16><<<(unsigned)blocks, 256, 0, stream>>>((const bf16*)x, rows, h, w, c, ln_weight, ln_bias, eps, (bf16*)out); break;
-        default: patch_merge_ln<float><<<(unsigned)blocks, 256, 0, stream>>>((const float*)x, rows, h, w, c, ln_weight, ln_bias, eps, (float*)out); break;
-    }
-    AP_HIP_CHECK(hipGetLastError());
-    return AP_OK;
+    return dispatch_dtype("patch_merge_ln", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        patch_merge_ln<T><<<(unsigned)blocks, 256, 0, stream>>>((const T*)x, rows, h, w, c, ln_weight, ln_bias, eps, (T*)out);
+    });
 }
 
 }  // namespace ap

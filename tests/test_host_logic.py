@@ -417,6 +417,69 @@ def test_attention_entry_points_refuse_on_the_host_before_any_launch():
             assert call(dtype, p, o, 0, 4, 1, 64) == 0
 
 
+def test_dtype_dispatch_refuses_unknown_dtypes_on_the_host_before_any_launch():
+    """Every exported entry point whose launcher picks its kernel through dispatch_dtype / dispatch_half (kernel_util.h): dtype 3
+    and -1 with otherwise valid arguments return AP_ERR_INVALID and ap_last_error() names the entry point (the wrapper's name, or the
+    launcher's, which is the same without "ap_"); the f16 / bf16-only ones refuse AP_F32 the same way; n = 0 / rows = 0 is AP_OK for
+    every admitted dtype where the entry point returns in front of its first HIP call.  No GPU: a launch would have come back as
+    AP_ERR_HIP.  The pointers are made up and 32-byte aligned: nothing reads them.
+    Not in the table: ap_preproc_u8hwc_to_chw / _to_patchrows (and the engines' stem preprocess) fetch the normalisation table of
+    the current device (hipGetDevice) before they look at the dtype; ap_gemm / ap_gemm_fused / ap_fold_ln / ap_fold_ls have no
+    empty problem that is AP_OK (M, rows > 0 are required), so they are checked for the refusals only."""
+    from atlaspatch_amd import _lib
+    lib = _lib.load()
+    a, b, c, d, e, f = (0x10000 * (i + 1) for i in range(6))
+    ANY, HALF = (0, 1, 2), (1, 2)
+    # name: (admitted dtypes, arguments after the dtype, index of n / rows among them or None)
+    table = {
+        "ap_attention": (ANY, (a, b, 1, 4, 1, 64, None), 2),
+        "ap_attention_scaled": (ANY, (a, b, 1, 4, 1, 64, 0.125, None), 2),
+        "ap_attention_cls": (ANY, (a, b, 128, 0, 64, c, 1, 4, 1, 64, 0.125, None), 6),
+        "ap_attention_probe": (ANY, (a, b, 128, 0, 64, c, 1, 4, 1, 64, 0.125, None), 6),
+        "ap_attn_pool": (HALF, (a, b, c, 1, 4, 1, None), 3),
+        "ap_rope": (ANY, (a, 1, 4, 1, 1, 64, b, c, 3, None), 1),
+        "ap_swiglu": (ANY, (a, 1, 8, b, None), 1),
+        "ap_layernorm": (ANY, (a, 64, 1, 64, b, c, 1e-6, d, None), 2),
+        "ap_stream_init": (HALF, (a, 1, 64, 1e-6, b, c, None), 1),
+        "ap_stream_to_f32": (HALF, (a, 8, 1, 8, b, None), 2),
+        "ap_cls_stream": (HALF, (a, 1, 0, 1, 4, 64, b, c, None), 3),
+        "ap_cls_exact_update": (HALF, (a, b, 1, 4, 64, c, d, None), 2),
+        "ap_fold_ln": (HALF, (a, 64, 64, 64, b, c, d, e, f, f + 4096, 0, None), None),
+        "ap_fold_ls": (HALF, (a, 64, 64, 64, b, c, d, e, None), None),
+        "ap_gemm": (ANY, (0, a, 64, b, 64, 128, 128, 64, c, None, d, 128, 0, 0, None), None),
+        "ap_gemm_fused": (HALF, (4, a, 64, b, 64, 128, 128, 64, c, d, e, None, f, 128, 0, None), None),
+        "ap_conv2d_nhwc": (ANY, (a, 1, 8, 8, 8, b, c, 64, 3, 1, 1, None, 1, d, None), 1),
+        "ap_conv2d_nhwc_ex": (ANY, (a, 1, 8, 8, 8, b, c, 32, 3, 1, 1, None, 2, d, None), 1),
+        "ap_maxpool3x3s2_nhwc": (ANY, (a, 1, 8, 8, 8, b, None), 1),
+        "ap_avgpool_nhwc": (ANY, (a, 1, 4, 8, b, None), 1),
+        "ap_avgpool2x2_nhwc": (ANY, (a, 1, 8, 8, 8, b, None), 1),
+        "ap_clip_attnpool_tokens": (ANY, (a, b, 1, 4, 8, c, d, None), 2),
+        "ap_dwconv7_ln_nhwc": (ANY, (a, 1, 8, 8, 8, b, c, d, e, 1e-6, f, None), 1),
+        "ap_layernorm_rows": (ANY, (a, 1, 8, b, c, 1e-6, d, None), 1),
+        "ap_swin_window_attention": (ANY, (a, 1, 7, 7, 1, 0, b, c, None), 1),
+        "ap_patch_merge_ln": (ANY, (a, 1, 2, 2, 8, b, c, 1e-6, d, None), 1),
+    }
+    calls = {name: (lambda dt, *rest, fn=getattr(lib, name): fn(dt, *rest)) for name in table}
+    # the two-dtype entry points: both dtypes at once, and each alone beside a valid partner
+    table["ap_add2_layernorm"] = (ANY, (a, 64, b, 64, None, None, 0, None, 1, 1, 64, c, d, 1e-6, e, None), 9)
+    calls["ap_add2_layernorm"] = lambda dt, *rest: lib.ap_add2_layernorm(dt, dt, *rest)
+    table["ap_chw_to_patchrows"] = (ANY, (a, 1, 16, 4, b, 48, None), 1)
+    calls["ap_chw_to_patchrows"] = lambda dt, *rest: lib.ap_chw_to_patchrows(dt, dt, *rest)
+    table["ap_chw_to_patchrows (input)"] = (ANY, (1, a, 1, 16, 4, b, 48, None), 2)
+    calls["ap_chw_to_patchrows (input)"] = lib.ap_chw_to_patchrows
+    table["ap_chw_to_patchrows (output)"] = (ANY, (a, 1, 16, 4, b, 48, None), 1)
+    calls["ap_chw_to_patchrows (output)"] = lambda dt, *rest: lib.ap_chw_to_patchrows(0, dt, *rest)
+    for name, (admitted, rest, n_at) in table.items():
+        who = name.split()[0][3:].encode()                      # "ap_rope" -> b"rope": in the wrapper's text and in the launcher's
+        for dt in (3, -1) + tuple(x for x in ANY if x not in admitted):
+            rc = calls[name](dt, *rest)
+            assert rc == -1 and who in lib.ap_last_error(), (name, dt, rc, lib.ap_last_error())
+        if n_at is not None:
+            empty = rest[:n_at] + (0,) + rest[n_at + 1:]
+            for dt in admitted:
+                assert calls[name](dt, *empty) == 0, (name, dt, lib.ap_last_error())
+
+
 # ----------------------------------------------------------------------------- native host tile sources of the ring
 def test_host_synth_tiles_equal_the_numpy_renderer():
     """ap_host_synth_tiles (the synthetic slide's native 'decoder' behind read_tiles_into) == render_region bit for bit,
