@@ -53,6 +53,13 @@ class VitConfigEx(VitConfig):
     _fields_ = [("no_class_token", C.c_int)]
 
 
+class VitConfigEx2(VitConfigEx):
+    """``ap_vit_config_ex2``: ``ap_vit_config_ex`` followed by the attentional pooler's fields of the CoCa / CONCH v1.5 towers
+    (112 bytes; all four zero = ``VitConfigEx``)."""
+    _fields_ = [("pool_head_dim", C.c_int), ("pool_skip_final_norm", C.c_int), ("pool_proj_dim", C.c_int),
+                ("out_normalize", C.c_int)]
+
+
 class ResnetConfig(C.Structure):
     """``ap_resnet_config`` (additive to ABI v20); ``struct_size`` is filled in here."""
     _fields_ = [("struct_size", C.c_uint32), ("block", C.c_int), ("depths", C.c_int * 4), ("stem_width", C.c_int),
@@ -237,6 +244,7 @@ SIGNATURES = {
     "ap_fold_ls": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                              C.c_void_p]),
     "ap_cls_mean_pool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ap_l2_normalize_rows": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "ap_stream_to_f32": (C.c_int, [C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ap_chw_to_patchrows": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "ap_cls_stream": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -245,6 +245,8 @@ int launch_rope(int dtype, void* qkv, int n, int tokens, int prefix, int heads, 
                 int which, hipStream_t stream);
 // AP_POOL_CLS_MEAN: y f32 [n * tokens, dim] (final LayerNorm of every token) -> out f32 [n, 2 * dim] = [row 0 | mean of rows prefix ..]
 int launch_cls_mean_pool(const float* y, int n, int tokens, int prefix, int dim, float* out, hipStream_t stream);
+// out f32 [rows, dim] (dense) = x[row] / max(||x[row]||, eps), x f32 rows of `stride` elements; out == x needs stride == dim
+int launch_l2_normalize_rows(const float* x, long stride, int rows, int dim, float eps, float* out, hipStream_t stream);
 // Weight folding (ap_vit_finalize).  w32: f32 [rows, ld] (zero padded beyond cols).
 //   fold_ln: wout T [rows, ld] = T(w32[n][k] * gamma[k]); colsum[n] = sum_k float(wout[n][k]);
 //            bias_out[n] = bias_in[n] + sum_k w32[n][k] * beta[k]

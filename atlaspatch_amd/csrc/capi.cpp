@@ -438,6 +438,16 @@ int ap_cls_mean_pool(const float* y, int n, int tokens, int prefix, int dim, flo
     return ap::launch_cls_mean_pool(y, n, tokens, prefix, dim, out, (hipStream_t)stream);
 }
 
+int ap_l2_normalize_rows(const float* x, long stride, int rows, int dim, float eps, float* out, ap_stream_t stream) {
+    AP_REQUIRE(x && out, "ap_l2_normalize_rows: null pointer");
+    AP_REQUIRE(rows >= 0 && dim > 0 && dim % 4 == 0 && stride >= dim && stride % 4 == 0,
+               "ap_l2_normalize_rows: bad shape (%d rows, dim %d, stride %ld: multiples of 4, stride >= dim)", rows, dim, stride);
+    AP_REQUIRE(aligned16(x, out), "ap_l2_normalize_rows: x and out must be 16-byte aligned");
+    AP_REQUIRE(x != out || stride == dim, "ap_l2_normalize_rows: in place (out == x) needs dense rows, stride %ld != dim %d", stride, dim);
+    AP_REQUIRE(eps > 0.f && std::isfinite(eps), "ap_l2_normalize_rows: eps must be positive and finite (a zero row is divided by it)");
+    return ap::launch_l2_normalize_rows(x, stride, rows, dim, eps, out, (hipStream_t)stream);
+}
+
 int ap_stream_to_f32(int dtype, const void* x, long stride, int rows, int dim, float* dst, ap_stream_t stream) {
     AP_REQUIRE(x && dst, "ap_stream_to_f32: null pointer");
     AP_REQUIRE(half_dtype(dtype), "ap_stream_to_f32: dtype %d (f16 / bf16 only)", dtype);

@@ -642,6 +642,30 @@ __global__ __launch_bounds__(256) void cls_mean_pool_kernel(const float* __restr
     o[dim + d] = (float)(acc / (double)(tokens - prefix));
 }
 
+// out[row] = x[row] / max(||x[row]||, eps) (torch F.normalize; CoCa's encode_image): one wave per row, four rows per workgroup,
+// 16-byte loads; a lane sums the squares of its vectors in order in double (the squares are exact there, so the norm is the
+// correctly rounded one and an element carries two float roundings: the norm's and the division's), wave_sum combines them.  The
+// second pass reads x again, each lane only what it writes itself, so out may be x.  A zero row stays zero.
+__global__ __launch_bounds__(256) void l2_normalize_rows_kernel(const float* x, long stride, int rows, int dim, float eps, float* out) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* xr = x + (size_t)row * stride;
+    float* orow = out + (size_t)row * dim;
+    const int nv = dim >> 2;
+    double ss = 0.0;
+    for (int k = lane; k < nv; k += 64) {
+        const f32x4 v = *(const f32x4*)(xr + k * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ss += (double)v[e] * (double)v[e];
+    }
+    const float norm = (float)sqrt(wave_sum(ss));
+    const float d = fmaxf(norm, eps);
+    for (int k = lane; k < nv; k += 64) {
+        const f32x4 v = *(const f32x4*)(xr + k * 4);
+        *(f32x4*)(orow + k * 4) = f32x4{v[0] / d, v[1] / d, v[2] / d, v[3] / d};
+    }
+}
+
 }  // namespace
 
 int launch_add2_layernorm(int delta_dtype, int out_dtype, float* x, long stride, const void* delta0, long dstride0,
@@ -755,6 +779,17 @@ int launch_cls_mean_pool(const float* y, int n, int tokens, int prefix, int dim,
     if (n == 0) return AP_OK;
     dim3 grid((unsigned)((dim + 255) / 256), (unsigned)n);
     cls_mean_pool_kernel<<<grid, 256, 0, stream>>>(y, tokens, prefix, dim, out);
+    AP_HIP_CHECK(hipGetLastError());
+    return AP_OK;
+}
+
+int launch_l2_normalize_rows(const float* x, long stride, int rows, int dim, float eps, float* out, hipStream_t stream) {
+    AP_REQUIRE(dim > 0 && dim % 4 == 0 && stride % 4 == 0 && stride >= dim, "l2_normalize_rows: dim %d / stride %ld (multiples of 4, stride >= dim)",
+               dim, stride);
+    AP_REQUIRE(aligned16(x, out), "l2_normalize_rows: x / out must be 16-byte aligned");
+    AP_REQUIRE(x != out || stride == dim, "l2_normalize_rows: in place needs dense rows (stride %ld, dim %d)", stride, dim);
+    if (rows <= 0) return AP_OK;
+    l2_normalize_rows_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, stream>>>(x, stride, rows, dim, eps, out);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }

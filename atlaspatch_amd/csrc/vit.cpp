@@ -43,7 +43,7 @@ struct FusedBlock {
 };
 struct PoolParams {
     const float *ln_k_w, *ln_k_b, *kv_b, *q, *out_b, *ln_out_w, *ln_out_b;
-    const Param *kv, *out;
+    const Param *kv, *out, *proj;      // proj: attn_pool.proj.weight [P2, P] (pool_proj_dim), else null
 };
 // AP_POOL_MAP: SigLIP's attention-pooling head (map.* parameters)
 struct MapParams {
@@ -60,6 +60,9 @@ struct ap_vit {
     int hd = 64, dattn = 0;                 // head width as stored (64 / 128), heads * hd = width of q, k, v and of proj's input
     int fc1_rows = 0;                       // mlp_dim (GELU) or 2 * mlp_dim (SwiGLU packed)
     float attn_scale = 0.125f;
+    // ap_vit_config_ex2 (AP_POOL_ATTN): head width of the pooler on the one-query probe kernel (0: 64 wide on attn_pool_kernel, the
+    // path conch_v1 takes), ln_k straight on the residual stream, projection width after ln_out, L2-normalised output rows
+    int pool_hd = 0, pool_skip_norm = 0, pool_proj = 0, out_norm = 0;
     float* prefix_dev = nullptr;            // f32 [prefix, dim]: class / register tokens (+ their position rows), built at finalize
     std::map<std::string, ap::Param> params;
     bool finalized = false;
@@ -568,26 +571,36 @@ int run_blocks(ap_vit* m, int n, const Workspace& w, float* out, hipStream_t str
         return ap::launch_gemm_impl(dt, ap::EPI_BIAS_RESID, g, 128, 0, stream);                             // out = r + (acc + bias), f32
     }
 
-    // the other poolings: final LN on ALL tokens (y f32 [M, D], reuses qkv)
-    float* y = (float*)w.qkv;
-    if ((rc = ap::launch_add_layernorm(dt, AP_F32, w.tok, D, pending, D, pending_ls, M, D, m->norm_w, m->norm_b, c.ln_eps, y,
-                                       stream)) != AP_OK) return rc;
-    if (c.pool == AP_POOL_CLS_MEAN)      // [class token | mean of the patch tokens] -> out f32 [n, 2 D]
-        return ap::launch_cls_mean_pool(y, n, m->tokens, m->prefix, D, out, stream);
-
-    // ---- AP_POOL_ATTN (CONCH visual tower): the one-query attentional pooler on the normalised tokens.
-    // Buffers: xk T [M, D] = xn, kv T [M, 2P] reuses hid, pooled T [n, P] = att, o32 f32 [n, P] reuses delta.
     const int P = c.pool_dim;
     const ap::PoolParams& pp = m->pool;
-    if ((rc = ap::launch_layernorm(dt, y, D, M, D, pp.ln_k_w, pp.ln_k_b, c.pool_ln_eps, w.xn,
-                                   stream)) != AP_OK) return rc;
+    if (c.pool == AP_POOL_ATTN && m->pool_skip_norm) {
+        // CoCa (open_clip VisionTransformer + AttentionalPooler): no LayerNorm after the last block, the pooler's ln_k reads the
+        // residual stream -- the launch that folds the last branch in normalises with the ln_k parameters
+        if ((rc = ap::launch_add_layernorm(dt, dt, w.tok, D, pending, D, pending_ls, M, D, pp.ln_k_w, pp.ln_k_b, c.pool_ln_eps, w.xn,
+                                           stream)) != AP_OK) return rc;
+    } else {
+        // the other poolings: final LN on ALL tokens (y f32 [M, D], reuses qkv)
+        float* y = (float*)w.qkv;
+        if ((rc = ap::launch_add_layernorm(dt, AP_F32, w.tok, D, pending, D, pending_ls, M, D, m->norm_w, m->norm_b, c.ln_eps, y,
+                                           stream)) != AP_OK) return rc;
+        if (c.pool == AP_POOL_CLS_MEAN)      // [class token | mean of the patch tokens] -> out f32 [n, 2 D]
+            return ap::launch_cls_mean_pool(y, n, m->tokens, m->prefix, D, out, stream);
+        if ((rc = ap::launch_layernorm(dt, y, D, M, D, pp.ln_k_w, pp.ln_k_b, c.pool_ln_eps, w.xn,
+                                       stream)) != AP_OK) return rc;
+    }
+    // ---- AP_POOL_ATTN (CONCH / CoCa visual towers): the one-query attentional pooler on the normalised tokens.
+    // Buffers: xk T [M, D] = xn, kv T [M, 2P] reuses hid, pooled T [n, P] = att, o32 f32 [n, P] reuses delta; with a projection
+    // ln_out's rows T [n, P] go to xn (the kv GEMM has read it) and the product straight into the caller's buffer in f32.
     {
         ap::GemmArgs g{};
         g.A = w.xn; g.lda = D; set_weight(m, g, pp.kv); g.M = M; g.N = 2 * P; g.K = D;
         g.bias = pp.kv_b; g.out = w.hid; g.ldo = 2 * P;
         if ((rc = ap::launch_gemm(dt, ap::EPI_BIAS_STORE, g, stream)) != AP_OK) return rc;
     }
-    if ((rc = ap::launch_attn_pool(dt, w.hid, pp.q, w.att, n, m->tokens, c.pool_heads, stream)) != AP_OK) return rc;
+    if (m->pool_hd == 0) {
+        if ((rc = ap::launch_attn_pool(dt, w.hid, pp.q, w.att, n, m->tokens, c.pool_heads, stream)) != AP_OK) return rc;
+    } else if ((rc = ap::launch_attention_probe(dt, pp.q, w.hid, 2 * P, 0, P, w.att, n, m->tokens, c.pool_heads, m->pool_hd,
+                                                1.0f / sqrtf((float)m->pool_hd), stream)) != AP_OK) return rc;
     float* o32 = (float*)w.delta;
     AP_HIP_CHECK(hipMemsetAsync(o32, 0, (size_t)n * P * sizeof(float), stream));
     {
@@ -596,7 +609,20 @@ int run_blocks(ap_vit* m, int n, const Workspace& w, float* out, hipStream_t str
         g.bias = pp.out_b; g.out = o32; g.ldo = P;
         if ((rc = ap::launch_gemm(dt, ap::EPI_BIAS_RESID, g, stream)) != AP_OK) return rc;    // 0 + (acc + bias), f32
     }
-    return ap::launch_layernorm(AP_F32, o32, P, n, P, pp.ln_out_w, pp.ln_out_b, c.pool_ln_eps, out, stream);
+    if (m->pool_proj == 0) {
+        if ((rc = ap::launch_layernorm(AP_F32, o32, P, n, P, pp.ln_out_w, pp.ln_out_b, c.pool_ln_eps, out, stream)) != AP_OK) return rc;
+    } else {
+        const int P2 = m->pool_proj;
+        if ((rc = ap::launch_layernorm(dt, o32, P, n, P, pp.ln_out_w, pp.ln_out_b, c.pool_ln_eps, w.xn, stream)) != AP_OK) return rc;
+        AP_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)n * P2 * sizeof(float), stream));
+        ap::GemmArgs g{};
+        g.A = w.xn; g.lda = P; set_weight(m, g, pp.proj); g.M = n; g.N = P2; g.K = P;
+        g.bias = m->zero_bias; g.out = out; g.ldo = P2;
+        if ((rc = ap::launch_gemm_impl(dt, ap::EPI_BIAS_RESID, g, 128, 0, stream)) != AP_OK) return rc;      // 0 + acc, f32
+    }
+    if (!m->out_norm) return AP_OK;
+    const int E = m->pool_proj > 0 ? m->pool_proj : P;
+    return ap::launch_l2_normalize_rows(out, E, n, E, 1e-12f, out, stream);
 }
 
 // AP_VIT_OPT_SPLIT_F16: every matrix of a float32 encoder also as [hi 32 | lo 32] f16 rows (same bytes again: ViT-B 0.34 GB)
@@ -662,16 +688,19 @@ int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
     AP_REQUIRE(cfg && out, "vit_create: null argument");
     static_assert(sizeof(ap_vit_config) == AP_VIT_CONFIG_SIZE_V20, "ap_vit_config is fixed at its ABI v20 fields: append to ap_vit_config_ex");
     static_assert(sizeof(ap_vit_config_ex) == AP_VIT_CONFIG_SIZE_EX, "ap_vit_config_ex grew: append only, and accept its earlier size below");
-    // The hand-over has had two sizes: ap_vit_config (AP_VIT_CONFIG_SIZE_V20) and ap_vit_config_ex (the same bytes + the fields
-    // appended since).  The longer one's tail is taken here, and its base goes through the size rules as the shorter one.
-    ap_vit_config_ex ex;
-    memset(&ex, 0, sizeof(ex));
-    if (cfg->struct_size == AP_VIT_CONFIG_SIZE_EX) {
-        memcpy(&ex, cfg, sizeof(ex));
+    // The hand-over has had three sizes: ap_vit_config (AP_VIT_CONFIG_SIZE_V20), ap_vit_config_ex and ap_vit_config_ex2 (the same
+    // bytes + the fields appended since).  A longer one's tail is taken here, and its base goes through the size rules as the shortest.
+    static_assert(sizeof(ap_vit_config_ex2) == AP_VIT_CONFIG_SIZE_EX2, "ap_vit_config_ex2 grew: append only, and accept its earlier size below");
+    ap_vit_config_ex2 ex2;
+    memset(&ex2, 0, sizeof(ex2));
+    ap_vit_config_ex& ex = ex2.base;
+    if (cfg->struct_size == AP_VIT_CONFIG_SIZE_EX || cfg->struct_size == AP_VIT_CONFIG_SIZE_EX2) {
+        memcpy(&ex2, cfg, cfg->struct_size);
         ex.base.struct_size = AP_VIT_CONFIG_SIZE_V20;
         cfg = &ex.base;
     }
     const int nct = ex.no_class_token;
+    const int phd = ex2.pool_head_dim, skipn = ex2.pool_skip_final_norm, pproj = ex2.pool_proj_dim, onorm = ex2.out_normalize;
     // A binding written for ABI <= 19 (no size member, image_size first) presents 224 / 448 / 518 here: only sizes up to 64 bytes
     // past this library's count as a newer caller, so that one is refused as invalid, unread.
     ap_vit_config c;
@@ -707,11 +736,29 @@ int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
                    "no_class_token (ap_vit_config_ex)", c.pool);
         AP_REQUIRE(c.proj_dim == 0, "vit_create: AP_POOL_MAP has no projection (proj_dim %d)", c.proj_dim);
     }
+    if (c.pool != AP_POOL_ATTN) {        // the fields of ap_vit_config_ex2 belong to the attentional pooler
+        AP_REQUIRE(phd == 0, "vit_create: pool_head_dim %d goes with AP_POOL_ATTN, not pool %d", phd, c.pool);
+        AP_REQUIRE(skipn == 0, "vit_create: pool_skip_final_norm %d goes with AP_POOL_ATTN, not pool %d", skipn, c.pool);
+        AP_REQUIRE(pproj == 0, "vit_create: pool_proj_dim %d goes with AP_POOL_ATTN, not pool %d", pproj, c.pool);
+        AP_REQUIRE(onorm == 0, "vit_create: out_normalize %d goes with AP_POOL_ATTN, not pool %d", onorm, c.pool);
+    }
     if (c.pool == AP_POOL_ATTN) {
-        AP_REQUIRE(c.compute_dtype != AP_F32, "vit_create: the attentional pooler runs in float16 / bfloat16 only");
-        AP_REQUIRE(c.pool_heads > 0 && c.pool_dim == c.pool_heads * 64 && c.pool_dim % 128 == 0 &&
-                   2 * c.pool_dim <= c.mlp_dim && 2 * c.pool_dim <= 3 * c.dim,
-                   "vit_create: pool_dim %d / pool_heads %d (heads of 64, multiple of 128)", c.pool_dim, c.pool_heads);
+        AP_REQUIRE(phd == 0 || phd == 64 || phd == 96 || phd == 128, "vit_create: pool_head_dim %d (0 = 64 wide; 64, 96 or 128)", phd);
+        // pool_head_dim 0 is the pooler as it was before the field existed, its refusals included
+        AP_REQUIRE(c.compute_dtype != AP_F32 || phd != 0, "vit_create: the attentional pooler runs in float16 / bfloat16 only");
+        if (phd == 0)
+            AP_REQUIRE(c.pool_heads > 0 && c.pool_dim == c.pool_heads * 64 && c.pool_dim % 128 == 0 &&
+                       2 * c.pool_dim <= c.mlp_dim && 2 * c.pool_dim <= 3 * c.dim,
+                       "vit_create: pool_dim %d / pool_heads %d (heads of 64, multiple of 128)", c.pool_dim, c.pool_heads);
+        else
+            AP_REQUIRE(c.pool_heads > 0 && c.pool_dim == c.pool_heads * phd && c.pool_dim % 128 == 0 &&
+                       2 * c.pool_dim <= c.mlp_dim && 2 * c.pool_dim <= 3 * c.dim,
+                       "vit_create: pool_dim %d is not pool_heads %d x pool_head_dim %d, a multiple of 128 with 2 x pool_dim within mlp_dim "
+                       "and 3 x dim", c.pool_dim, c.pool_heads, phd);
+        AP_REQUIRE(skipn == 0 || skipn == 1, "vit_create: pool_skip_final_norm %d", skipn);
+        AP_REQUIRE(onorm == 0 || onorm == 1, "vit_create: out_normalize %d", onorm);
+        AP_REQUIRE(pproj == 0 || (pproj > 0 && pproj % 128 == 0 && pproj <= c.pool_dim),
+                   "vit_create: pool_proj_dim %d (0, or a multiple of 128 of at most pool_dim %d)", pproj, c.pool_dim);
     }
     AP_REQUIRE(c.rope == 0 || (c.head_dim == 0 || c.head_dim * c.heads == c.dim), "vit_create: rope needs the true head width");
     AP_REQUIRE(c.act == AP_ACT_GELU || ((c.act == AP_ACT_QUICK_GELU || c.act == AP_ACT_GELU_TANH) && c.mlp_type == AP_MLP_GELU),
@@ -732,6 +779,7 @@ int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
     m->pos_rows = c.no_embed_class ? g * g : m->tokens;            // (no_class_token: tokens = g * g either way)
     m->pos_row0 = c.no_embed_class ? 0 : prefix;
     m->hd = hd; m->dattn = c.heads * hd;
+    m->pool_hd = phd; m->pool_skip_norm = skipn; m->pool_proj = pproj; m->out_norm = onorm;
     m->attn_scale = c.attn_scale > 0.f ? c.attn_scale : 1.0f / sqrtf((float)hd);
     m->fc1_rows = c.mlp_type == AP_MLP_SWIGLU ? 2 * c.mlp_dim : c.mlp_dim;
     m->kpe = (int)ap::align_up(3 * c.patch_size * c.patch_size, 64);
@@ -749,14 +797,14 @@ int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
     if (!nct) add("cls_token", 1, D, false);
     if (c.reg_tokens > 0) add("reg_tokens", c.reg_tokens, D, false);
     add("pos_embed", m->pos_rows, D, false);
-    add("norm.weight", 1, D, false);
-    add("norm.bias", 1, D, false);
+    if (!skipn) { add("norm.weight", 1, D, false); add("norm.bias", 1, D, false); }
     if (c.pre_norm) { add("pre_norm.weight", 1, D, false); add("pre_norm.bias", 1, D, false); }
     if (c.rope) { add("rope.cos", m->patches, hd, false); add("rope.sin", m->patches, hd, false); }
-    if (c.proj_dim > 0) {
-        add("head_proj.weight", c.proj_dim, D, true);
-        if (rc == AP_OK && (hipMalloc((void**)&m->zero_bias, (size_t)c.proj_dim * sizeof(float)) != hipSuccess ||
-                            hipMemset(m->zero_bias, 0, (size_t)c.proj_dim * sizeof(float)) != hipSuccess)) {
+    if (c.proj_dim > 0 || pproj > 0) {       // (proj_dim goes with AP_POOL_CLS, pool_proj_dim with AP_POOL_ATTN: never both)
+        const int pd = c.proj_dim > 0 ? c.proj_dim : pproj;
+        if (c.proj_dim > 0) add("head_proj.weight", c.proj_dim, D, true);
+        if (rc == AP_OK && (hipMalloc((void**)&m->zero_bias, (size_t)pd * sizeof(float)) != hipSuccess ||
+                            hipMemset(m->zero_bias, 0, (size_t)pd * sizeof(float)) != hipSuccess)) {
             ap::set_error("vit_create: hipMalloc of the projection's zero bias failed");
             rc = AP_ERR_HIP;
         }
@@ -778,6 +826,7 @@ int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
         add("attn_pool.q", 1, P, false);
         add("attn_pool.out.weight", P, P, true); add("attn_pool.out.bias", 1, P, false);
         add("attn_pool.ln_out.weight", 1, P, false); add("attn_pool.ln_out.bias", 1, P, false);
+        if (pproj > 0) add("attn_pool.proj.weight", pproj, P, true);
     }
     if (c.pool == AP_POOL_MAP) {
         const int DA = m->dattn, H = c.mlp_dim;
@@ -930,6 +979,7 @@ int ap_vit_finalize(ap_vit* m) {
         pp.kv = find(m, "attn_pool.kv.weight"); pp.kv_b = vec("attn_pool.kv.bias"); pp.q = vec("attn_pool.q");
         pp.out = find(m, "attn_pool.out.weight"); pp.out_b = vec("attn_pool.out.bias");
         pp.ln_out_w = vec("attn_pool.ln_out.weight"); pp.ln_out_b = vec("attn_pool.ln_out.bias");
+        pp.proj = m->pool_proj > 0 ? find(m, "attn_pool.proj.weight") : nullptr;
     }
     if (m->cfg.pool == AP_POOL_MAP) {
         ap::MapParams& mp = m->map;
@@ -1016,6 +1066,7 @@ size_t ap_vit_workspace_bytes(const ap_vit* m, int n) {
 int ap_vit_embed_dim(const ap_vit* m) {
     if (!m) return 0;
     if (m->cfg.proj_dim > 0) return m->cfg.proj_dim;
+    if (m->pool_proj > 0) return m->pool_proj;
     return m->cfg.pool == AP_POOL_ATTN ? m->cfg.pool_dim : (m->cfg.pool == AP_POOL_CLS_MEAN ? 2 * m->cfg.dim : m->cfg.dim);
 }
 

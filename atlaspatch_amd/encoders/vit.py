@@ -73,6 +73,9 @@ TRANSFORM_RESIZE = {
     # medsiglip.py:38 AutoProcessor(use_fast=True) of google/medsiglip-448 = SiglipImageProcessor: resize to 448 x 448 (both sides,
     # no crop), `resample: 2` = bilinear, rescale 1 / 255, mean = std = 0.5 (public model card, unverifiable offline)
     "medsiglip": (448, "bilinear"),
+    # open_clip image transforms (omiclip.py:59-61: create_model_and_transforms of coca_ViT-L-14; conch.py:97-100: CONCH v1.5's own
+    # 448-px transform; the packages are absent offline, unverified): Resize(S, bicubic) + CenterCrop(S)
+    "omiclip": (224, "bicubic"), "conch_v15": (448, "bicubic"),
 }
 
 # Normalize() constants per registered name (default: ImageNet)
@@ -91,6 +94,8 @@ TRANSFORM_NORM = {
     "h0_mini": ((0.707223, 0.578729, 0.703617), (0.211883, 0.230117, 0.177517)),          # the hub config's (H-optimus statistics)
     "lunit_vit_small_patch16_dino": ((0.70322989, 0.53606487, 0.66096631), (0.21716536, 0.26081574, 0.20723464)),
     "lunit_vit_small_patch8_dino": ((0.70322989, 0.53606487, 0.66096631), (0.21716536, 0.26081574, 0.20723464)),
+    "omiclip": (OPENAI_CLIP_MEAN, OPENAI_CLIP_STD),            # open_clip's default constants (unverified offline)
+    "conch_v15": (IMAGENET_MEAN, IMAGENET_STD),                # CONCH v1.5's transform (unverified offline)
 }
 
 ARCHS = {
@@ -220,6 +225,21 @@ ARCHS = {
     # LayerNorm, then LayerNorm + MLP with a residual).  Heads 72 wide, stored zero-padded to 96; MLP 4304, stored as 4352.
     "medsiglip": dict(image_size=448, patch_size=14, dim=1152, depth=27, heads=16, mlp_dim=4304, ln_eps=1e-6, layer_scale=False,
                       act="gelu_tanh", pool="map", no_class_token=True),
+    # The two ViT-L towers behind a 96-wide attentional pooler (open_clip AttentionalPooler(d_model 768, context 1024, 8 heads)).
+    # The reference only calls open_clip and the TITAN repository's conch_v1_5.py: both architectures are restated here from the
+    # public packages [3P], UNVERIFIED OFFLINE, and parity is claimed against the restatement in tests/coca_reference.py only.
+    # omiclip (models/patch/omiclip.py:14,46,59-61): open_clip "coca_ViT-L-14" visual tower, CoCa.encode_image(x).  ViT-L/14 at 224
+    # px (257 tokens), no patch-embedding bias, ln_pre, erf GELU, LayerNorm 1e-5, NO LayerNorm after the last block; the pooler has
+    # 256 queries of which row 0 is the pooled vector (rows 1 .. 255 are the caption tokens), then ln_post, `proj` [768, 768]
+    # without bias and L2 normalisation (normalize=True, encode_image's default).
+    "omiclip": dict(image_size=224, patch_size=14, dim=1024, depth=24, heads=16, mlp_dim=4096, ln_eps=1e-5, layer_scale=False,
+                    pre_norm=True, pool="attn", pool_dim=768, pool_heads=8, pool_ln_eps=1e-5, pool_head_dim=96,
+                    pool_skip_final_norm=True, pool_proj_dim=768, out_normalize=True),
+    # conch_v15 (models/patch/conch.py:82-85,97-100): build_conch(ConchConfig()) of the TITAN repository, model(x).  timm ViT-L/16
+    # trunk at 448 px (785 tokens) with LayerScale, LayerNorm 1e-6, the trunk's final norm on all tokens, a ONE-query pooler
+    # (attn_pool_contrast) and ln_contrast; no projection, not normalised: 768 floats.
+    "conch_v15": dict(image_size=448, patch_size=16, dim=1024, depth=24, heads=16, mlp_dim=4096, ln_eps=1e-6, layer_scale=True,
+                      pool="attn", pool_dim=768, pool_heads=8, pool_ln_eps=1e-5, pool_head_dim=96),
 }
 
 
@@ -625,15 +645,18 @@ def pad_mlp(state: dict, *, mlp_dim: int, depth: int, swiglu: bool) -> dict:
 def attn_pool_canonical(pool: dict, *, pool_eps: float = 1e-5) -> dict:
     """open_clip ``AttentionalPooler`` (+ the LayerNorm after it) -> ``attn_pool.*`` parameters.
 
-    ``pool`` holds the module's own tensors: ``query`` [1, P], ``ln_q.weight|bias``, ``ln_k.weight|bias``,
+    ``pool`` holds the module's own tensors: ``query`` [Q, P], ``ln_q.weight|bias``, ``ln_k.weight|bias``,
     ``attn.q_proj_weight`` [P, P], ``attn.k_proj_weight`` / ``attn.v_proj_weight`` [P, C], ``attn.in_proj_bias``
-    [3P], ``attn.out_proj.weight|bias`` and ``ln_out.weight|bias`` (CONCH: ``visual.ln_contrast``).
-    The projected query is input independent and is folded here (float64 on the host)."""
+    [3P], ``attn.out_proj.weight|bias`` and ``ln_out.weight|bias`` (CONCH: ``visual.ln_contrast``; CoCa: ``visual.ln_post``),
+    and optionally ``proj`` [P, P2] (CoCa's projection, stored transposed as ``attn_pool.proj.weight``).
+    The projected query is input independent and is folded here (float64 on the host).  Of Q queries only row 0 is the pooled
+    vector (CoCa: rows 1 .. 255 are the caption tokens, which ``encode_image`` drops); the head width plays no part here."""
     f = lambda k: pool[k].detach().to(torch.float64, copy=True).cpu()
     P = pool["attn.q_proj_weight"].shape[0]
-    q = torch.nn.functional.layer_norm(f("query").reshape(1, P), (P,), f("ln_q.weight"), f("ln_q.bias"), pool_eps)
+    q = torch.nn.functional.layer_norm(f("query").reshape(-1, P)[:1], (P,), f("ln_q.weight"), f("ln_q.bias"), pool_eps)
     q = q @ f("attn.q_proj_weight").T + f("attn.in_proj_bias")[:P]
-    out = {"attn_pool.q": q.reshape(-1),
+    extra = {"attn_pool.proj.weight": f("proj").T} if "proj" in pool else {}
+    out = {"attn_pool.q": q.reshape(-1), **extra,
            "attn_pool.ln_k.weight": f("ln_k.weight"), "attn_pool.ln_k.bias": f("ln_k.bias"),
            "attn_pool.kv.weight": torch.cat([f("attn.k_proj_weight"), f("attn.v_proj_weight")], 0),
            "attn_pool.kv.bias": f("attn.in_proj_bias")[P:],
@@ -644,13 +667,140 @@ def attn_pool_canonical(pool: dict, *, pool_eps: float = 1e-5) -> dict:
 
 def conch_state_dicts(sd: dict) -> tuple[dict, dict]:
     """Split a CONCH v1 checkpoint (open_clip_custom CoCa; key names from the public package [3P], unverified
-    offline) into the timm trunk state dict and the pooler tensors ``attn_pool_canonical`` expects."""
-    trunk = {k[len("visual.trunk."):]: v for k, v in sd.items() if k.startswith("visual.trunk.")}
-    pre = "visual.attn_pool_contrast."
+    offline) into the timm trunk state dict and the pooler tensors ``attn_pool_canonical`` expects.  The tower's keys
+    (``trunk.*``, ``attn_pool_contrast.*``, ``ln_contrast.*``) may stand under ``visual.`` (CONCH v1), under ``vision_encoder.``
+    or bare (CONCH v1.5)."""
+    root = next((r for r in ("visual.", "vision_encoder.", "") if any(k.startswith(r + "trunk.") for k in sd)), "visual.")
+    trunk = {k[len(root + "trunk."):]: v for k, v in sd.items() if k.startswith(root + "trunk.")}
+    pre = root + "attn_pool_contrast."
     pool = {k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}
-    pool["ln_out.weight"] = sd["visual.ln_contrast.weight"]
-    pool["ln_out.bias"] = sd["visual.ln_contrast.bias"]
+    pool["ln_out.weight"] = sd[root + "ln_contrast.weight"]
+    pool["ln_out.bias"] = sd[root + "ln_contrast.bias"]
     return trunk, pool
+
+
+POOLER_KEYS = ("query", "ln_q.weight", "ln_q.bias", "ln_k.weight", "ln_k.bias", "attn.q_proj_weight", "attn.k_proj_weight",
+               "attn.v_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight", "attn.out_proj.bias")
+
+
+def attn_tower_canonical_shapes(arch: dict) -> dict:
+    """Canonical key -> shape of a class-token ViT with the attentional pooler (``arch``: an ``ARCHS`` entry with ``pool="attn"``)."""
+    d, mlp, ps, P = arch["dim"], arch["mlp_dim"], arch["patch_size"], arch["pool_dim"]
+    tokens = 1 + (arch["image_size"] // ps) ** 2
+    want = {"patch_embed.weight": (d, 3, ps, ps), "patch_embed.bias": (d,), "cls_token": (d,), "pos_embed": (tokens, d),
+            "attn_pool.q": (P,), "attn_pool.ln_k.weight": (d,), "attn_pool.ln_k.bias": (d,), "attn_pool.kv.weight": (2 * P, d),
+            "attn_pool.kv.bias": (2 * P,), "attn_pool.out.weight": (P, P), "attn_pool.out.bias": (P,),
+            "attn_pool.ln_out.weight": (P,), "attn_pool.ln_out.bias": (P,)}
+    if not arch.get("pool_skip_final_norm"):
+        want.update({"norm.weight": (d,), "norm.bias": (d,)})
+    if arch.get("pre_norm"):
+        want.update({"pre_norm.weight": (d,), "pre_norm.bias": (d,)})
+    if arch.get("pool_proj_dim"):
+        want["attn_pool.proj.weight"] = (arch["pool_proj_dim"], P)
+    for i in range(arch["depth"]):
+        b = f"blocks.{i}."
+        want.update({b + "ln1.weight": (d,), b + "ln1.bias": (d,), b + "qkv.weight": (3 * d, d), b + "qkv.bias": (3 * d,),
+                     b + "proj.weight": (d, d), b + "proj.bias": (d,), b + "ln2.weight": (d,), b + "ln2.bias": (d,),
+                     b + "fc1.weight": (mlp, d), b + "fc1.bias": (mlp,), b + "fc2.weight": (d, mlp), b + "fc2.bias": (d,)})
+        if arch.get("layer_scale"):
+            want.update({b + "ls1": (d,), b + "ls2": (d,)})
+    return want
+
+
+def _mapped_canonical(src: dict, table: dict, pool_prefix: str, ln_out: str, arch: dict, *, family: str, source: str) -> dict:
+    """The body both pooler-tower adapters share: ``table`` (canonical name -> checkpoint key, or a callable on the checkpoint)
+    plus the pooler under ``pool_prefix`` with ``ln_out`` as its closing LayerNorm, checked against ``attn_tower_canonical_shapes``.
+    A checkpoint key nothing reads, a key the architecture needs and a wrong shape are each a ``ValueError`` naming it."""
+    used: set = set()
+    out: dict[str, torch.Tensor] = {}
+
+    def take(key):
+        used.add(key)
+        return src.get(key)
+
+    for name, key in table.items():
+        t = take(key)
+        if t is not None:
+            out[name] = t.detach().to(dtype=torch.float32, device="cpu").contiguous()
+    pool = {k: take(pool_prefix + k) for k in POOLER_KEYS}
+    pool["ln_out.weight"], pool["ln_out.bias"] = take(ln_out + ".weight"), take(ln_out + ".bias")
+    if arch.get("pool_proj_dim"):
+        pool["proj"] = take("proj")
+    P, d = arch["pool_dim"], arch["dim"]
+    shapes = {"query": None, "ln_q.weight": (P,), "ln_q.bias": (P,), "ln_k.weight": (d,), "ln_k.bias": (d,),
+              "attn.q_proj_weight": (P, P), "attn.k_proj_weight": (P, d), "attn.v_proj_weight": (P, d), "attn.in_proj_bias": (3 * P,),
+              "attn.out_proj.weight": (P, P), "attn.out_proj.bias": (P,), "ln_out.weight": (P,), "ln_out.bias": (P,),
+              "proj": (P, arch.get("pool_proj_dim") or 0)}
+    for k, t in pool.items():                                          # what the float64 fold below multiplies must fit first
+        want = shapes[k]
+        if t is not None and (tuple(t.shape) != want if want else (t.dim() != 2 or t.shape[1] != P)):
+            key = {"ln_out.weight": ln_out + ".weight", "ln_out.bias": ln_out + ".bias", "proj": "proj"}.get(k, pool_prefix + k)
+            raise ValueError(f"{family} checkpoint: {key} has shape {tuple(t.shape)}, expected {want or ('Q', P)}")
+    if all(t is not None for k, t in pool.items() if k != "proj"):
+        out.update(attn_pool_canonical({k: t for k, t in pool.items() if t is not None}, pool_eps=arch.get("pool_ln_eps", 1e-5)))
+    unknown = sorted(k for k in src if k not in used)
+    absent = sorted(k for k in used if k not in src)
+    try:
+        return check_canonical(out, attn_tower_canonical_shapes(arch), unknown, family=family, source=source)
+    except ValueError as exc:
+        if unknown or not absent:
+            raise
+        raise ValueError(f"{exc}; the checkpoint lacks {absent[:5]}") from None
+
+
+def coca_canonical_state_dict(sd: dict, arch: dict) -> dict:
+    """The ``open_clip_coca`` adapter: open_clip's CoCa visual tower (``coca_ViT-L-14``; key names from the public package [3P],
+    unverified offline) -> canonical names.  Takes ``visual.*`` bare or prefixed, or the whole CoCa model, whose ``text.*``,
+    ``text_decoder.*`` and ``logit_scale`` are dropped.  ``conv1`` has no bias (zeros are uploaded, as for the CLIP towers); there
+    is no LayerNorm after the last block; query row 0 is folded through ``ln_q`` and ``q_proj`` in float64 (``attn_pool_canonical``);
+    ``ln_post`` closes the pooler and ``proj`` is stored transposed as ``attn_pool.proj.weight``."""
+    src = {k: v for k, v in sd.items() if not (k.startswith("text.") or k.startswith("text_decoder.") or k == "logit_scale")}
+    if any(k.startswith("visual.") for k in src):
+        src = {(k[len("visual."):] if k.startswith("visual.") else k): v for k, v in src.items()}
+    d = arch["dim"]
+    table = {"patch_embed.weight": "conv1.weight", "cls_token": "class_embedding", "pos_embed": "positional_embedding",
+             "pre_norm.weight": "ln_pre.weight", "pre_norm.bias": "ln_pre.bias"}
+    for i in range(arch["depth"]):
+        p, b = f"transformer.resblocks.{i}.", f"blocks.{i}."
+        table.update({b + "ln1.weight": p + "ln_1.weight", b + "ln1.bias": p + "ln_1.bias",
+                      b + "qkv.weight": p + "attn.in_proj_weight", b + "qkv.bias": p + "attn.in_proj_bias",
+                      b + "proj.weight": p + "attn.out_proj.weight", b + "proj.bias": p + "attn.out_proj.bias",
+                      b + "ln2.weight": p + "ln_2.weight", b + "ln2.bias": p + "ln_2.bias",
+                      b + "fc1.weight": p + "mlp.c_fc.weight", b + "fc1.bias": p + "mlp.c_fc.bias",
+                      b + "fc2.weight": p + "mlp.c_proj.weight", b + "fc2.bias": p + "mlp.c_proj.bias"})
+    src = dict(src)
+    src["<zero patch-embedding bias>"] = torch.zeros(d)
+    table["patch_embed.bias"] = "<zero patch-embedding bias>"
+    return _mapped_canonical(src, table, "attn_pool.", "ln_post", arch, family="CoCa", source="open_clip_coca")
+
+
+def conch_v15_canonical_state_dict(sd: dict, arch: dict) -> tuple[dict, bool]:
+    """CONCH v1.5 (``conch_v1_5.py`` of the TITAN repository; key names from the public package [3P], unverified offline) ->
+    (canonical names, layer_scale).  ``trunk.*`` (timm ViT-L/16), ``attn_pool_contrast.*`` and ``ln_contrast.*``, bare or under
+    ``visual.`` / ``vision_encoder.``.  LayerScale is taken from the checkpoint when ``trunk.blocks.<i>.ls1.gamma`` is there; a
+    checkpoint without it gives a model without it (the second value)."""
+    root = next((r for r in ("visual.", "vision_encoder.", "") if any(k.startswith(r + "trunk.") for k in sd)), "")
+    src = {(k[len(root):] if k.startswith(root) else k): v for k, v in sd.items()}
+    layer_scale = "trunk.blocks.0.ls1.gamma" in src
+    if "trunk.cls_token" in src:                                       # timm keeps a leading batch axis on both
+        src["trunk.cls_token"] = src["trunk.cls_token"].reshape(-1)
+    if "trunk.pos_embed" in src and src["trunk.pos_embed"].dim() == 3:
+        src["trunk.pos_embed"] = src["trunk.pos_embed"][0]
+    table = {"patch_embed.weight": "trunk.patch_embed.proj.weight", "patch_embed.bias": "trunk.patch_embed.proj.bias",
+             "cls_token": "trunk.cls_token", "pos_embed": "trunk.pos_embed", "norm.weight": "trunk.norm.weight",
+             "norm.bias": "trunk.norm.bias"}
+    for i in range(arch["depth"]):
+        p, b = f"trunk.blocks.{i}.", f"blocks.{i}."
+        table.update({b + "ln1.weight": p + "norm1.weight", b + "ln1.bias": p + "norm1.bias",
+                      b + "qkv.weight": p + "attn.qkv.weight", b + "qkv.bias": p + "attn.qkv.bias",
+                      b + "proj.weight": p + "attn.proj.weight", b + "proj.bias": p + "attn.proj.bias",
+                      b + "ln2.weight": p + "norm2.weight", b + "ln2.bias": p + "norm2.bias",
+                      b + "fc1.weight": p + "mlp.fc1.weight", b + "fc1.bias": p + "mlp.fc1.bias",
+                      b + "fc2.weight": p + "mlp.fc2.weight", b + "fc2.bias": p + "mlp.fc2.bias"})
+        if layer_scale:
+            table.update({b + "ls1": p + "ls1.gamma", b + "ls2": p + "ls2.gamma"})
+    spec = dict(arch, layer_scale=layer_scale)
+    return _mapped_canonical(src, table, "attn_pool_contrast.", "ln_contrast", spec, family="CONCH v1.5", source="conch_v15"), layer_scale
 
 
 def random_attn_pool(arch: dict, seed: int = 0) -> dict:
@@ -709,6 +859,10 @@ def random_canonical_state_dict(arch: dict, seed: int = 0) -> dict:
         sd["pre_norm.weight"] = 1.0 + w(d, s=0.1); sd["pre_norm.bias"] = w(d)
     if arch.get("proj_dim"):
         sd["head_proj.weight"] = w(arch["proj_dim"], d, s=d ** -0.5)
+    if arch.get("pool_proj_dim"):                                     # CoCa's `proj`, as the adapter stores it: [P2, P]
+        sd["attn_pool.proj.weight"] = w(arch["pool_proj_dim"], arch["pool_dim"], s=arch["pool_dim"] ** -0.5)
+    if arch.get("pool_skip_final_norm"):                              # no LayerNorm after the last block: no norm.* parameters
+        del sd["norm.weight"], sd["norm.bias"]
     return sd
 
 
@@ -730,8 +884,13 @@ class HipViT(NativeEncoder):
             self.embed_dim = int(arch["proj_dim"])
         hd_true = arch["dim"] // arch["heads"]
         hd_stored = stored_head_dim(arch["dim"], arch["heads"])
-        # the fields appended since ABI v20 travel in the longer structure; every other model hands over the v20 one, as before
-        config = _lib.VitConfigEx if arch.get("no_class_token") else _lib.VitConfig
+        if arch.get("pool_proj_dim"):                      # CoCa's projection after the pooler
+            self.embed_dim = int(arch["pool_proj_dim"])
+        # the fields appended since ABI v20 travel in the longer structures; every other model hands over the v20 one, as before
+        ex2 = [int(arch.get("pool_head_dim", 0)), 1 if arch.get("pool_skip_final_norm") else 0, int(arch.get("pool_proj_dim", 0)),
+               1 if arch.get("out_normalize") else 0]
+        tail = [1 if arch.get("no_class_token") else 0] + ex2 if any(ex2) else ([1] if arch.get("no_class_token") else [])
+        config = _lib.VitConfigEx2 if any(ex2) else (_lib.VitConfigEx if arch.get("no_class_token") else _lib.VitConfig)
         cfg = config(arch["image_size"], arch["patch_size"], arch["dim"], arch["depth"],
                              arch["heads"], stored_mlp_dim(arch["mlp_dim"]), float(arch["ln_eps"]),
                              1 if arch.get("layer_scale") else 0, _lib.torch_dtype_code(dtype),
@@ -742,7 +901,7 @@ class HipViT(NativeEncoder):
                              0.0 if hd_stored == hd_true else float(1.0 / np.sqrt(np.float32(hd_true))),
                              1 if arch.get("pre_norm") else 0, {"quick_gelu": 1, "gelu_tanh": 2}.get(arch.get("act"), 0),
                              int(arch.get("proj_dim", 0)), 1 if arch.get("rope") else 0,
-                     *([1] if arch.get("no_class_token") else []))
+                     *tail)
         state = pad_heads(state, dim=arch["dim"], heads=arch["heads"], depth=arch["depth"])
         state = pad_mlp(state, mlp_dim=arch["mlp_dim"], depth=arch["depth"], swiglu=arch.get("mlp") == "swiglu")
         self._open(cfg, state)
@@ -897,6 +1056,38 @@ def register_medsiglip(registry, *, device, dtype=torch.float32, num_workers: in
         ex.max_batch = medsiglip_max_batch(ex.vit)
         return ex
     registry.register("medsiglip", build)
+
+
+def register_coca_towers(registry, *, device, dtype=torch.float32, num_workers: int = 0, **arch_overrides) -> None:
+    """omiclip (models/patch/omiclip.py: open_clip ``coca_ViT-L-14``, ``encode_image``) and conch_v15 (models/patch/conch.py:67-112:
+    ``build_conch(ConchConfig())`` of the TITAN repository): ViT-L trunks whose features come from an attentional pooler with eight
+    96-wide heads over the 1024-wide tokens.  Both architectures are restated from the public packages, unverified offline (see
+    ``ARCHS``).  Transform: Pillow-exact bicubic resize of the shorter side to 224 / 448 and the centre crop on the device, OpenAI
+    CLIP / ImageNet constants.  Weights: ``$ATLASPATCH_WEIGHTS_DIR/<name>.{safetensors,pt,pth}`` (omiclip: ``visual.*`` bare or
+    prefixed, or the whole CoCa model; conch_v15: ``trunk.*`` / ``attn_pool_contrast.*`` / ``ln_contrast.*``, bare or under
+    ``visual.`` / ``vision_encoder.``) or ``ATLASPATCH_RANDOM_INIT=<seed>``.  omiclip runs in float32 too (257 tokens); conch_v15
+    (785 tokens) in float16 / bfloat16 only.  Not in the default registry: ``plugins/coca_towers.py`` ships them."""
+    def build(name):
+        spec = dict(ARCHS[name]); spec.update(arch_overrides)
+        tokens = 1 + (spec["image_size"] // spec["patch_size"]) ** 2
+        if dtype == torch.float32 and (tokens > 288 or stored_head_dim(spec["dim"], spec["heads"]) != 64):
+            raise ValueError(f"{name}: --feature-precision float32 is not available: {tokens} tokens with heads stored "
+                             f"{stored_head_dim(spec['dim'], spec['heads'])} wide exceed the float32 attention kernel's limits (288 "
+                             "tokens, 64 wide); use float16 or bfloat16")
+        state, path = None, weights_path(name)
+        if path is not None:
+            if name == "omiclip":
+                state = coca_canonical_state_dict(load_checkpoint(path), spec)
+            else:
+                state, spec["layer_scale"] = conch_v15_canonical_state_dict(load_checkpoint(path), spec)
+        mean, std = TRANSFORM_NORM[name]
+        ex = build_hip_vit_extractor(name=name, arch=spec, device=device, dtype=dtype, state_dict=state, source="canonical" if state else "auto",
+                                     random_init_seed=_env_seed(), mean=mean, std=std, resize=TRANSFORM_RESIZE[name], expect_size=None,
+                                     max_batch=256)
+        ex.max_batch = medsiglip_max_batch(ex.vit, cap=256)          # ap_vit_workspace_bytes against the byte budget
+        return ex
+    for name in ("omiclip", "conch_v15"):
+        registry.register(name, lambda n=name: build(n))
 
 
 def register_conch(registry, *, device, dtype=torch.float32, num_workers: int = 0) -> None:

@@ -201,7 +201,7 @@ typedef struct ap_vit_config {
                             AP_POOL_CLS_MEAN: final LN on all tokens, out = [class token | mean of the PATCH tokens]
                             (2 * dim floats; register tokens excluded): torch.cat([cls, patch_tokens.mean(1)], -1) of
                             models/patch/midnight.py:58-61, virchow.py:58-61,111-114, hoptimus.py:158-161 */
-    int pool_dim;        /* 512 (conch_v1); heads of 64 */
+    int pool_dim;        /* 512 (conch_v1); heads of 64 (other widths: pool_head_dim of ap_vit_config_ex2) */
     int pool_heads;      /* 8 */
     float pool_ln_eps;   /* 1e-5 (open_clip LayerNorm) */
     /* ---- ABI v17: the rest of the reference's ViT zoo (models/patch/vit.py:9-15 vit_b_32 / vit_l_32 / vit_h_14,
@@ -246,6 +246,24 @@ typedef struct ap_vit_config_ex {
                             combined with pre_norm or rope in this build */
 } ap_vit_config_ex;
 #define AP_VIT_CONFIG_SIZE_EX 96u    /* sizeof(ap_vit_config_ex) */
+/* The second extension (additive as the first: AP_ABI_VERSION stays 20): ap_vit_config_ex followed by the attentional pooler's
+ * fields for the ViT-L towers of CoCa (open_clip coca_ViT-L-14, models/patch/omiclip.py) and CONCH v1.5 (models/patch/conch.py:82-100).
+ * Handed over like ap_vit_config_ex, with base.base.struct_size = sizeof(ap_vit_config_ex2); ap_vit_create takes exactly the
+ * three sizes 92, 96 and 112.  All four fields zero = ap_vit_config_ex, bit for bit.  They go with AP_POOL_ATTN only. */
+typedef struct ap_vit_config_ex2 {
+    ap_vit_config_ex base;
+    int pool_head_dim;        /* 0: the pooler's heads are 64 wide, on the kernel conch_v1 has always run (f16 / bf16 only).  64, 96
+                                 or 128: pool_dim = pool_heads * pool_head_dim, softmax scale 1 / sqrt(pool_head_dim), on the
+                                 one-query kernel of ap_attention_probe -- in float32 too, inside the float32 limits of the trunk
+                                 (288 tokens, 64-wide trunk heads) */
+    int pool_skip_final_norm; /* 1: no LayerNorm on the tokens after the last block (open_clip's VisionTransformer with an
+                                 attentional pooler): the pooler's ln_k reads the residual stream, and there are no norm.weight |
+                                 norm.bias parameters */
+    int pool_proj_dim;        /* 0, or P2: the pooled vector (after ln_out) is multiplied by attn_pool.proj.weight [P2, pool_dim]
+                                 without bias (open_clip `proj`); P2 % 128 == 0, P2 <= pool_dim; ap_vit_embed_dim = P2 */
+    int out_normalize;        /* 1: every output row is divided by max(its L2 norm, 1e-12) (encode_image(normalize=True)) */
+} ap_vit_config_ex2;
+#define AP_VIT_CONFIG_SIZE_EX2 112u  /* sizeof(ap_vit_config_ex2) */
 size_t ap_sizeof_vit_config(void);   /* sizeof(ap_vit_config) inside the library */
 /* Zero-fills sizeof_caller bytes at cfg and records sizeof_caller in cfg->struct_size.  AP_ERR_INVALID when cfg is NULL,
  * sizeof_caller < AP_VIT_CONFIG_SIZE_V20 or not a multiple of 4. */
@@ -284,6 +302,8 @@ void ap_vit_destroy(ap_vit* m);
  *   attn_pool.ln_k.weight|bias [dim]   attn_pool.kv.weight [2P, dim] (rows k_proj; v_proj)   attn_pool.kv.bias [2P]
  *   attn_pool.q [P]  (the projected query q_proj(ln_q(query)) + bias: input independent, computed by the host)
  *   attn_pool.out.weight [P, P] | .bias [P]   attn_pool.ln_out.weight|bias [P]
+ *   ap_vit_config_ex2: attn_pool.proj.weight [pool_proj_dim, P] when pool_proj_dim > 0 (open_clip's `proj`, transposed; no bias);
+ *   pool_skip_final_norm: there are no norm.weight / norm.bias parameters
  * AP_POOL_MAP adds (DA = heads * head_dim as stored, H = mlp_dim; SiglipMultiheadAttentionPoolingHead):
  *   map.q [DA]  (W_q probe + b_q, the query third of attention.in_proj applied to the probe: computed by the host)
  *   map.kv.weight [2 DA, dim] (rows k; v of attention.in_proj_weight, heads zero-padded to head_dim)   map.kv.bias [2 DA]
@@ -342,7 +362,8 @@ int ap_vit_finalize(ap_vit* m);
 int ap_vit_set_option(ap_vit* m, int option, int value);
 
 size_t ap_vit_workspace_bytes(const ap_vit* m, int n);
-int ap_vit_embed_dim(const ap_vit* m);   /* dim (AP_POOL_CLS, AP_POOL_MAP), pool_dim (AP_POOL_ATTN) or 2 * dim (AP_POOL_CLS_MEAN) */
+int ap_vit_embed_dim(const ap_vit* m);   /* dim (AP_POOL_CLS, AP_POOL_MAP), pool_dim (AP_POOL_ATTN) or 2 * dim (AP_POOL_CLS_MEAN);
+                                            proj_dim / pool_proj_dim when the configuration has a projection */
 
 /* Optional per-launch timing with HIP events recorded on the forward's own stream (what
  * bench.py's roofline block reads).  Off by default; when on, every kernel launch of a forward
@@ -536,6 +557,10 @@ int ap_attention(int dtype, const void* qkv, void* out, int n, int tokens, int h
  *   a plain conversion.  f16 / bf16.
  * ap_cls_mean_pool: y f32 [n * tokens, dim] -> out f32 [n, 2 * dim] = [row 0 of the image | mean of its rows prefix ..
  *   tokens - 1] (summed in double, one division); prefix >= 1, tokens > prefix.
+ * ap_l2_normalize_rows: out f32 [rows, dim] dense = x[row] / max(||x[row]||, eps), x f32 rows of `stride` elements (torch
+ *   F.normalize; the last step of CoCa's encode_image, out_normalize of ap_vit_config_ex2).  The squares are summed in double, so
+ *   an element carries two float roundings (the norm's, the division's); a row whose norm is below eps is divided by eps: a zero
+ *   row stays zero.  dim % 4 == 0, stride % 4 == 0, stride >= dim, eps > 0; out == x (in place) with stride == dim.
  * ap_stream_to_f32: x T rows of `stride` elements -> dst f32 [rows, dim] dense, exact.  f16 / bf16; dim, stride % 4 == 0.
  * ap_chw_to_patchrows: x [n, 3, S, S] of x_dtype -> dst T [n * g * g, ld], g = S / ps: row (img * g + py) * g + px, column
  *   (c * ps + ky) * ps + kx = x[img][c][py * ps + ky][px * ps + kx], one rounding; columns >= 3 ps^2 are not written.
@@ -567,6 +592,7 @@ int ap_fold_ln(int dtype, const float* w32, int rows, int cols, int ld, const fl
 int ap_fold_ls(int dtype, const float* w32, int rows, int cols, int ld, const float* ls, const float* bias_in, void* wout,
                float* bias_out, ap_stream_t stream);
 int ap_cls_mean_pool(const float* y, int n, int tokens, int prefix, int dim, float* out, ap_stream_t stream);
+int ap_l2_normalize_rows(const float* x, long stride, int rows, int dim, float eps, float* out, ap_stream_t stream);
 int ap_stream_to_f32(int dtype, const void* x, long stride, int rows, int dim, float* dst, ap_stream_t stream);
 int ap_chw_to_patchrows(int x_dtype, int dtype, const void* x, int n, int S, int ps, void* dst, int ld, ap_stream_t stream);
 int ap_cls_stream(int dtype, const float* prefix, int prefix_rows, int img_rows, int n, int tokens, int dim, void* x,
