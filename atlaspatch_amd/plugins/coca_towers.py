@@ -1,7 +1,7 @@
 """``--feature-plugin`` module: the reference's ``omiclip`` (open_clip ``coca_ViT-L-14``, models/patch/omiclip.py) and
 ``conch_v15`` (CONCH v1.5 of the TITAN repository, models/patch/conch.py:67-112) on the native HIP kernels: ViT-L trunks whose
 features come from open_clip's AttentionalPooler with eight 96-wide heads.  The reference only calls the two packages; both
-architectures are restated from the public packages and are UNVERIFIED OFFLINE (``encoders/vit.py::ARCHS``), and parity is
+architectures are restated from the public packages and are UNVERIFIED OFFLINE (``encoders/vit_archs.py::ARCHS``), and parity is
 claimed against that restatement (tests/coca_reference.py), not against the packages.
 
     python -m atlaspatch_amd process SLIDE -o OUT --feature-extractors omiclip,conch_v15 --feature-precision float16 \
