@@ -10,6 +10,7 @@
 //   delta, delta2 T [M, D] branch outputs (fc2 / proj) waiting to be folded into tok by a LayerNorm launch
 //   hid   T   [M, mlp]    GELU(fc1) ; the patch-row matrix [n*P, Kpe] aliases it
 // Weights are converted once to T, K-contiguous ([out, in], exactly the checkpoint layout).
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -168,9 +169,16 @@ Workspace carve(const ap_vit* m, int n, char* base) {
     Workspace w;
     const size_t o_tok = take(M * D * 4);
     const size_t o_xn = take(M * D * es);
-    const size_t o_qkv = take(M * 3 * (size_t)m->dattn * es);
-    const size_t o_att = take(M * (size_t)m->dattn * es);
-    const size_t o_delta = take(M * D * es);
+    // The heads of run_blocks put other data into qkv, att and delta, so each is sized for the largest thing that lands in it.
+    // With heads * head_dim < dim the blocks' own tensors are the smaller ones: f32 y [M, D] (final LayerNorm of every token,
+    // AP_POOL_CLS_MEAN and AP_POOL_ATTN with the norm kept) would run through att into delta, which the launch that writes y
+    // still reads as the pending branch of the f32 stream.  At heads * head_dim == dim the first term is the larger one.
+    const ap_vit_config& c = m->cfg;
+    const bool writes_y = c.pool == AP_POOL_CLS_MEAN || (c.pool == AP_POOL_ATTN && !m->pool_skip_norm);
+    const size_t head_rows = c.pool == AP_POOL_ATTN ? (size_t)c.pool_dim : (size_t)c.proj_dim;   // pooled T [n, P] / CLIP projection T [n, proj_dim] in att
+    const size_t o_qkv = take(std::max(M * 3 * (size_t)m->dattn * es, writes_y ? M * D * 4 : (size_t)0));
+    const size_t o_att = take(std::max(M * (size_t)m->dattn * es, (size_t)n * head_rows * es));
+    const size_t o_delta = take(std::max(M * D * es, c.pool == AP_POOL_ATTN ? (size_t)n * c.pool_dim * 4 : (size_t)0));   // o32 f32 [n, P]
     const size_t o_delta2 = take(M * D * es);
     // SwiGLU: fc1 output [M, 2 mlp] followed by the gated product [M, mlp] (ws.hid2)
     size_t hid_bytes = M * (size_t)(m->cfg.mlp_type == AP_MLP_SWIGLU ? 3 * m->cfg.mlp_dim : m->cfg.mlp_dim) * es;
@@ -516,7 +524,8 @@ int run_blocks(ap_vit* m, int n, const Workspace& w, float* out, hipStream_t str
     const float* pending_ls = st.pending_ls;
     if (c.pool == AP_POOL_CLS && c.proj_dim > 0) {
         // CLIP: final LayerNorm on the class rows in the compute type (xn, T [n, D]), the bias-free visual projection on the
-        // 128 x 128 kernel (att, T [n, P]), widened to f32.  (The reference's half-precision model does the same roundings.)
+        // 128 x 128 kernel (att, T [n, P]; carve() sizes att for it), widened to f32.  (The reference's half-precision model does
+        // the same roundings.)
         const int P = c.proj_dim;
         if ((rc = ap::launch_add_layernorm(dt, dt, w.tok, st.tok_stride, pending, st.pending_stride, pending_ls, n, D, m->norm_w,
                                            m->norm_b, c.ln_eps, w.xn, stream)) != AP_OK) return rc;
@@ -536,7 +545,9 @@ int run_blocks(ap_vit* m, int n, const Workspace& w, float* out, hipStream_t str
         // ---- SigLIP's attention-pooling head (transformers SiglipMultiheadAttentionPoolingHead): final LN on all tokens in the
         // compute type (xn, the kv GEMM's A operand), kv T [M, 2 DA] in qkv, the probe's attention per (image, head) (att, T [n, DA]),
         // out_proj into the caller's buffer in f32 (r), LayerNorm(r) (xn, T [n, D]), fc1 + tanh GELU (hid, T [n, H]) and fc2 added
-        // to r in place in f32.  The n-row GEMMs run on the 128 x 128 kernel (cls_tail_rows).
+        // to r in place in f32.  The n-row GEMMs run on the 128 x 128 kernel (cls_tail_rows).  Every reuse fits without a
+        // check in ap_vit_create: kv [M, 2 DA] lies in qkv [M, 3 DA], the probe's output [n, DA] in att [M, DA], and [n, D] in xn and
+        // [n, H] in hid are the first n of the M rows the blocks wrote there.
         const int DA = m->dattn, H = c.mlp_dim;
         const ap::MapParams& mp = m->map;
         { ScopedTimer t(m->prof, AP_PROF_LAYERNORM, stream);
@@ -579,7 +590,7 @@ int run_blocks(ap_vit* m, int n, const Workspace& w, float* out, hipStream_t str
         if ((rc = ap::launch_add_layernorm(dt, dt, w.tok, D, pending, D, pending_ls, M, D, pp.ln_k_w, pp.ln_k_b, c.pool_ln_eps, w.xn,
                                            stream)) != AP_OK) return rc;
     } else {
-        // the other poolings: final LN on ALL tokens (y f32 [M, D], reuses qkv)
+        // the other poolings: final LN on ALL tokens (y f32 [M, D], reuses qkv: carve() sizes qkv for it)
         float* y = (float*)w.qkv;
         if ((rc = ap::launch_add_layernorm(dt, AP_F32, w.tok, D, pending, D, pending_ls, M, D, m->norm_w, m->norm_b, c.ln_eps, y,
                                            stream)) != AP_OK) return rc;
@@ -589,8 +600,9 @@ int run_blocks(ap_vit* m, int n, const Workspace& w, float* out, hipStream_t str
                                        stream)) != AP_OK) return rc;
     }
     // ---- AP_POOL_ATTN (CONCH / CoCa visual towers): the one-query attentional pooler on the normalised tokens.
-    // Buffers: xk T [M, D] = xn, kv T [M, 2P] reuses hid, pooled T [n, P] = att, o32 f32 [n, P] reuses delta; with a projection
-    // ln_out's rows T [n, P] go to xn (the kv GEMM has read it) and the product straight into the caller's buffer in f32.
+    // Buffers: xk T [M, D] = xn, kv T [M, 2P] reuses hid (ap_vit_create: 2P <= mlp_dim), pooled T [n, P] = att and o32 f32 [n, P]
+    // reuses delta (carve() sizes both for it); with a projection ln_out's rows T [n, P] go to xn (the kv GEMM has read it;
+    // P <= 3D / 2 <= tokens * D, a sequence has two tokens at least) and the product straight into the caller's buffer in f32.
     {
         ap::GemmArgs g{};
         g.A = w.xn; g.lda = D; set_weight(m, g, pp.kv); g.M = M; g.N = 2 * P; g.K = D;
@@ -674,6 +686,13 @@ void mark_set(ap_vit* m, const char* name, Param& p) {
     }
 }
 
+// The heads hand `out` to kernels that store four floats per lane (the n-row GEMMs of the projections and of the MAP head,
+// ap_l2_normalize_rows): refused here, before any launch, instead of by one of them in the middle of a forward.
+int check_out_alignment(const char* who, const float* out) {
+    AP_REQUIRE(((uintptr_t)out & 15) == 0, "%s: out must be 16-byte aligned", who);
+    return AP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -716,6 +735,9 @@ int ap_vit_create(const ap_vit_config* cfg, ap_vit** out) {
     AP_REQUIRE(hd == 64 || hd == 128 || (hd == 96 && c.compute_dtype != AP_F32),
                "vit_create: head_dim %d: q / k / v heads must be stored 64, 96 (f16 / bf16) or 128 wide (zero-pad other widths and set attn_scale)", hd);
     AP_REQUIRE(c.dim % 128 == 0 && c.mlp_dim % 128 == 0, "vit_create: dim and mlp_dim must be multiples of 128");
+    // (with head_dim = dim / heads this is dim again; a forward used to meet it in its first qkv GEMM, after the patch embedding)
+    AP_REQUIRE((c.heads * hd) % 128 == 0, "vit_create: heads %d x head_dim %d = %d: the width of q, k and v must be a multiple of 128 "
+               "(the column granularity of the qkv GEMM)", c.heads, hd, c.heads * hd);
     AP_REQUIRE(c.reg_tokens >= 0 && c.reg_tokens <= 64, "vit_create: reg_tokens %d", c.reg_tokens);
     AP_REQUIRE(c.mlp_type == AP_MLP_GELU || c.mlp_type == AP_MLP_SWIGLU, "vit_create: mlp_type %d", c.mlp_type);
     AP_REQUIRE(c.attn_scale >= 0.f, "vit_create: attn_scale %g", (double)c.attn_scale);
@@ -1081,6 +1103,7 @@ int ap_vit_forward_u8(ap_vit* m, const uint8_t* patches, int n, int h, int w, co
                       ap_stream_t stream) {
     int rc = ap::check_forward_args("vit", m, n, patches && out, workspace, workspace_bytes, ap_vit_workspace_bytes);
     if (rc != AP_OK || n == 0) return rc;
+    if ((rc = check_out_alignment("vit_forward_u8", out)) != AP_OK) return rc;
     const int S = m->cfg.image_size;
     AP_REQUIRE(h >= S && w >= S, "vit_forward_u8: %dx%d tiles smaller than the %d model input "
                "(resampling preprocess not in this build)", h, w, S);
@@ -1123,6 +1146,7 @@ int ap_vit_forward_chw(ap_vit* m, const void* x, int x_dtype, int n, float* out,
                        size_t workspace_bytes, ap_stream_t stream) {
     int rc = ap::check_forward_args("vit", m, n, x && out, workspace, workspace_bytes, ap_vit_workspace_bytes);
     if (rc != AP_OK || n == 0) return rc;
+    if ((rc = check_out_alignment("vit_forward_chw", out)) != AP_OK) return rc;
     AP_REQUIRE(x_dtype == AP_F32 || x_dtype == m->cfg.compute_dtype,
                "vit_forward_chw: input dtype %d must be f32 or the compute dtype", x_dtype);
     const Workspace ws = carve(m, n, (char*)workspace);

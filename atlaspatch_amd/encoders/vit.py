@@ -29,12 +29,14 @@ ACT_CODES = {"quick_gelu": 1, "gelu_tanh": 2}          # 0 = erf GELU
 
 def vit_config(arch: dict, dtype: torch.dtype):
     """The structure ``ap_vit_create`` takes for ``arch``.  Heads and MLP are given as the device stores them (``stored_head_dim``,
-    ``stored_mlp_dim``); ``attn_scale`` is 1 / sqrt(true head width) where the stored width differs, else 0 (= the default).  The
+    ``stored_mlp_dim``); ``attn_scale`` is 1 / sqrt(true head width) where the stored width differs, else 0 (= the default); the
+    true width is dim / heads unless ``arch`` has a "head_dim" (attention narrower than the stream: no model of the zoo).  The
     fields appended since ABI v20 travel in the longer structures only when one of them is set: ``VitConfigEx`` (96 bytes) for
     ``no_class_token``, ``VitConfigEx2`` (112 bytes) for the CoCa / CONCH v1.5 pooler's; every other model hands over the 92 bytes
     of ``VitConfig``, as before."""
     flag = lambda key: 1 if arch.get(key) else 0
-    hd_true, hd_stored = arch["dim"] // arch["heads"], stored_head_dim(arch["dim"], arch["heads"])
+    hd_true = int(arch.get("head_dim") or arch["dim"] // arch["heads"])        # "head_dim": heads narrower than dim / heads
+    hd_stored = stored_head_dim(arch["dim"], arch["heads"], hd_true)
     fields = dict(
         image_size=arch["image_size"], patch_size=arch["patch_size"], dim=arch["dim"], depth=arch["depth"], heads=arch["heads"],
         mlp_dim=stored_mlp_dim(arch["mlp_dim"]), ln_eps=float(arch["ln_eps"]), layer_scale=flag("layer_scale"),
@@ -66,7 +68,7 @@ class HipViT(NativeEncoder):
         # features: the pooler's (attn), [class token | mean patch token] (cls_mean), else dim floats; a projection's output if any
         self.embed_dim = int(arch.get("pool_proj_dim") or arch.get("proj_dim") or
                              {"attn": arch.get("pool_dim"), "cls_mean": 2 * arch["dim"]}.get(arch.get("pool"), arch["dim"]))
-        state = pad_heads(state, dim=arch["dim"], heads=arch["heads"], depth=arch["depth"])
+        state = pad_heads(state, dim=arch["dim"], heads=arch["heads"], depth=arch["depth"], head_dim=arch.get("head_dim"))
         state = pad_mlp(state, mlp_dim=arch["mlp_dim"], depth=arch["depth"], swiglu=arch.get("mlp") == "swiglu")
         self._open(vit_config(arch, dtype), state)
 

@@ -344,6 +344,8 @@ def canonical_shapes(arch: dict) -> dict:
     """Canonical key -> shape BEFORE head / MLP padding of any ``ARCHS``-style dict: the parameter set ``random_canonical_state_dict``
     draws and the strict adapters check a checkpoint against."""
     d, mlp, ps, pool = arch["dim"], arch["mlp_dim"], arch["patch_size"], arch.get("pool")
+    hd = int(arch.get("head_dim") or d // arch["heads"])                # "head_dim": heads narrower than dim / heads (da < d)
+    da = arch["heads"] * hd
     reg, patches = int(arch.get("reg_tokens", 0)), (arch["image_size"] // ps) ** 2
     rows = patches if (arch.get("no_embed_class") or arch.get("no_class_token")) else 1 + reg + patches
     f1 = 2 * mlp if arch.get("mlp") == "swiglu" else mlp
@@ -359,7 +361,7 @@ def canonical_shapes(arch: dict) -> dict:
     if not arch.get("pool_skip_final_norm"):
         want.update({"norm.weight": (d,), "norm.bias": (d,)})
     if pool == "map":
-        want.update({"map.q": (d,), "map.kv.weight": (2 * d, d), "map.kv.bias": (2 * d,), "map.out.weight": (d, d), "map.out.bias": (d,),
+        want.update({"map.q": (da,), "map.kv.weight": (2 * da, d), "map.kv.bias": (2 * da,), "map.out.weight": (d, da), "map.out.bias": (d,),
                      "map.ln.weight": (d,), "map.ln.bias": (d,), "map.fc1.weight": (mlp, d), "map.fc1.bias": (mlp,),
                      "map.fc2.weight": (d, mlp), "map.fc2.bias": (d,)})
     if arch.get("pre_norm"):
@@ -371,11 +373,11 @@ def canonical_shapes(arch: dict) -> dict:
     if arch.get("proj_dim"):
         want["head_proj.weight"] = (arch["proj_dim"], d)
     if arch.get("rope"):
-        want.update({"rope.cos": (patches, d // arch["heads"]), "rope.sin": (patches, d // arch["heads"])})
+        want.update({"rope.cos": (patches, hd), "rope.sin": (patches, hd)})
     for i in range(arch["depth"]):
         b = f"blocks.{i}."
-        want.update({b + "ln1.weight": (d,), b + "ln1.bias": (d,), b + "qkv.weight": (3 * d, d), b + "qkv.bias": (3 * d,),
-                     b + "proj.weight": (d, d), b + "proj.bias": (d,), b + "ln2.weight": (d,), b + "ln2.bias": (d,),
+        want.update({b + "ln1.weight": (d,), b + "ln1.bias": (d,), b + "qkv.weight": (3 * da, d), b + "qkv.bias": (3 * da,),
+                     b + "proj.weight": (d, da), b + "proj.bias": (d,), b + "ln2.weight": (d,), b + "ln2.bias": (d,),
                      b + "fc1.weight": (f1, d), b + "fc1.bias": (f1,), b + "fc2.weight": (d, mlp), b + "fc2.bias": (d,)})
         if arch.get("layer_scale"):
             want.update({b + "ls1": (d,), b + "ls2": (d,)})
@@ -514,10 +516,11 @@ def to_canonical(state_dict: dict, spec: dict, source: str = "auto") -> tuple[di
 
 
 # ----------------------------------------------------------------------------- what the device stores
-def stored_head_dim(dim: int, heads: int) -> int:
+def stored_head_dim(dim: int, heads: int, head_dim: Optional[int] = None) -> int:
     """Width of one q / k / v head as the device stores it: 64, 96 or 128 (other true widths are zero-padded up; 96 -- the 80-wide
-    heads of ViT-H/14 and Virchow -- exists in the float16 / bfloat16 attention kernels only, like 128)."""
-    hd = dim // heads
+    heads of ViT-H/14 and Virchow -- exists in the float16 / bfloat16 attention kernels only, like 128).  ``head_dim``: the true
+    width where it is not dim / heads (an ``ARCHS``-style dict's "head_dim")."""
+    hd = int(head_dim or dim // heads)
     if hd <= 64:
         return 64
     if hd <= 96:
@@ -527,12 +530,12 @@ def stored_head_dim(dim: int, heads: int) -> int:
     raise ValueError(f"head width {hd} (dim {dim} / heads {heads}) exceeds 128")
 
 
-def pad_heads(state: dict, *, dim: int, heads: int, depth: int) -> dict:
+def pad_heads(state: dict, *, dim: int, heads: int, depth: int, head_dim: Optional[int] = None) -> dict:
     """Canonical state dict -> the same model with every attention head zero-padded from dim / heads to
     ``stored_head_dim`` channels: qkv rows [3, heads, hd, :] -> [3, heads, hdp, :], proj columns likewise.  Zero q / k
     channels add nothing to q.k, zero v channels give zero outputs that meet zero proj columns: the function is unchanged
     as long as the softmax scale stays 1 / sqrt(hd) (``attn_scale``)."""
-    hd, hdp = dim // heads, stored_head_dim(dim, heads)
+    hd, hdp = int(head_dim or dim // heads), stored_head_dim(dim, heads, head_dim)
     if hd == hdp:
         return state
     out = dict(state)

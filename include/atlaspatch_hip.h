@@ -215,7 +215,10 @@ typedef struct ap_vit_config {
     int head_dim;        /* 0 = dim / heads (must be 64); else the width of one head of q / k / v as STORED: qkv.weight has
                             3 * heads * head_dim rows, proj.weight heads * head_dim columns (64, 128, or -- float16 / bfloat16 --
                             96).  A model whose true head width is none of these (vit_h_14, Virchow: 80) is uploaded zero-padded
-                            to the next one (96) with attn_scale set */
+                            to the next one (96) with attn_scale set.  heads * head_dim may be smaller than dim (attention narrower
+                            than the stream: dim 512, 2 heads of 64): accepted for every pooling as long as heads * head_dim is a
+                            multiple of 128 (else AP_ERR_INVALID), and the workspace is sized for what the pooling heads put into
+                            the blocks' q | k | v, attention-output and branch buffers (tested against a float64 reference) */
     float attn_scale;    /* 0 = 1 / sqrt(head_dim); else the softmax scale (vit_h_14: 1 / sqrt(80)) */
     /* ---- ABI v18: CLIP vision towers (models/patch/clip.py, plip.py, quilt.py: open_clip VisionTransformer / transformers
      *      CLIPVisionModel).  All zero = the v17 behaviour. */
@@ -383,7 +386,10 @@ int ap_vit_profile_enable(ap_vit* m, int on);
 int ap_vit_profile_read(ap_vit* m, double* ms_by_kind, long long* launches_by_kind, int kinds);
 
 /* patches: device uint8 [n, h, w, 3]; centre-cropped to image_size, normalised with
- * mean/std, embedded.  out: device float32 [n, dim].  Asynchronous on `stream`.
+ * mean/std, embedded.  out: device float32 [n, ap_vit_embed_dim], 16-byte aligned: both forwards refuse another address with
+ * AP_ERR_INVALID before any launch (the heads store four floats per lane).  workspace: 256-byte aligned, ap_vit_workspace_bytes(m, n)
+ * bytes are all a forward touches; fewer: AP_ERR_WORKSPACE, nothing launched.  No forward reads a workspace byte it has not
+ * written in the same call.  Asynchronous on `stream`.
  * For the CLS readout the last block computes K / V for every token and everything after that for the CLS row
  * only (nothing reads the other rows; identical features; AP_VIT_OPT_FULL_LAST_BLOCK disables it). */
 int ap_vit_forward_u8(ap_vit* m, const uint8_t* patches, int n, int h, int w,
@@ -645,7 +651,8 @@ int ap_resnet_embed_dim(const ap_resnet* m);   /* 8 x stem_width (basic) or 32 x
 int ap_resnet_profile_enable(ap_resnet* m, int on);
 int ap_resnet_profile_read(ap_resnet* m, double* ms_by_kind, long long* launches_by_kind, int kinds);
 /* patches: device uint8 [n, h, w, 3] (h, w >= image_size): centre crop, normalise, network, global average pool.
- * out: device float32 [n, embed_dim].  Same arguments as ap_vit_forward_u8; asynchronous on `stream`. */
+ * out: device float32 [n, embed_dim] at any float-aligned address (the pool stores single floats: the same bits wherever out
+ * lies).  Same arguments and workspace rules as ap_vit_forward_u8; asynchronous on `stream`. */
 int ap_resnet_forward_u8(ap_resnet* m, const uint8_t* patches, int n, int h, int w,
                          const float mean[3], const float stdv[3],
                          float* out, void* workspace, size_t workspace_bytes, ap_stream_t stream);
@@ -704,7 +711,7 @@ int ap_convnext_embed_dim(const ap_convnext* m);   /* widths[3] */
 #define AP_CONVNEXT_PROF_KINDS 6
 int ap_convnext_profile_enable(ap_convnext* m, int on);
 int ap_convnext_profile_read(ap_convnext* m, double* ms_by_kind, long long* launches_by_kind, int kinds);
-/* Same arguments and semantics as ap_resnet_forward_u8; out: device float32 [n, widths[3]]. */
+/* Same arguments and semantics as ap_resnet_forward_u8 (out at any float-aligned address); out: device float32 [n, widths[3]]. */
 int ap_convnext_forward_u8(ap_convnext* m, const uint8_t* patches, int n, int h, int w,
                            const float mean[3], const float stdv[3],
                            float* out, void* workspace, size_t workspace_bytes, ap_stream_t stream);
@@ -779,7 +786,7 @@ int ap_swin_embed_dim(const ap_swin* m);   /* 8 x embed_dim */
 #define AP_SWIN_PROF_KINDS 9
 int ap_swin_profile_enable(ap_swin* m, int on);
 int ap_swin_profile_read(ap_swin* m, double* ms_by_kind, long long* launches_by_kind, int kinds);
-/* Same arguments and semantics as ap_convnext_forward_u8; out: device float32 [n, 8 x embed_dim]. */
+/* Same arguments and semantics as ap_convnext_forward_u8 (out at any float-aligned address); out: device float32 [n, 8 x embed_dim]. */
 int ap_swin_forward_u8(ap_swin* m, const uint8_t* patches, int n, int h, int w,
                        const float mean[3], const float stdv[3],
                        float* out, void* workspace, size_t workspace_bytes, ap_stream_t stream);
@@ -849,7 +856,9 @@ int ap_clip_resnet_embed_dim(const ap_clip_resnet* m);   /* output_dim */
 #define AP_CLIP_RESNET_PROF_KINDS 5
 int ap_clip_resnet_profile_enable(ap_clip_resnet* m, int on);
 int ap_clip_resnet_profile_read(ap_clip_resnet* m, double* ms_by_kind, long long* launches_by_kind, int kinds);
-/* Same arguments and semantics as ap_resnet_forward_u8; out: device float32 [n, output_dim]. */
+/* Same arguments and semantics as ap_resnet_forward_u8; out: device float32 [n, output_dim] at any float-aligned address, the
+ * same bits wherever it lies (float32: the last convolution writes a 16-byte aligned out itself and goes through a workspace
+ * buffer and a copy otherwise). */
 int ap_clip_resnet_forward_u8(ap_clip_resnet* m, const uint8_t* patches, int n, int h, int w,
                               const float mean[3], const float stdv[3],
                               float* out, void* workspace, size_t workspace_bytes, ap_stream_t stream);

@@ -260,10 +260,12 @@ def _ln(x, w, b, eps):
 def canonical_forward(state, x, arch, dtype=torch.float64):
     """x [n, 3, S, S] -> features, from the canonical state dict (``ap_vit_set_param`` names) and an ``ARCHS``-style dict, in plain
     matrix products in ``dtype``.  Honours every field the two towers use, the four of ``ap_vit_config_ex2`` included
-    (``pool_head_dim`` 0 = 64)."""
+    (``pool_head_dim`` 0 = 64), an optional ``head_dim`` -- H heads of that width whatever dim / H is: ``qkv.weight`` [3 H hd, D],
+    ``proj.weight`` [D, H hd], scale 1 / sqrt(hd) -- and the readouts ``pool`` "attn", "cls_mean" ([class token | mean of the patch
+    tokens] after the final norm) and none (the class token after the final norm)."""
     s = {k: v.to(dtype) for k, v in state.items()}
     n, S, ps, D, H = x.shape[0], arch["image_size"], arch["patch_size"], arch["dim"], arch["heads"]
-    g, hd = S // ps, D // H
+    g, hd = S // ps, int(arch.get("head_dim") or D // H)
     rows = x.to(dtype).reshape(n, 3, g, ps, g, ps).permute(0, 2, 4, 1, 3, 5).reshape(n, g * g, 3 * ps * ps)
     t = rows @ s["patch_embed.weight"].reshape(D, -1).T + s["patch_embed.bias"]
     t = torch.cat([s["cls_token"].reshape(1, 1, D).expand(n, 1, D), t], 1) + s["pos_embed"]
@@ -275,7 +277,7 @@ def canonical_forward(state, x, arch, dtype=torch.float64):
         y = _ln(t, s[b + "ln1.weight"], s[b + "ln1.bias"], arch["ln_eps"])
         q, k, v = (y @ s[b + "qkv.weight"].T + s[b + "qkv.bias"]).reshape(n, T, 3, H, hd).permute(2, 0, 3, 1, 4)
         a = torch.softmax(q @ k.transpose(-1, -2) / math.sqrt(hd), -1) @ v
-        o = a.permute(0, 2, 1, 3).reshape(n, T, D) @ s[b + "proj.weight"].T + s[b + "proj.bias"]
+        o = a.permute(0, 2, 1, 3).reshape(n, T, H * hd) @ s[b + "proj.weight"].T + s[b + "proj.bias"]
         t = t + (o * s[b + "ls1"] if arch.get("layer_scale") else o)
         y = _ln(t, s[b + "ln2.weight"], s[b + "ln2.bias"], arch["ln_eps"])
         h = y @ s[b + "fc1.weight"].T + s[b + "fc1.bias"]
@@ -284,6 +286,10 @@ def canonical_forward(state, x, arch, dtype=torch.float64):
         t = t + (o * s[b + "ls2"] if arch.get("layer_scale") else o)
     if not arch.get("pool_skip_final_norm"):
         t = _ln(t, s["norm.weight"], s["norm.bias"], arch["ln_eps"])
+    if arch.get("pool") == "cls_mean":
+        return torch.cat([t[:, 0], t[:, 1:].mean(1)], -1)
+    if arch.get("pool") != "attn":
+        return t[:, 0]
     P, ph = arch["pool_dim"], arch["pool_heads"]
     pw = arch.get("pool_head_dim") or 64
     assert P == ph * pw
@@ -319,9 +325,11 @@ def toggled(arch, field):
 
 def full_state(arch, seed):
     """A canonical state dict that holds EVERY optional tensor (norm.*, attn_pool.proj.weight, ...), seeded like ``seed_module``, so
-    that any toggle of the four fields finds its parameters; ``select`` cuts it down to what one configuration uploads."""
+    that any toggle of the four fields finds its parameters; ``select`` cuts it down to what one configuration uploads.  With
+    ``head_dim`` the attention is heads x head_dim wide; without ``pool_dim`` there are no ``attn_pool.*`` tensors."""
     g = torch.Generator().manual_seed(seed)
-    d, mlp, ps, P = arch["dim"], arch["mlp_dim"], arch["patch_size"], arch["pool_dim"]
+    d, mlp, ps, P = arch["dim"], arch["mlp_dim"], arch["patch_size"], arch.get("pool_dim")
+    da = arch["heads"] * int(arch.get("head_dim") or d // arch["heads"])
     tokens = 1 + (arch["image_size"] // ps) ** 2
     mat = lambda r, c: torch.randn(r, c, generator=g) * (1.4 * c ** -0.5)
     vec = lambda k: torch.randn(k, generator=g) * 0.3
@@ -331,10 +339,12 @@ def full_state(arch, seed):
          "pre_norm.weight": gain(d), "pre_norm.bias": vec(d)}
     for i in range(arch["depth"]):
         b = f"blocks.{i}."
-        s.update({b + "ln1.weight": gain(d), b + "ln1.bias": vec(d), b + "qkv.weight": mat(3 * d, d), b + "qkv.bias": vec(3 * d),
-                  b + "proj.weight": mat(d, d), b + "proj.bias": vec(d), b + "ln2.weight": gain(d), b + "ln2.bias": vec(d),
+        s.update({b + "ln1.weight": gain(d), b + "ln1.bias": vec(d), b + "qkv.weight": mat(3 * da, d), b + "qkv.bias": vec(3 * da),
+                  b + "proj.weight": mat(d, da), b + "proj.bias": vec(d), b + "ln2.weight": gain(d), b + "ln2.bias": vec(d),
                   b + "fc1.weight": mat(mlp, d), b + "fc1.bias": vec(mlp), b + "fc2.weight": mat(d, mlp), b + "fc2.bias": vec(d),
                   b + "ls1": 0.3 + 0.4 * torch.rand(d, generator=g), b + "ls2": 0.3 + 0.4 * torch.rand(d, generator=g)})
+    if not P:
+        return s
     s.update({"attn_pool.q": torch.randn(P, generator=g) * 5.0, "attn_pool.ln_k.weight": gain(d), "attn_pool.ln_k.bias": vec(d),
               "attn_pool.kv.weight": mat(2 * P, d), "attn_pool.kv.bias": vec(2 * P), "attn_pool.out.weight": mat(P, P),
               "attn_pool.out.bias": vec(P), "attn_pool.ln_out.weight": gain(P), "attn_pool.ln_out.bias": vec(P),

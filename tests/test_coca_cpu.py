@@ -208,3 +208,39 @@ def test_each_new_field_shows_in_the_reference_far_above_the_device_tolerance(fo
         r = R.rel(R.canonical_forward(state, x, R.toggled(arch, field)), base)
         print(f"{form} width {width}: {field} toggled moves the reference by {r:.3f} (floor {floor})")
         assert r > floor, (form, width, field, r)
+
+
+# ----------------------------------------------------------------------------- head_dim and the class readouts of the reference
+def _narrow_arch(head_dim, pool):
+    arch = dict(image_size=64, patch_size=16, dim=512, depth=2, heads=2, head_dim=head_dim, mlp_dim=512, ln_eps=1e-6, layer_scale=False)
+    if pool == "attn":
+        arch.update(pool="attn", pool_dim=256, pool_heads=4, pool_ln_eps=1e-5, pool_head_dim=64)
+    elif pool:
+        arch["pool"] = pool
+    return arch
+
+
+@pytest.mark.parametrize("pool", [None, "cls_mean", "attn"])
+def test_reference_moves_with_head_dim(pool):
+    """tests/test_gpu_engine_workspace.py compares the engine at heads * head_dim < dim with ``canonical_forward``: the reference
+    must use the field.  Two heads of 64 in a 512-wide stream against the same tensors read as four heads of 32 (head_dim is all
+    that tells them apart): more than 0.3 apart norm-wise, ten times the loosest device bound.  head_dim = dim / heads
+    spelled out is the old forward bit for bit, and the class-token readout is the first half of "cls_mean"."""
+    x = R.images(3, 64)
+    narrow = _narrow_arch(64, pool)
+    full = R.full_state(narrow, seed=41)
+    assert tuple(full["blocks.0.qkv.weight"].shape) == (384, 512) and tuple(full["blocks.1.proj.weight"].shape) == (512, 128)
+    want = R.canonical_forward(R.select(full, narrow), x, narrow)
+    assert tuple(want.shape) == (3, {None: 512, "cls_mean": 1024, "attn": 256}[pool]) and bool(torch.isfinite(want).all())
+    regrouped = dict(narrow, heads=4, head_dim=32)       # the same tensors read as four heads of 32: other groups, other scale
+    moved = R.rel(R.canonical_forward(R.select(full, regrouped), x, regrouped), want)
+    print(f"2 heads of 64 -> 4 heads of 32 on the same tensors, pool {pool}: the reference moves by {moved:.3f}")
+    assert moved > 0.3
+    implicit = {k: v for k, v in _narrow_arch(256, pool).items() if k != "head_dim"}
+    st = R.full_state(implicit, seed=42)
+    a = R.canonical_forward(R.select(st, implicit), x, implicit)
+    b = R.canonical_forward(R.select(st, implicit), x, dict(implicit, head_dim=256))
+    assert torch.equal(a, b)
+    if pool == "cls_mean":
+        cls = R.canonical_forward(R.select(full, narrow), x, {k: v for k, v in narrow.items() if k != "pool"})
+        assert torch.equal(want[:, :512], cls)
