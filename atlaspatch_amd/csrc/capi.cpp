@@ -169,8 +169,9 @@ static inline bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
 static int gemm_contract(const char* fn, int dtype, int epilogue, const ap::GemmArgs& g, int impl) {
     const size_t es = ap::dtype_size(dtype), oes = epilogue == ap::EPI_BIAS_RESID ? 4 : es;
     const int kt = 128 / (int)es, ocols = epilogue == ap::EPI_NORM_SWIGLU ? g.N / 2 : g.N;
+    const int nt = g.split ? 32 : 128;       // the split-f16 form (impl 129) masks the 128-wide tile's tail
     AP_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, "%s: empty problem %d x %d x %d", fn, g.M, g.N, g.K);
-    AP_REQUIRE(g.N % 128 == 0 && g.K % kt == 0, "%s: N = %d must be a multiple of 128 and K = %d of %d", fn, g.N, g.K, kt);
+    AP_REQUIRE(g.N % nt == 0 && g.K % kt == 0, "%s: N = %d must be a multiple of %d and K = %d of %d", fn, g.N, nt, g.K, kt);
     AP_REQUIRE(g.lda >= g.K && g.ldw >= g.K && g.ldo >= ocols, "%s: row strides (lda %d, ldw %d, ldo %d) smaller than the rows (K = %d, %d output columns)",
                fn, g.lda, g.ldw, g.ldo, g.K, ocols);
     AP_REQUIRE(((size_t)g.lda * es) % 16 == 0 && ((size_t)g.ldw * es) % 16 == 0 && aligned16(g.A, g.W),
@@ -202,9 +203,8 @@ int ap_gemm(int dtype, int epilogue, const void* A, int lda, const void* W, int 
         AP_REQUIRE(dtype == AP_F32, "ap_gemm: impl 129 (split-f16 products) takes float32 buffers");
         g.split = 1;
         impl = 128;
-    } else if (const int rc = gemm_contract("ap_gemm", dtype, epilogue, g, impl); rc != AP_OK) {
-        return rc;
     }
+    if (const int rc = gemm_contract("ap_gemm", dtype, epilogue, g, impl); rc != AP_OK) return rc;
     return ap::launch_gemm_impl(dtype, epilogue, g, impl, variant, (hipStream_t)stream);
 }
 

@@ -370,6 +370,13 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
                     // separate residual (the SAM2 trunk's x = shortcut + f(x)): added AFTER the activation, GemmArgs::resid
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = act_f32<kAct>(v[e]);
+                    if constexpr (EPI == EPI_BIAS_STORE) {               // LayerScale, where the exact chain below applies it
+                        if (g.gamma) {
+                            const f32x4 ga = *(const f32x4*)(g.gamma + n);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) v[e] *= ga[e];
+                        }
+                    }
                     if (g.resid) {
                         const f32x4 r = *(const f32x4*)(g.resid + (size_t)rrow * (size_t)g.ldr + n);
 #pragma unroll

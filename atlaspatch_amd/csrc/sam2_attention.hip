@@ -23,10 +23,16 @@
 // Softmax in the log2 domain (scale * log2(e) folded into the exponent), float32 throughout.
 //
 // Split-f16 form (SPLIT, round 6; the default -- ap_sattention_f32's `exact` argument selects the chain above): every operand
-// x = hi + lo with hi = f16(x), lo = f16(x - hi) (22 of 24 mantissa bits; the f16 MFMA takes subnormal operands exactly --
-// tools/isa_probes/mfma_f16_denorm.hip -- so a small lo only loses absolute precision below 2^-25) and both products as
-//     a b ~= a_hi b_hi + a_hi b_lo + a_lo b_hi        three v_mfma_f32_32x32x16_f16 into the SAME f32 accumulator
-// 36 MFMAs of 32 cycles per 32-key tile at d = 96 instead of 96 of 64 cycles; the split costs ~3 VALU per value.  Same
+// x = hi + lo 2^-11 with hi = f16(x), lo = f16((x - hi) 2^11), gemm.hip's split: 22 of 24 mantissa bits, and lo stays a NORMAL
+// f16 wherever hi is one.  (Unscaled, lo = f16(x - hi) is an f16 subnormal for every |x| < 2^-2 -- nearly every softmax weight
+// -- and loses 2^-25 ABSOLUTE whatever the value's size: measured per element, 2^-13 of a value at 2^-12 and errors that add up
+// over identical keys; tests/test_gpu_split_f16.py, families tiny / channel_ladder / coherent.)  Both products as
+//     a b ~= a_hi b_hi + 2^-11 (a_hi b_lo + a_lo b_hi)        three v_mfma_f32_32x32x16_f16
+// with the two small terms of a tile summed in an accumulator of their own (it starts from the MFMA's inline zero) and folded
+// in with one fma per element when the tile's product is complete.  36 MFMAs of 32 cycles per 32-key tile at d = 96 instead of
+// 96 of 64 cycles; the split costs ~3 VALU per value (sa_split8), and Q is split ONCE, on its way into LDS (hi and lo of eight
+// values take the 32 bytes the eight floats took), not once per tile: the loop is bound by its VALU work, not by the MFMAs, and
+// that is what pays for the scaling (4096 x 4096 keys, 4 heads of 96: 130.5 us against 134 us with the unscaled halves).  Same
 // loads, same fragment assignment (a lane's eight k slots of a 16-deep step are two of its 16-byte vectors), same softmax.
 //
 // Roofline: f32 MFMA, 4 * tq * tk * d flop per head (split form: three times that on the f16 MFMA).
@@ -46,20 +52,36 @@ __device__ __forceinline__ float sa_partner_sum(float v) {
     return a + b;
 }
 
-// 8 f32 -> f16 hi and f16 lo = f16(x - hi), unscaled
+constexpr float kLoScale = 2048.0f, kLoUnscale = 1.0f / 2048.0f;
+
+// 8 f32 -> f16 hi and f16 lo = f16((x - hi) * 2^11), as fma(hi, -2^11, x * 2^11): the fma's value is exactly representable in
+// float32, so its single rounding is the one to f16.  Written so that hipcc packs it: one v_cvt_pk_f16_f32 and one v_pk_mul_f32
+// per two values, one v_fma_mix{lo,hi}_f16 per value (the f16 operand read in place, the result written as f16).
 __device__ __forceinline__ void sa_split8(f32x4 x0, f32x4 x1, f16x8& hi8, f16x8& lo8) {
+    typedef float f32x2v __attribute__((ext_vector_type(2)));
+    typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
+    const f32x4 s0 = x0 * kLoScale, s1 = x1 * kLoScale;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const f16 h0 = (f16)x0[j], h1 = (f16)x1[j];
-        hi8[j] = h0; hi8[4 + j] = h1;
-        lo8[j] = (f16)(x0[j] - (float)h0);
-        lo8[4 + j] = (f16)(x1[j] - (float)h1);
+    for (int j = 0; j < 4; j += 2) {
+        const f16x2v h0 = __builtin_convertvector(f32x2v{x0[j], x0[j + 1]}, f16x2v);
+        const f16x2v h1 = __builtin_convertvector(f32x2v{x1[j], x1[j + 1]}, f16x2v);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            hi8[j + i] = h0[i]; hi8[4 + j + i] = h1[i];
+            lo8[j + i] = (f16)__builtin_fmaf((float)h0[i], -kLoScale, s0[j + i]);
+            lo8[4 + j + i] = (f16)__builtin_fmaf((float)h1[i], -kLoScale, s1[j + i]);
+        }
     }
 }
-__device__ __forceinline__ f32x16 sa_mma3(f16x8 ah, f16x8 al, f16x8 bh, f16x8 bl, f32x16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, c, 0, 0, 0);          // the small terms first
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, c, 0, 0, 0);
+// one 16-deep step: the leading term into c, the two 2^-11 terms into cl
+__device__ __forceinline__ void sa_mma3(f16x8 ah, f16x8 al, f16x8 bh, f16x8 bl, f32x16& c, f32x16& cl) {
+    cl = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, cl, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, c, 0, 0, 0);
+    cl = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, cl, 0, 0, 0);
+}
+__device__ __forceinline__ void sa_fold(f32x16& c, const f32x16& cl) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) c[e] = __builtin_fmaf(cl[e], kLoUnscale, c[e]);
 }
 
 struct SAttnArgs {
@@ -92,10 +114,22 @@ __global__ __launch_bounds__(256, 2) void sattention_kernel(SAttnArgs a) {
     // The wave's Q rows live in LDS (rows padded to D + 4 floats: conflict-free 16-byte reads), not in 48 registers: one
     // ds_read_b128 per four MFMAs is nothing next to 64-cycle MFMAs, and the register file holds K, V, S and O without spills.
     // The buffer is the first wave-slice of `red`, which is not written before every wave has finished its key loop.
+    // Split form: the lane that stores vectors j and j + 1 of a 16-deep step is the lane that reads them, so it stores their
+    // halves instead -- hi of the eight values where vector j lay, lo where vector j + 1 lay.
     float (*qs)[D + 4] = red[0];
     if (wave == 0) {
+        if constexpr (SPLIT) {
 #pragma unroll
-        for (int j = 0; j < KJ; ++j) *(f32x4*)&qs[l31][8 * j + 4 * hi] = *(const f32x4*)(qp + 8 * j);
+            for (int j = 0; j < KJ; j += 2) {
+                f16x8 qh, ql;
+                sa_split8(*(const f32x4*)(qp + 8 * j), *(const f32x4*)(qp + 8 * j + 8), qh, ql);
+                *(f16x8*)&qs[l31][8 * j + 4 * hi] = qh;
+                *(f16x8*)&qs[l31][8 * j + 8 + 4 * hi] = ql;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < KJ; ++j) *(f32x4*)&qs[l31][8 * j + 4 * hi] = *(const f32x4*)(qp + 8 * j);
+        }
     }
     __syncthreads();
 
@@ -135,13 +169,17 @@ __global__ __launch_bounds__(256, 2) void sattention_kernel(SAttnArgs a) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) st[e] = 0.f;
         if constexpr (SPLIT) {
+            f32x16 sl;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) sl[e] = 0.f;
 #pragma unroll
             for (int j = 0; j < KJ; j += 2) {                     // one 16-deep step = the lane's vectors j, j + 1 on both operands
-                f16x8 kh, kl, qh, ql;
+                f16x8 kh, kl;
                 sa_split8(kf[j], kf[j + 1], kh, kl);
-                sa_split8(*(const f32x4*)&qs[l31][8 * j + 4 * hi], *(const f32x4*)&qs[l31][8 * j + 8 + 4 * hi], qh, ql);
-                st = sa_mma3(kh, kl, qh, ql, st);
+                const f16x8 qh = *(const f16x8*)&qs[l31][8 * j + 4 * hi], ql = *(const f16x8*)&qs[l31][8 * j + 8 + 4 * hi];
+                sa_mma3(kh, kl, qh, ql, st, sl);
             }
+            sa_fold(st, sl);
         } else {
 #pragma unroll
             for (int j = 0; j < KJ; ++j) {
@@ -178,18 +216,24 @@ __global__ __launch_bounds__(256, 2) void sattention_kernel(SAttnArgs a) {
             for (int e = 0; e < 16; ++e) ot[db][e] *= alpha;
         // ---------------- O^T += V^T P^T
         if constexpr (SPLIT) {
+            f16x8 ph[2], pl[2];
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {                         // keys 16 u ..: accumulator / V registers 8 u .. 8 u + 7
-                f16x8 ph, pl;
+            for (int u = 0; u < 2; ++u)                           // keys 16 u ..: accumulator / V registers 8 u .. 8 u + 7
                 sa_split8(f32x4{st[8 * u], st[8 * u + 1], st[8 * u + 2], st[8 * u + 3]},
-                          f32x4{st[8 * u + 4], st[8 * u + 5], st[8 * u + 6], st[8 * u + 7]}, ph, pl);
+                          f32x4{st[8 * u + 4], st[8 * u + 5], st[8 * u + 6], st[8 * u + 7]}, ph[u], pl[u]);
 #pragma unroll
-                for (int db = 0; db < DB; ++db) {
+            for (int db = 0; db < DB; ++db) {
+                f32x16 ol;                                        // the tile's 2^-11 terms of this channel block
+#pragma unroll
+                for (int e = 0; e < 16; ++e) ol[e] = 0.f;
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
                     f16x8 vh, vl;
                     sa_split8(f32x4{vf[db][8 * u], vf[db][8 * u + 1], vf[db][8 * u + 2], vf[db][8 * u + 3]},
                               f32x4{vf[db][8 * u + 4], vf[db][8 * u + 5], vf[db][8 * u + 6], vf[db][8 * u + 7]}, vh, vl);
-                    ot[db] = sa_mma3(vh, vl, ph, pl, ot[db]);
+                    sa_mma3(vh, vl, ph[u], pl[u], ot[db], ol);
                 }
+                sa_fold(ot[db], ol);
             }
         } else {
 #pragma unroll

@@ -429,8 +429,8 @@ int ap_vit_forward_chw(ap_vit* m, const void* x, int x_dtype, int n,
  *        impl 0 picks it only then;
  *   bias, gamma, colsum, rowstats: 16-byte aligned;  partial: 8-byte aligned (rowstats [M, 2] and partial [M, N / 64, 2] are dense).
  * Both entry points refuse anything else, and an impl that does not take the problem, with AP_ERR_INVALID and their name
- * in ap_last_error(); nothing is launched.  Whichever kernel runs, the same call gives the same bits.  (impl 129, below, has
- * its own rule: N % 32 == 0.) */
+ * in ap_last_error(); nothing is launched.  Whichever kernel runs, the same call gives the same bits.  impl 129 (below) is held
+ * to the same rule with N % 32 == 0 in place of N % 128 == 0, and gamma, where given, is applied as by impl 128. */
 #define AP_EPI_BIAS 0
 #define AP_EPI_BIAS_GELU 1
 #define AP_EPI_BIAS_RESID 2
@@ -444,7 +444,8 @@ int ap_gemm(int dtype, int epilogue, const void* A, int lda, const void* W, int 
  * number of BYTES: per 32 consecutive values 32 f16 `hi` followed by 32 f16 `lo`, hi = f16(w), lo = f16((w - hi) * 2^11).
  * ap_gemm(AP_F32, ..., impl = 129) then takes such rows as W (ldw still in f32 elements), float32 A / bias / out, and
  * computes  sum_k  w_hi a_hi + 2^-11 (w_hi a_lo + w_lo a_hi)  with a split in registers, f32 accumulation: ~2^-22 per
- * product against the exact f32 chain of impl 128, at 2-3x its rate.  K % 32 == 0, N % 128 == 0. */
+ * product against the exact f32 chain of impl 128, at 2-3x its rate.  K % 32 == 0, N % 32 == 0 (the 128-wide tile's tail is
+ * masked); otherwise the layout rule above, refused the same way.  |x| < 65504 for every operand value (hi = f16(x)). */
 int ap_split_f16_weights(const float* w32, void* out, size_t count, ap_stream_t stream);
 /* The same product as a row-wise float32 layer with an optional SEPARATE residual (the SAM2 trunk's Linear / MLP layers,
  * services/segmentation.py:120-180 runs them in float32):
@@ -899,8 +900,10 @@ int ap_softmax_rows(float* x, long ld, int rows, int cols, ap_stream_t stream); 
 int ap_sattention_f32(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, int batch, int heads,
                       int tq, int tk, int d, float scale, float* out, long ldo, ap_stream_t stream);
 /* The same operator (same arguments, float32 in and out) with both products as split-f16 MFMA passes:
- * a b ~= a_hi b_hi + a_hi b_lo + a_lo b_hi on v_mfma_f32_32x32x16_f16 with f32 accumulation, hi = f16(x), lo = f16(x - hi)
- * (float32-accurate: ~2^-22 per product; the softmax stays float32).  2-3x the rate of the exact chain on the image-wide blocks. */
+ * a b ~= a_hi b_hi + 2^-11 (a_hi b_lo + a_lo b_hi) on v_mfma_f32_32x32x16_f16 with f32 accumulation, hi = f16(x),
+ * lo = f16((x - hi) * 2^11): the split of ap_split_f16_weights, x = hi + lo 2^-11 to 2^-21 |x| + 2^-36, so float32-accurate
+ * (~2^-22 per product) for values of every size inside f16's range, |x| < 65504; the softmax stays float32.  Held per element
+ * to the bound of the exact chain (tests/test_gpu_split_f16.py).  2x the rate of the exact chain on the image-wide blocks. */
 int ap_sattention_split_f16(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, int batch, int heads,
                             int tq, int tk, int d, float scale, float* out, long ldo, ap_stream_t stream);
 /* uint8 [h, w, 3] -> rows [(h/4)*(w/4), 147] of ((x/255) - mean) / std in (c, ky, kx) order: the im2col of

@@ -17,7 +17,7 @@ The check, per element (tests/vit_ops_reference.py: ``failures``, ``U``, ``FLOOR
 A is the float64 sum of the absolute values of the terms behind the element.  With
     terms = sum_k |a w| + |bias|                                    (ap_gemm)
     terms = |rstd| sum_k |x w'| + |nmr colsum| + |bias|             (the NORM forms; C = the pre-activation)
-  AP_EPI_BIAS / AP_EPI_NORM     A = terms
+  AP_EPI_BIAS / AP_EPI_NORM     A = terms                          (AP_EPI_BIAS with gamma: out = gamma C, A = |gamma| terms)
   AP_EPI_BIAS_RESID             A = |gamma| terms + |out0|
   tanh GELU                     A = 1.13 terms + |g| (1 + |z| sigmoid(-z)),  z = 2 sqrt(2 / pi) (C + 0.044715 C^3): as
                                 tests/siglip_reference.py derives it
@@ -158,10 +158,12 @@ def _sigmoid(x):
     return 1.0 / (1.0 + torch.exp(-x))
 
 
-def ref_gemm(a, fd=torch.float64, mutate=None):
+def ref_gemm(a, fd=torch.float64, mutate=None, product=None):
+    """product: (acc, sum of |a w|) in fd computed by the caller instead of _product (tests/split_f16_reference.py: the emulated
+    split-f16 products go through the same epilogues)."""
     epi, dt, M, N = a["epi"], a["dtype"], a["M"], a["N"]
     variant = mutate if mutate in ("a_stride_k", "w_stride_k", "last_ktile_dropped", "first_ktile_twice") else None
-    acc, absacc = _product(a, fd, variant)
+    acc, absacc = product if product is not None else _product(a, fd, variant)
     if absacc is None:
         absacc = torch.zeros(M, N, dtype=torch.float64)            # a mutated evaluation: A is not used
     bias = a["bias"]
@@ -183,6 +185,10 @@ def ref_gemm(a, fd=torch.float64, mutate=None):
         terms = absacc + bias.abs().double()
         act = epi
     C64 = C.double()
+    if act == "bias" and a["gamma"] is not None:            # ap_gemm applies gamma under AP_EPI_BIAS as well (LayerScale without a residual)
+        if mutate == "gamma_ignored":
+            return {"out": GOut(C, dt, terms)}
+        return {"out": GOut(C * a["gamma"].to(fd), dt, terms * a["gamma"].abs().double())}
     if act in ("bias", "", "norm"):
         return {"out": GOut(C, dt, terms)}
     if act == "gelu":

@@ -417,6 +417,32 @@ def test_attention_entry_points_refuse_on_the_host_before_any_launch():
             assert call(dtype, p, o, 0, 4, 1, 64) == 0
 
 
+def test_gemm_impl_129_is_held_to_the_layout_contract_on_the_host_before_any_launch():
+    """ap_gemm with impl = 129 (split-f16 products) goes through the layout rule of impl 128 with N % 32 == 0 in place of
+    N % 128 == 0: every call the rule excludes returns AP_ERR_INVALID with "ap_gemm:" and the broken clause in ap_last_error(),
+    decided on the host (no GPU here: a launch would have come back as AP_ERR_HIP).  N = 96 itself is not refused: with one more
+    fault the message names that fault, not N.  The pointers are made up: nothing reads them."""
+    from atlaspatch_amd import _lib
+    lib = _lib.load()
+    a, b, c, d, e = (0x10000 * (i + 1) for i in range(5))
+    keys = ("dtype", "epi", "A", "lda", "W", "ldw", "M", "N", "K", "bias", "gamma", "out", "ldo", "impl", "variant", "stream")
+    base = dict(dtype=0, epi=0, A=a, lda=64, W=b, ldw=64, M=128, N=96, K=64, bias=c, gamma=None, out=d, ldo=96, impl=129, variant=0, stream=None)
+    cases = (("ldo < N", dict(ldo=64), "row strides"), ("ldo % 4", dict(ldo=98), "ldo % 4"), ("lda < K", dict(lda=32), "row strides"),
+             ("ldw < K", dict(ldw=32), "row strides"), ("lda off 16 bytes", dict(lda=66), "16-byte"), ("ldw off 16 bytes", dict(ldw=70), "16-byte"),
+             ("A off 16 bytes", dict(A=a + 4), "16-byte"), ("W off 16 bytes", dict(W=b + 8), "16-byte"), ("out off 16 bytes", dict(out=d + 4), "four elements"),
+             ("out off 16 bytes under resid", dict(epi=2, out=d + 8), "four elements"), ("bias off 16 bytes", dict(bias=c + 4), "bias / gamma"),
+             ("gamma off 16 bytes", dict(gamma=e + 4), "bias / gamma"), ("gamma off 16 bytes under resid", dict(epi=2, gamma=e + 8), "bias / gamma"),
+             ("N % 32", dict(N=80, ldo=80), "multiple of 32"), ("N % 32, a whole tile and a bit", dict(N=144, ldo=144), "multiple of 32"),
+             ("K % 32", dict(K=48), "K = 48 of 32"), ("M = 0", dict(M=0), "empty"), ("N = 0", dict(N=0), "empty"),
+             ("f16 buffers", dict(dtype=1), "float32"), ("bf16 buffers", dict(dtype=2), "float32"))
+    for what, kw, clause in cases:
+        rc = lib.ap_gemm(*[{**base, **kw}[k] for k in keys])
+        msg = lib.ap_last_error().decode()
+        assert rc == _lib.AP_ERR_INVALID and "ap_gemm:" in msg and clause in msg, (what, rc, msg)
+    # impl 128 keeps N % 128 == 0
+    assert lib.ap_gemm(*[{**base, "impl": 128}[k] for k in keys]) == _lib.AP_ERR_INVALID and b"multiple of 128" in lib.ap_last_error()
+
+
 def test_dtype_dispatch_refuses_unknown_dtypes_on_the_host_before_any_launch():
     """Every exported entry point whose launcher picks its kernel through dispatch_dtype / dispatch_half (kernel_util.h): dtype 3
     and -1 with otherwise valid arguments return AP_ERR_INVALID and ap_last_error() names the entry point (the wrapper's name, or the
