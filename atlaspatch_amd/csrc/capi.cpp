@@ -181,7 +181,8 @@ static int gemm_contract(const char* fn, int dtype, int epilogue, const ap::Gemm
     AP_REQUIRE(aligned16(g.bias, g.gamma, g.colsum, g.rowstats) && aligned8(g.partial),
                "%s: bias / gamma / colsum / rowstats need 16-byte aligned pointers, partial an 8-byte aligned one", fn);
     AP_REQUIRE((impl != 256 && impl != 257) || ap::gemm256_supports(dtype, epilogue, g),
-               "%s: impl %d (the 256 x 256 kernel) takes f16 / bf16, N %% 256 == 0, K %% 128 == 0, K >= 128, 16-byte aligned output rows", fn, impl);
+               "%s: impl %d (the 256 x 256 kernel) takes f16 / bf16, N %% 256 == 0, K %% 128 == 0, K >= 128, 16-byte aligned output rows, 255 rows of A / W below 4 GiB, "
+               "M <= 2^29 under the NORM epilogues", fn, impl);
     return AP_OK;
 }
 

@@ -826,6 +826,8 @@ bool AP_G256_FN(gemm256_supports)(int dtype, int epilogue, const GemmArgs& a) {
     if (a.N % kBN != 0 || a.K % 128 != 0 || a.K < 128) return false;
     if (((size_t)a.lda * 2) % 16 != 0 || ((size_t)a.ldw * 2) % 16 != 0) return false;
     if ((size_t)255 * a.lda * 2 + 128 > 0xffffffffull || (size_t)255 * a.ldw * 2 + 128 > 0xffffffffull) return false;
+    // the NORM epilogues stage rowstats / bias / colsum by 32-bit byte offsets from their bases (stage_ops: row * 8, column * 4)
+    if (epi_is_norm(epilogue) && (a.M > (1 << 29) || a.N > (1 << 30))) return false;
     // 16-byte row stores: output row stride and base must keep 16-byte alignment
     const size_t oes = epilogue == EPI_BIAS_RESID ? 4 : 2;
     if (((size_t)a.ldo * oes) % 16 != 0 || ((uintptr_t)a.out & 15) != 0) return false;

@@ -427,6 +427,10 @@ int ap_vit_forward_chw(ap_vit* m, const void* x, int x_dtype, int n,
  *   out: ldo % 4 == 0 and the pointer aligned to 4 * sizeof(To) (a lane stores four consecutive columns); the 256 x 256
  *        kernel stores 16 bytes per lane: impl 256 needs ldo * sizeof(To) % 16 == 0 and a 16-byte aligned pointer, and
  *        impl 0 picks it only then;
+ *   sizes: the buffers may be of any size -- every row is addressed with 64 bits (row index x stride), so rows beyond element
+ *        2^31 and byte 2^32 of A and out are as good as the first.  The 256 x 256 kernel keeps 32-bit BYTE offsets inside one
+ *        tile and into rowstats: impl 256 needs 255 * lda * sizeof(T) + 128 and 255 * ldw * sizeof(T) + 128 below 2^32, and under
+ *        the AP_EPI_NORM* epilogues M <= 2^29 (rowstats below 4 GiB) and N <= 2^30; impl 0 picks it only then;
  *   bias, gamma, colsum, rowstats: 16-byte aligned;  partial: 8-byte aligned (rowstats [M, 2] and partial [M, N / 64, 2] are dense).
  * Both entry points refuse anything else, and an impl that does not take the problem, with AP_ERR_INVALID and their name
  * in ap_last_error(); nothing is launched.  Whichever kernel runs, the same call gives the same bits.  impl 129 (below) is held
