@@ -202,6 +202,55 @@ class SynthWSI(IWSI):
         _lib.check(code, "ap_host_decode_jpeg_tiles")
         return True
 
+    def jpeg_coefficient_sampling(self, rows, tile_side: int) -> Optional[int]:
+        """Optional IWSI capability beside ``read_tiles_into``, switched on by ATLASPATCH_JPEG_DEVICE=1: the sampling
+        (``AP_JPEG_*``) of this slide's JPEG tile store when its tiles can cross the ring as entropy-decoded coefficients
+        (``read_coefficients_into``), else None.  Found by ``ap_host_jpeg_probe`` on the first of ``rows`` that the store
+        holds as a baseline ``tile_side``-square tile; tiles of another kind take the host route chunk by chunk."""
+        import ctypes as C
+        from ... import _lib
+        from ...utils.env import env_flag
+        self._ensure_loaded()
+        if self.jpeg_dir is None or not env_flag("ATLASPATCH_JPEG_DEVICE"):
+            return None
+        lib = _lib.load()
+        w, h, s = C.c_int(), C.c_int(), C.c_int()
+        for x, y, rw, rh, lv in rows:
+            path = os.path.join(self.jpeg_dir, f"{int(x)}_{int(y)}_{int(rw)}.jpg")
+            if int(lv) != 0 or int(rw) != tile_side or int(rh) != tile_side or not os.path.exists(path):
+                continue
+            code = lib.ap_host_jpeg_probe(path.encode(), C.byref(w), C.byref(h), C.byref(s))
+            if code == _lib.AP_ERR_UNSUPPORTED:            # no usable libjpeg on this host
+                return None
+            if code == _lib.AP_OK and w.value == tile_side and h.value == tile_side:
+                return int(s.value)
+        return None
+
+    def read_coefficients_into(self, rows, dst_ptr: int, tile_side: int, sampling: int) -> bool:
+        """Entropy-decode the JPEG tiles of ``rows`` into consecutive ``ap_jpeg_slot_bytes(tile_side, sampling)``-byte slots
+        at ``dst_ptr`` in ONE call outside the interpreter lock (``ap_host_jpeg_coefficients``), or return False: a tile the
+        store lacks, a progressive or damaged tile, another sampling or size, or no libjpeg.  The caller then reads that
+        chunk as pixels (``read_tiles_into``, then tile by tile), which decodes, renders or raises as it always did."""
+        import ctypes as C
+        from ... import _lib
+        self._ensure_loaded()
+        if self.jpeg_dir is None or not rows or getattr(self, "_jpeg_coefficients", True) is False:
+            return False
+        if any(int(r[2]) != tile_side or int(r[3]) != tile_side or int(r[4]) != 0 for r in rows):
+            return False
+        files = [os.path.join(self.jpeg_dir, f"{int(x)}_{int(y)}_{int(rw)}.jpg") for x, y, rw, rh, lv in rows]
+        if not all(os.path.exists(f) for f in files):
+            return False
+        arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
+        code = _lib.load().ap_host_jpeg_coefficients(dst_ptr, arr, len(files), tile_side, int(sampling))
+        if code == _lib.AP_ERR_UNSUPPORTED:
+            self._jpeg_coefficients = False
+            return False
+        if code == _lib.AP_ERR_INVALID:
+            return False
+        _lib.check(code, "ap_host_jpeg_coefficients")
+        return True
+
     def get_size(self, lv: int = 0) -> Tuple[int, int]:
         self._ensure_loaded()
         return self.dims[lv]

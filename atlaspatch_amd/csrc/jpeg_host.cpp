@@ -19,6 +19,7 @@
 #include <mutex>
 #include <vector>
 #include "ap_common.h"
+#include "jpeg_slot.h"
 
 namespace {
 
@@ -109,8 +110,42 @@ struct jpeg_decompress_struct {
     void *master, *main_, *coef, *post, *inputctl, *marker, *entropy, *idct, *upsample, *cconvert, *cquantize;
 };
 
+// what the coefficient reader (ap_host_jpeg_coefficients) needs beyond the pixel decoder's subset
+typedef short JCOEF;
+typedef JCOEF JBLOCK[64];
+typedef JBLOCK* JBLOCKROW;
+typedef JBLOCKROW* JBLOCKARRAY;
+typedef void* jvirt_barray_ptr;
+
+struct JQUANT_TBL {
+    unsigned short quantval[64];         // natural order (not the zigzag order of the DQT marker)
+    boolean_t sent_table;
+};
+
+struct jpeg_component_info {             // >= v7 layout (DCT_h_scaled_size / DCT_v_scaled_size)
+    int component_id, component_index, h_samp_factor, v_samp_factor, quant_tbl_no, dc_tbl_no, ac_tbl_no;
+    JDIMENSION width_in_blocks, height_in_blocks;
+    int DCT_h_scaled_size, DCT_v_scaled_size;
+    JDIMENSION downsampled_width, downsampled_height;
+    boolean_t component_needed;
+    int MCU_width, MCU_height, MCU_blocks, MCU_sample_width, last_col_width, last_row_height;
+    JQUANT_TBL* quant_table;
+    void* dct_table;
+};
+
+struct jpeg_memory_mgr {                 // only access_virt_barray (the 9th method) is called
+    void* alloc_small; void* alloc_large; void* alloc_sarray; void* alloc_barray;
+    void* request_virt_sarray; void* request_virt_barray; void* realize_virt_arrays; void* access_virt_sarray;
+    JBLOCKARRAY (*access_virt_barray)(void* cinfo, jvirt_barray_ptr ptr, JDIMENSION start_row, JDIMENSION num_rows,
+                                      boolean_t writable);
+    void* free_pool; void* self_destruct;
+    long max_memory_to_use, max_alloc_chunk;
+};
+
 constexpr int kJpegLibVersion = 80;
+constexpr int JCS_GRAYSCALE = 1;
 constexpr int JCS_RGB = 2;
+constexpr int JCS_YCbCr = 3;
 constexpr int JPEG_HEADER_OK = 1;
 
 struct Api {
@@ -122,6 +157,7 @@ struct Api {
     JDIMENSION (*read_scanlines)(jpeg_decompress_struct*, JSAMPARRAY, JDIMENSION);
     boolean_t (*finish)(jpeg_decompress_struct*);
     void (*destroy)(jpeg_decompress_struct*);
+    jvirt_barray_ptr* (*read_coefficients)(jpeg_decompress_struct*);
     bool ok = false;
     char why[200] = "";
 };
@@ -194,6 +230,81 @@ int decode_one(const Api& api, const unsigned char* data, size_t size, int want_
     return 0;
 }
 
+// The entropy-decoded half of a decode: header checks, then (slot != nullptr) libjpeg's Huffman decoder behind
+// jpeg_read_coefficients and a copy of every component's quantisation table and blocks into `slot` (jpeg_slot.h).  Fills
+// wh / sampling from the header; slot == nullptr stops there (ap_host_jpeg_probe).  A stream outside the device decoder's
+// subset -- baseline Huffman, 8 bit, grey or YCbCr at 4:4:4 / 4:2:2 / 4:2:0 -- or one libjpeg warned about is refused with its
+// reason in `why` and nothing written to the slot.
+int read_one(const Api& api, const unsigned char* data, size_t size, int wh[2], int* sampling, int want_side, int want_sampling,
+             unsigned char* slot, char* why, size_t why_cap) {
+    jpeg_decompress_struct c;
+    ErrJmp err;
+    memset(&c, 0, sizeof(c));
+    c.err = api.std_error(&err.pub);
+    err.pub.error_exit = on_error;
+    err.pub.emit_message = on_message;
+    err.text[0] = 0;
+    volatile bool created = false;
+    if (setjmp(err.jb)) {
+        snprintf(why, why_cap, "libjpeg: %s", err.text);
+        if (created) api.destroy(&c);
+        return -1;
+    }
+    api.create(&c, kJpegLibVersion, sizeof(jpeg_decompress_struct));
+    created = true;
+    api.mem_src(&c, data, (unsigned long)size);
+#define refuse(...) (snprintf(why, why_cap, __VA_ARGS__), api.destroy(&c), -1)
+    if (api.read_header(&c, 1) != JPEG_HEADER_OK) return refuse("not a JPEG stream");
+    if (c.progressive_mode) return refuse("progressive stream");
+    if (c.arith_code) return refuse("arithmetic-coded stream");
+    if (c.data_precision != 8) return refuse("%d-bit samples", c.data_precision);
+    const jpeg_component_info* comp = (const jpeg_component_info*)c.comp_info;
+    const bool grey = c.num_components == 1 && c.jpeg_color_space == JCS_GRAYSCALE;
+    if (!comp || !(grey || (c.num_components == 3 && c.jpeg_color_space == JCS_YCbCr)))
+        return refuse("%d components in colour space %d: neither greyscale nor YCbCr", c.num_components, c.jpeg_color_space);
+    int found = -1;
+    if (grey) {
+        if (comp[0].h_samp_factor == 1 && comp[0].v_samp_factor == 1) found = AP_JPEG_GRAY;
+    } else if (comp[1].h_samp_factor == 1 && comp[1].v_samp_factor == 1 && comp[2].h_samp_factor == 1 && comp[2].v_samp_factor == 1) {
+        const int h = comp[0].h_samp_factor, v = comp[0].v_samp_factor;
+        found = h == 1 && v == 1 ? AP_JPEG_444 : h == 2 && v == 1 ? AP_JPEG_422 : h == 2 && v == 2 ? AP_JPEG_420 : -1;
+    }
+    if (found < 0)
+        return refuse("sampling factors %dx%d%s are none of 4:4:4, 4:2:2 (2x1), 4:2:0 (2x2), greyscale", comp[0].h_samp_factor,
+                      comp[0].v_samp_factor, grey ? "" : " (or subsampled luma / oversampled chroma)");
+    wh[0] = (int)c.image_width;
+    wh[1] = (int)c.image_height;
+    *sampling = found;
+    if (!slot) { api.destroy(&c); return 0; }
+    if (found != want_sampling) return refuse("sampling %d, expected %d", found, want_sampling);
+    if (wh[0] != want_side || wh[1] != want_side) return refuse("tile is %d x %d, expected %d x %d", wh[0], wh[1], want_side, want_side);
+    ap::JpegGeom g;
+    if (!ap::jpeg_geom(want_side, want_sampling, &g)) return refuse("bad side %d", want_side);
+    jvirt_barray_ptr* arrays = api.read_coefficients(&c);
+    if (!arrays) return refuse("jpeg_read_coefficients suspended");
+    // jpeg_read_coefficients has consumed the stream up to its EOI marker, so every warning is in by now.  No
+    // jpeg_finish_decompress before the copy: it releases the image pool, which holds comp_info and the coefficient arrays.
+    if (err.pub.num_warnings > 0)
+        return refuse("libjpeg reported %ld warning(s): truncated or corrupt JPEG stream", err.pub.num_warnings);
+    const jpeg_memory_mgr* mem = (const jpeg_memory_mgr*)c.mem;
+    for (int ci = 0; ci < g.ncomp; ++ci)
+        if ((int)comp[ci].width_in_blocks != g.wb[ci] || (int)comp[ci].height_in_blocks != g.hb[ci] || !comp[ci].quant_table)
+            return refuse("component %d: %u x %u blocks (expected %d x %d) or no quantisation table", ci, comp[ci].width_in_blocks,
+                          comp[ci].height_in_blocks, g.wb[ci], g.hb[ci]);
+    memset(slot, 0, ap::kJpegSlotHeader);
+    for (int ci = 0; ci < g.ncomp; ++ci) {
+        memcpy(slot + (size_t)ci * 128, comp[ci].quant_table->quantval, 128);
+        const size_t row_bytes = (size_t)g.wb[ci] * sizeof(JBLOCK);
+        for (int r = 0; r < g.hb[ci]; ++r) {
+            JBLOCKARRAY rows = mem->access_virt_barray(&c, arrays[ci], (JDIMENSION)r, 1, 0);
+            memcpy(slot + g.off[ci] + (size_t)r * row_bytes, rows[0], row_bytes);
+        }
+    }
+    api.destroy(&c);
+    return 0;
+#undef refuse
+}
+
 // 8 x 8 grey JFIF (all pixels 128): the load-time self-check of the restated declarations
 const unsigned char kProbe[] = {
     0xFF,0xD8,0xFF,0xE0,0x00,0x10,0x4A,0x46,0x49,0x46,0x00,0x01,0x01,0x00,0x00,0x01,0x00,0x01,0x00,0x00,
@@ -219,7 +330,9 @@ void load_api() {
     a.read_scanlines = (decltype(a.read_scanlines))sym("jpeg_read_scanlines");
     a.finish = (decltype(a.finish))sym("jpeg_finish_decompress");
     a.destroy = (decltype(a.destroy))sym("jpeg_destroy_decompress");
-    if (!a.std_error || !a.create || !a.mem_src || !a.read_header || !a.start || !a.read_scanlines || !a.finish || !a.destroy) {
+    a.read_coefficients = (decltype(a.read_coefficients))sym("jpeg_read_coefficients");
+    if (!a.std_error || !a.create || !a.mem_src || !a.read_header || !a.start || !a.read_scanlines || !a.finish || !a.destroy ||
+        !a.read_coefficients) {
         snprintf(a.why, sizeof(a.why), "libjpeg.so.8 lacks a required symbol");
         return;
     }
@@ -232,7 +345,38 @@ void load_api() {
     }
     for (unsigned char v : px)
         if (v != 128) { snprintf(a.why, sizeof(a.why), "libjpeg.so.8 self-check decoded %d, expected 128", (int)v); return; }
+    // the coefficient reader's declarations (component info, memory manager, quantisation table): the same probe is one
+    // block with DC 0 under an all-ones table; poison first so that a reader that delivers nothing is caught too
+    ap::JpegGeom g;
+    ap::jpeg_geom(8, AP_JPEG_GRAY, &g);
+    unsigned char slot[ap::kJpegSlotHeader + 128];
+    memset(slot, 0x5A, sizeof(slot));
+    int wh[2], sampling = -1;
+    if (g.bytes != sizeof(slot) || read_one(a, kProbe, sizeof(kProbe), wh, &sampling, 8, AP_JPEG_GRAY, slot, why, sizeof(why)) != 0) {
+        snprintf(a.why, sizeof(a.why), "libjpeg.so.8 coefficient self-check failed: %s", why);
+        return;
+    }
+    const unsigned short* q = (const unsigned short*)slot;
+    const short* blk = (const short*)(slot + ap::kJpegSlotHeader);
+    bool good = wh[0] == 8 && wh[1] == 8 && sampling == AP_JPEG_GRAY;
+    for (int k = 0; k < 64; ++k) good = good && q[k] == 1 && blk[k] == 0;
+    if (!good) { snprintf(a.why, sizeof(a.why), "libjpeg.so.8 coefficient self-check read other values than the probe holds"); return; }
     a.ok = true;
+}
+
+// whole file -> buf; the message names the file
+int read_file(const char* what, const char* path, std::vector<unsigned char>& buf) {
+    FILE* f = fopen(path, "rb");
+    AP_REQUIRE(f, "%s: cannot open %s", what, path);
+    fseek(f, 0, SEEK_END);
+    const long size = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    buf.resize(size > 0 ? (size_t)size : 1);
+    const size_t got = size > 0 ? fread(buf.data(), 1, (size_t)size, f) : 0;
+    fclose(f);
+    AP_REQUIRE(size > 0 && got == (size_t)size, "%s: short read of %s", what, path);
+    buf.resize((size_t)size);
+    return AP_OK;
 }
 
 }  // namespace
@@ -261,6 +405,56 @@ extern "C" int ap_host_decode_jpeg_tiles(void* dst, const char* const* paths, in
         if (decode_one(g_api, buf.data(), (size_t)size, side, side, (unsigned char*)dst + (size_t)i * tile_bytes,
                        (size_t)side * 3, why, sizeof(why)) != 0) {
             ap::set_error("ap_host_decode_jpeg_tiles: %s: %s", paths[i], why);
+            return AP_ERR_INVALID;
+        }
+    }
+    return AP_OK;
+}
+
+extern "C" size_t ap_jpeg_slot_bytes(int side, int sampling) {
+    ap::JpegGeom g;
+    return ap::jpeg_geom(side, sampling, &g) ? g.bytes : 0;
+}
+
+extern "C" int ap_host_jpeg_probe(const char* path, int* width, int* height, int* sampling) {
+    AP_REQUIRE(path && width && height && sampling, "ap_host_jpeg_probe: null pointer");
+    std::call_once(g_once, load_api);
+    if (!g_api.ok) {
+        ap::set_error("ap_host_jpeg_probe: %s", g_api.why);
+        return AP_ERR_UNSUPPORTED;
+    }
+    std::vector<unsigned char> buf;
+    if (int rc = read_file("ap_host_jpeg_probe", path, buf)) return rc;
+    char why[200] = "";
+    int wh[2] = {0, 0}, found = -1;
+    if (read_one(g_api, buf.data(), buf.size(), wh, &found, 0, 0, nullptr, why, sizeof(why)) != 0) {
+        ap::set_error("ap_host_jpeg_probe: %s: %s", path, why);
+        return AP_ERR_INVALID;
+    }
+    *width = wh[0];
+    *height = wh[1];
+    *sampling = found;
+    return AP_OK;
+}
+
+extern "C" int ap_host_jpeg_coefficients(void* slots, const char* const* paths, int n, int side, int sampling) {
+    AP_REQUIRE(slots && (paths || n == 0) && n >= 0, "ap_host_jpeg_coefficients: bad arguments");
+    const size_t stride = ap_jpeg_slot_bytes(side, sampling);
+    AP_REQUIRE(stride, "ap_host_jpeg_coefficients: bad side %d or sampling %d", side, sampling);
+    std::call_once(g_once, load_api);
+    if (!g_api.ok) {
+        ap::set_error("ap_host_jpeg_coefficients: %s", g_api.why);
+        return AP_ERR_UNSUPPORTED;
+    }
+    std::vector<unsigned char> buf;
+    for (int i = 0; i < n; ++i) {
+        AP_REQUIRE(paths[i], "ap_host_jpeg_coefficients: null path %d", i);
+        if (int rc = read_file("ap_host_jpeg_coefficients", paths[i], buf)) return rc;
+        char why[200] = "";
+        int wh[2], found;
+        if (read_one(g_api, buf.data(), buf.size(), wh, &found, side, sampling, (unsigned char*)slots + (size_t)i * stride, why,
+                     sizeof(why)) != 0) {
+            ap::set_error("ap_host_jpeg_coefficients: %s: %s", paths[i], why);
             return AP_ERR_INVALID;
         }
     }

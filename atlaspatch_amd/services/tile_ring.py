@@ -93,6 +93,14 @@ def _pin_order(device, *, sysfs: str = "/sys", allowed=None, bdf: str | None = N
     return order
 
 
+# Tiles of JPEG-store slides that crossed the ring since import: "device" = shipped as entropy-decoded coefficients and decoded
+# by ap_jpeg_decode_tiles, "host" = decoded on the host although the device path was on (a chunk the coefficient reader refused).
+# Written by the thread that drives the ring only.
+JPEG_TILES = {"device": 0, "host": 0}
+# ap_jpeg_decode_tiles holds a band of a tile in one workgroup's LDS: the widest tile it takes at every sampling
+_JPEG_DEVICE_MAX_SIDE = 976
+
+
 class TileRing:
     def __init__(self, *, device: torch.device, batch: int, patch_size: int, slots: int = 3,
                  workers: int = 4, tile_hw: tuple | None = None) -> None:
@@ -109,6 +117,7 @@ class TileRing:
         self.dev = [torch.empty((self.batch, self.th, self.tw, 3), dtype=torch.uint8, device=device)
                     for _ in range(self.slots)]
         self._out_host = None
+        self._coef = None                # ((sampling, slot bytes), pinned slots, device slots): allocated on first use
         self.copy_stream = torch.cuda.Stream(device=device)
         self.free_events: list[torch.cuda.Event | None] = [None] * self.slots
         self.workers = max(1, int(workers))
@@ -133,13 +142,34 @@ class TileRing:
 
         self.pool = futures.ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="tile", initializer=_pin_worker)
 
+    def _coefficient_slots(self, sampling: int):
+        """Pinned and device JPEG coefficient slots of the ring's depth for square tiles at ``sampling``, or None when
+        ap_jpeg_decode_tiles cannot take this ring's tiles (not square, too wide, or tile starts that are not 16-byte aligned)."""
+        if self.th != self.tw or self.tw > _JPEG_DEVICE_MAX_SIDE or (self.th * self.tw * 3) % 16:
+            return None
+        nbytes = int(self._lib.ap_jpeg_slot_bytes(self.tw, int(sampling)))
+        if nbytes == 0:
+            return None
+        if self._coef is None or self._coef[0] != (int(sampling), nbytes):
+            self._coef = None
+            host = [torch.empty((self.batch, nbytes), dtype=torch.uint8, pin_memory=True) for _ in range(self.slots)]
+            dev = [torch.empty((self.batch, nbytes), dtype=torch.uint8, device=self.device) for _ in range(self.slots)]
+            self._coef = ((int(sampling), nbytes), host, dev)
+        return self._coef
+
     def run(self, coords: np.ndarray, read_tile: Callable[[int, int, int, int, int], np.ndarray],
             forward: Callable[[torch.Tensor, torch.Tensor], None], out_dim: int, *,
-            read_chunk: Callable | None = None, out_host: torch.Tensor | None = None) -> np.ndarray:
+            read_chunk: Callable | None = None, out_host: torch.Tensor | None = None,
+            read_coefficients: Callable | None = None, coef_sampling: int | None = None) -> np.ndarray:
         """coords int32 [N, 5]; ``read_tile(x, y, rw, rh, lv)`` -> uint8 [th, tw, 3];
         ``forward(tiles_dev [n,th,tw,3], out_dev [n,D])`` enqueues on the current stream.
         ``read_chunk(rows, dst_ptr, tile_side) -> bool`` (optional): a backend's native batched decoder; when it
-        returns True the chunk's tiles are already in the pinned slot.  Returns float32 [N, D] (host; a fresh array --
+        returns True the chunk's tiles are already in the pinned slot.
+        ``read_coefficients(rows, dst_ptr, tile_side, sampling) -> bool`` with ``coef_sampling`` (optional): a JPEG backend's
+        entropy decoder; when it returns True the chunk's coefficient slots are in the pinned COEFFICIENT slot, cross PCIe
+        in that form and are decoded into the device tile slot by ``ap_jpeg_decode_tiles`` on the compute stream.  A chunk
+        it refuses takes the route above (``read_chunk``, then ``read_tile``) and crosses as RGB.
+        Returns float32 [N, D] (host; a fresh array --
         or, when the caller passes its own pinned ``out_host`` [>= N, D], a view of that buffer: no extra copy)."""
         n_total = int(coords.shape[0])
         if n_total == 0:
@@ -163,10 +193,14 @@ class TileRing:
             bounds.append((lo, hi))
             lo, size = hi, min(self.batch, size * 2)
         nb = len(bounds)
+        coef = self._coefficient_slots(coef_sampling) if read_coefficients is not None and coef_sampling is not None else None
+        if coef is not None:
+            (sampling, coef_bytes), coef_host, coef_dev = coef
 
         def fill(slot: int, b: int):
             lo, hi = bounds[b]
             base = self.host[slot].data_ptr()
+            cbase = coef_host[slot].data_ptr() if coef is not None else 0
             count = hi - lo
             chunk = max(1, -(-count // (4 * self.workers)))          # a few tasks per worker, not one per tile
             rows = coords[lo:hi].tolist()
@@ -177,6 +211,8 @@ class TileRing:
                 # decode the chunk, then ONE ap_host_gather_tiles call copies it into the pinned slot with the
                 # interpreter lock released (a NumPy slice assignment per tile would hold it for every 196 KB memcpy)
                 stop = min(count, start + chunk)
+                if coef is not None and read_coefficients(rows[start:stop], cbase + start * coef_bytes, self.tw, sampling):
+                    return True
                 if read_chunk is not None and self.th == self.tw and \
                         read_chunk(rows[start:stop], base + start * tile_bytes, self.tw):
                     return
@@ -191,7 +227,7 @@ class TileRing:
                 _lib.check(self._lib.ap_host_gather_tiles(base + start * tile_bytes, ptrs, len(tiles), tile_bytes),
                            "ap_host_gather_tiles")
 
-            return [self.pool.submit(some, s) for s in range(0, count, chunk)], count
+            return [self.pool.submit(some, s) for s in range(0, count, chunk)], count, chunk
 
         pending = {}
         try:
@@ -202,17 +238,34 @@ class TileRing:
                 pending[b] = fill(b % self.slots, b)
             for b in range(nb):
                 slot = b % self.slots
-                tasks, count = pending[b]
-                for t in tasks:
-                    t.result()
+                tasks, count, chunk = pending[b]
+                runs = []                                            # [first tile, end, crossed as coefficients] maximal runs
+                for i, t in enumerate(tasks):
+                    as_coef = bool(t.result())
+                    start, stop = i * chunk, min(count, (i + 1) * chunk)
+                    if runs and runs[-1][2] == as_coef:
+                        runs[-1][1] = stop
+                    else:
+                        runs.append([start, stop, as_coef])
                 del pending[b]
                 with torch.cuda.stream(self.copy_stream):
-                    if self.free_events[slot] is not None:           # device slot: the forward that read it is done
+                    if self.free_events[slot] is not None:           # device slots: the forward (and decode) that read them is done
                         self.copy_stream.wait_event(self.free_events[slot])
-                    self.dev[slot][:count].copy_(self.host[slot][:count], non_blocking=True)
+                    for start, stop, as_coef in runs:
+                        if as_coef:
+                            coef_dev[slot][start:stop].copy_(coef_host[slot][start:stop], non_blocking=True)
+                        else:
+                            self.dev[slot][start:stop].copy_(self.host[slot][start:stop], non_blocking=True)
                     copied = torch.cuda.Event()
                     copied.record(self.copy_stream)
                 compute.wait_event(copied)
+                for start, stop, as_coef in runs:
+                    if as_coef:                                      # coefficients -> RGB rows of the device tile slot
+                        _lib.check(self._lib.ap_jpeg_decode_tiles(coef_dev[slot][start:stop].data_ptr(), stop - start, self.tw,
+                                                                  sampling, self.dev[slot][start:stop].data_ptr(),
+                                                                  int(compute.cuda_stream)), "ap_jpeg_decode_tiles")
+                    if coef is not None:
+                        JPEG_TILES["device" if as_coef else "host"] += stop - start
                 forward(self.dev[slot][:count], out_dev[slot][:count])
                 lo = bounds[b][0]
                 out_host[lo:lo + count].copy_(out_dev[slot][:count], non_blocking=True)
@@ -228,7 +281,7 @@ class TileRing:
         except BaseException:
             # a tile source failed (or the forward did): let the decode tasks that are still filling pinned slots
             # finish before the ring is reused for the next slide, then drain the device
-            for tasks, _ in pending.values():
+            for tasks, *_ in pending.values():
                 for t in tasks:
                     try:
                         t.result()

@@ -88,6 +88,39 @@ int ap_host_format_passports(const int32_t* coords, int n, const char* prefix, c
  * AP_ERR_INVALID for a tile that is not side x side or not decodable. */
 int ap_host_decode_jpeg_tiles(void* dst, const char* const* paths, int n, int side);
 
+/* ---- K0: JPEG tile decode split at the entropy decoder ------------------------------------------
+ * Only a JPEG stream's Huffman decode is serial; dequantisation, the 8 x 8 inverse DCT, chroma upsampling and YCbCr -> RGB
+ * are independent per block and exactly defined in integers.  The host half (libjpeg-turbo's jpeg_read_coefficients, same
+ * dlopen'd libjpeg.so.8 as above) delivers a tile's quantised coefficients in a SLOT; the device half turns n slots into the
+ * RGB tiles ap_host_decode_jpeg_tiles / PIL's Image.open(...).convert("RGB") give, bit for bit (libjpeg's JDCT_ISLOW with
+ * fancy upsampling, restated).  Subset: baseline Huffman, 8 bit, greyscale or YCbCr at one of the samplings below.
+ *
+ * A slot is self-contained and ap_jpeg_slot_bytes(side, sampling) long (a multiple of 128; 0 on bad arguments):
+ *   uint16 quant[3][64]   natural order, the components' own order, padded to 512 bytes
+ *   per component         int16 [hb][wb][64], natural order, block rows major; wb x hb = ceil(downsampled size / 8), the
+ *                         component's width_in_blocks x height_in_blocks (not libjpeg's MCU-padded array width)
+ * (4:2:0 at side 256: 512 + 196 608 bytes, the RGB tile it replaces on the way to the device). */
+#define AP_JPEG_GRAY 0
+#define AP_JPEG_444 1
+#define AP_JPEG_422 2                     /* luma 2x1 */
+#define AP_JPEG_420 3                     /* luma 2x2 */
+size_t ap_jpeg_slot_bytes(int side, int sampling);
+/* Header of one file: its size and sampling.  AP_ERR_INVALID for a stream outside the subset (the message names the file
+ * and the reason), AP_ERR_UNSUPPORTED without a usable libjpeg.  Host only. */
+int ap_host_jpeg_probe(const char* path, int* width, int* height, int* sampling);
+/* Reads n files and entropy-decodes them into consecutive slots at `slots` (host memory, e.g. the ring's pinned staging
+ * buffer), one call per chunk outside the interpreter lock.  AP_ERR_INVALID, naming the file and the reason, for a stream
+ * that is progressive, arithmetic coded, not 8 bit, not grey / YCbCr, of another sampling than `sampling`, not side x side,
+ * or that libjpeg warned about (truncated / corrupt): that tile's slot and the slots after it are left untouched, the ones
+ * before it are complete.  AP_ERR_UNSUPPORTED without a usable libjpeg.  Host only, no device work. */
+int ap_host_jpeg_coefficients(void* slots, const char* const* paths, int n, int side, int sampling);
+/* Device half: slots (device, 16-byte aligned, n slots at ap_jpeg_slot_bytes pitch) -> rgb uint8 [n, side, side, 3] (device,
+ * 16-byte aligned).  Dequantise, inverse DCT, range limit, fancy upsampling, colour conversion in one kernel; no workspace.
+ * Reads nothing beyond n * slot_bytes and writes nothing beyond n * side * side * 3.  AP_ERR_INVALID for null or misaligned
+ * pointers, side <= 0, a side whose band does not fit one workgroup's 64 KB of LDS (every sampling takes side <= 976), n < 0,
+ * an unknown sampling; n == 0 is AP_OK. */
+int ap_jpeg_decode_tiles(const void* slots, int n, int side, int sampling, uint8_t* rgb, ap_stream_t stream);
+
 /* The same for a slide OpenSlide can open (the reference's production tile source): core/wsi/openslide_wsi.py:184-205 reads
  * one region per call in the interpreter -- openslide-python's read_region (premultiplied ARGB -> RGBA in its C helper, a
  * PIL image) + .convert("RGB") + np.array.  ap_host_openslide_read_tiles reads n regions of w x h pixels at `level` with
