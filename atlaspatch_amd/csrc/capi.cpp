@@ -5,6 +5,7 @@
 #include <climits>
 #include <cstring>
 #include <cstdlib>
+#include <mutex>
 #include <vector>
 #include <zlib.h>
 #include <cmath>
@@ -21,6 +22,12 @@ void set_error(const char* fmt, ...) {
     vsnprintf(g_error, sizeof(g_error), fmt, ap_);
     va_end(ap_);
 }
+
+// The zero row of ap_gemm_split_f16_windows mode 1: zero-initialised memory of the code object itself, which the loader
+// fills when it places the object on a device.  No first call has anything to allocate, to zero on some stream or to publish,
+// so no call on another stream or thread can find it half made.
+constexpr int kZeroFloats = 16384;
+__attribute__((used)) __device__ float g_zero_row[kZeroFloats];
 
 }  // namespace ap
 
@@ -229,18 +236,23 @@ static int gemm_split_f16(const float* A, int lda, const void* w_split, int M, i
         AP_REQUIRE((long)b * g.win_nwy * g.win_nwx * ws * ws == (long)M, "ap_gemm_split_f16_windows: M = %d is not %d images x %d x %d windows of %d x %d", M, b,
                    g.win_nwy, g.win_nwx, ws, ws);
         if (win_mode == 1) {
-            // padding rows of the gathered operand: one row of zeros per device, allocated on first use (outside any stream capture: the
-            // predictor's warm-up forward comes first)
-            constexpr int kZeroFloats = 16384;
+            // padding rows of the gathered operand: ap::g_zero_row, one copy per device.  Every thread and every stream reads the
+            // same row, and it is complete before anyone can ask for it; only its address is looked up once per device (the
+            // predictor's warm-up forward comes before any stream capture).
+            static std::mutex zero_mu;
             static float* zero_rows[64] = {};
             int dev = 0;
             AP_HIP_CHECK(hipGetDevice(&dev));
-            AP_REQUIRE(dev >= 0 && dev < 64 && K <= kZeroFloats, "ap_gemm_split_f16_windows: device %d / K %d", dev, K);
-            if (!zero_rows[dev]) {
-                AP_HIP_CHECK(hipMalloc((void**)&zero_rows[dev], kZeroFloats * sizeof(float)));
-                AP_HIP_CHECK(hipMemsetAsync(zero_rows[dev], 0, kZeroFloats * sizeof(float), (hipStream_t)stream));   // ordered before this launch
+            AP_REQUIRE(dev >= 0 && dev < 64 && K <= ap::kZeroFloats, "ap_gemm_split_f16_windows: device %d / K %d", dev, K);
+            {
+                std::lock_guard<std::mutex> lock(zero_mu);
+                if (!zero_rows[dev]) {
+                    void* row = nullptr;
+                    AP_HIP_CHECK(hipGetSymbolAddress(&row, HIP_SYMBOL(ap::g_zero_row)));
+                    zero_rows[dev] = (float*)row;
+                }
+                g.zero_row = zero_rows[dev];
             }
-            g.zero_row = zero_rows[dev];
         }
     }
     return ap::launch_gemm_impl(AP_F32, act == 1 ? ap::EPI_BIAS_GELU : ap::EPI_BIAS_STORE, g, 128, 0, (hipStream_t)stream);

@@ -481,13 +481,15 @@ static int sgemm_impl(const float* A, long lda, long strideA, const float* W, lo
         int dev = 0;
         AP_HIP_CHECK(hipGetDevice(&dev));
         static std::mutex mu;
-        static std::map<int, std::pair<float*, size_t>> scratch;         // per device, grow-only
+        // per (device, stream), grow-only: the partial sums live from this call's product kernel to its reduce kernel, and
+        // only work on the same stream is ordered against that.  Two streams never share a buffer, so no event ties them.
+        static std::map<std::pair<int, hipStream_t>, std::pair<float*, size_t>> scratch;
         std::lock_guard<std::mutex> lock(mu);
-        auto& sc = scratch[dev];
+        auto& sc = scratch[{dev, s}];
         if (sc.second < need) {
             // An outgrown buffer is kept alive (captured graphs may still launch kernels that point at it); sizes double,
             // so the total stays below twice the largest request.  hipMalloc is not legal inside a stream capture: callers
-            // that capture (services/sam2_hip.py) run every shape once before capturing.
+            // that capture (services/sam2_hip.py) run every shape once on the capturing stream before capturing.
             const size_t bytes = std::max(need, sc.second * 2);
             float* fresh = nullptr;
             AP_HIP_CHECK(hipMalloc((void**)&fresh, bytes));

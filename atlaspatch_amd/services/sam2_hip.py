@@ -58,6 +58,7 @@ class Sam2HipPredictor:
         self.input_size = 1024
         self.plan, self.stage_ends = block_plan()
         self._graph = None
+        self._capture_stream = None          # warm-up and capture share it: see _capture
         self._flop = None                    # set to 0.0 by count_flop(): _gemm / _attention then add their multiply-adds
         self._batch_graphs: dict = {}
         self.fused_attention = os.environ.get("ATLASPATCH_SAM2_UNFUSED_ATTENTION") in (None, "", "0")
@@ -516,6 +517,24 @@ class Sam2HipPredictor:
                 mask = out
             return mask.cpu().numpy()
 
+    def _capture(self, forward):
+        """``forward()`` once as a warm-up, then captured into a hipGraph, both on this predictor's capture stream.  Nothing may
+        allocate inside a capture, and the library keeps the split-K scratch of ap_sgemm per stream: the warm-up has to grow it
+        on the very stream the capture then records (torch captures on a side stream, never on the current one).  Returns the
+        graph and the captured call's result."""
+        if self._capture_stream is None:
+            self._capture_stream = torch.cuda.Stream(self.device)
+        side = self._capture_stream
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            forward()                                            # warm-up outside the capture (scratch growth, lazy initialisation)
+        with _lib.HIP_CAPTURE_LOCK:                              # no weight upload of a side thread inside the capture
+            torch.cuda.synchronize(self.device)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
+                out = forward()
+        return graph, out
+
     def _graph_mask_device(self, img: torch.Tensor) -> torch.Tensor:
         """``_graph_mask`` for an input already in HBM (device-to-device copy into the graph's static input)."""
         import os
@@ -524,13 +543,7 @@ class Sam2HipPredictor:
         if self._graph is None:
             self._static_img = torch.empty((self.input_size, self.input_size, 3), dtype=torch.uint8, device=self.device)
             self._static_img.copy_(img)
-            self._forward_mask(self._static_img)                 # warm-up outside the capture (lazy initialisation)
-            with _lib.HIP_CAPTURE_LOCK:                          # no weight upload of a side thread inside the capture
-                torch.cuda.synchronize(self.device)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    self._static_mask = self._forward_mask(self._static_img)
-            self._graph = graph
+            self._graph, self._static_mask = self._capture(lambda: self._forward_mask(self._static_img))
         self._static_img.copy_(img)
         self._graph.replay()
         return self._static_mask
@@ -560,12 +573,7 @@ class Sam2HipPredictor:
         if entry is None:
             static_in = torch.empty((B, self.input_size, self.input_size, 3), dtype=torch.uint8, device=self.device)
             static_in.copy_(imgs)
-            self._forward_masks(static_in)                       # warm-up outside the capture (scratch growth, lazy init)
-            with _lib.HIP_CAPTURE_LOCK:
-                torch.cuda.synchronize(self.device)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    static_out = self._forward_masks(static_in)
+            graph, static_out = self._capture(lambda: self._forward_masks(static_in))
             entry = self._batch_graphs[B] = (graph, static_in, static_out)
             while len(self._batch_graphs) > 3:                   # a run uses one batch size plus at most two remainder sizes (cohort, MAX_BATCH chunk)
                 self._batch_graphs.pop(next(iter(self._batch_graphs)))

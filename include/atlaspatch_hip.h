@@ -11,6 +11,29 @@
  * Each block cites the reference interface it replaces (paths under
  * /root/reference/atlas_patch).  INTEGRATION.md shows the ctypes stubs a
  * maintainer of the reference would add.
+ *
+ * Streams and threads (tests/test_gpu_streams.py; the test that backs each sentence in brackets):
+ *  - Operators may be called at the same time from several host threads and on several streams, as long as no call writes
+ *    a buffer that another call reads or writes.  Nothing the library owns is shared between two streams' kernels: the split-K
+ *    scratch of ap_sgemm / ap_sgemm_stacked is kept per (device, stream), grow-only, for the life of the process
+ *    [test_splitk_against_splitk, test_stacked_splitk_against_batched_splitk, test_splitk_against_non_split_controls,
+ *    test_first_use_in_a_fresh_process[growth], test_host_threads].
+ *  - ap_last_error() is per thread [test_host_threads].
+ *  - One engine handle may run forwards on several streams at once, given a workspace and an output of its own per
+ *    forward [test_one_vit_handle_on_two_streams]; different handles are independent [test_two_engines_on_two_streams].
+ *    Two restrictions, read from the engines' code [not covered by a test]: not while profiling is enabled (the handle
+ *    owns the events), and with AP_VIT_OPT_TWO_HALF_OVERLAP at most one forward of n >= 512 at a time (the handle owns the
+ *    side stream and its two events; the test runs one such forward beside a smaller one).
+ *  - *_set_param / *_set_params / *_finalize / *_set_option / *_profile_* are not concurrent with a forward on the same
+ *    handle [not covered by a test: it is a restriction].
+ *  - The first use of an operator, or of a larger shape, may allocate, upload and wait for its own upload (the scratch
+ *    above, the normalisation and cv2 tables): it must happen outside a stream capture, and, for the per-stream scratch, on
+ *    the stream that is then captured.  A captured graph keeps pointing at the scratch of the stream it was captured on:
+ *    replay it on one stream at a time.  State that is shared is complete before it is published; the zero row of
+ *    ap_gemm_split_f16_windows mode 1 is zero-initialised memory of the library's code object, complete when it is loaded
+ *    [test_first_use_in_a_fresh_process[zero_row], [lut_first], [attr_first]].
+ *  - Caches are per device.  The hipFuncSetAttribute guards (attention, device contours) are per process: a process that
+ *    drives several devices is not covered by these tests.
  */
 #ifndef ATLASPATCH_HIP_H
 #define ATLASPATCH_HIP_H
