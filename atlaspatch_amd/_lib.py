@@ -300,6 +300,16 @@ SIGNATURES = {
     "ap_host_openslide_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
     "ap_host_openslide_read_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ap_host_openslide_close": (None, [C.c_void_p]),
+    "ap_host_tiff_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
+    "ap_host_tiff_close": (None, [C.c_void_p]),
+    "ap_host_tiff_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_char_p, C.c_size_t,
+                                    C.POINTER(C.c_size_t)]),
+    "ap_host_tiff_level": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "ap_host_tiff_tile_present": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "ap_host_tiff_read_patches": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "ap_host_tiff_tile_coefficients": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "ap_gather_patches": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p]),
 }
 
 

@@ -1,5 +1,9 @@
 """Backend registry keyed by file extension (reference: core/wsi/wsi_factory.py:12-141), with the
-synthetic backend mapped to ``.synth``."""
+synthetic backend mapped to ``.synth``.
+
+``ATLASPATCH_TIFF_NATIVE=1`` (opt-in) sends ``.svs`` / ``.tif`` / ``.tiff`` files that ``ap_host_tiff_open`` accepts -- tiled TIFF
+with JPEG tiles -- to the native ``tiff`` backend (tiff_wsi.py); a file it refuses, and every file with the switch unset, goes
+to ``openslide`` as before.  ``backend="tiff"`` works either way."""
 from __future__ import annotations
 
 import os
@@ -10,14 +14,19 @@ from .image_wsi import ImageWSI
 from .iwsi import IWSI
 from .openslide_wsi import OpenSlideWSI
 from .synth_wsi import SynthWSI
+from .tiff_wsi import TiffWSI
 
 _OPENSLIDE_EXT = (".svs", ".tif", ".tiff", ".ndpi", ".vms", ".vmu", ".scn", ".mrxs", ".bif", ".biff",
                   ".dcm", ".dicom")
 _IMAGE_EXT = (".png", ".jpg", ".jpeg", ".bmp", ".webp", ".gif")
+_TIFF_NATIVE_EXT = (".svs", ".tif", ".tiff")
 
 
 class WSIFactory:
     _registry = {"openslide": OpenSlideWSI, "image": ImageWSI, "synth": SynthWSI}
+    # backends that are reached by name (or by detect() under their switch) and are NOT tried by try_load's default sweep, so that
+    # the registry's contents -- and with them every default path -- stay what they were
+    _by_name = {"tiff": TiffWSI}
     _formats = {**{e: "openslide" for e in _OPENSLIDE_EXT}, **{e: "image" for e in _IMAGE_EXT},
                 ".synth": "synth"}
 
@@ -33,7 +42,25 @@ class WSIFactory:
 
     @classmethod
     def detect(cls, path: str) -> Optional[str]:
-        return cls._formats.get(Path(path).suffix.lower())
+        ext = Path(path).suffix.lower()
+        backend = cls._formats.get(ext)
+        if backend == "openslide" and ext in _TIFF_NATIVE_EXT and cls._tiff_native(path):
+            return "tiff"
+        return backend
+
+    @staticmethod
+    def _tiff_native(path: str) -> bool:
+        """ATLASPATCH_TIFF_NATIVE=1 and ``ap_host_tiff_open`` accepts the file."""
+        from ...utils.env import env_flag
+        if not env_flag("ATLASPATCH_TIFF_NATIVE") or not os.path.isfile(path):
+            return False
+        from ... import _lib
+        from .tiff_wsi import open_native
+        handle, _ = open_native(path)
+        if handle is None:
+            return False
+        _lib.load().ap_host_tiff_close(handle)
+        return True
 
     @classmethod
     def load(cls, path: str, backend: Optional[str] = None, mpp: Optional[float] = None, **kwargs) -> IWSI:
@@ -43,9 +70,10 @@ class WSIFactory:
             backend = cls.detect(path)
             if backend is None:
                 raise ValueError(f"No backend found for: {path}")
-        elif backend not in cls._registry:
+        elif backend not in cls._registry and backend not in cls._by_name:
             raise ValueError(f"Unknown backend: {backend}")
-        return cls._registry[backend](path=path, mpp=mpp, **kwargs)
+        impl = cls._registry.get(backend) or cls._by_name[backend]
+        return impl(path=path, mpp=mpp, **kwargs)
 
     @classmethod
     def try_load(cls, path: str, backends: Optional[list] = None, mpp: Optional[float] = None, **kwargs) -> IWSI:
@@ -53,7 +81,7 @@ class WSIFactory:
             raise FileNotFoundError(f"File not found: {path}")
         problems = []
         for name in (backends if backends is not None else list(cls._registry)):
-            if name not in cls._registry:
+            if name not in cls._registry and name not in cls._by_name:
                 problems.append(f"{name}: not registered")
                 continue
             try:

@@ -20,6 +20,7 @@
 #include <vector>
 #include "ap_common.h"
 #include "jpeg_slot.h"
+#include "jpeg_host.h"
 
 namespace {
 
@@ -147,6 +148,7 @@ constexpr int JCS_GRAYSCALE = 1;
 constexpr int JCS_RGB = 2;
 constexpr int JCS_YCbCr = 3;
 constexpr int JPEG_HEADER_OK = 1;
+constexpr int JPEG_HEADER_TABLES_ONLY = 2;
 
 struct Api {
     jpeg_error_mgr* (*std_error)(jpeg_error_mgr*);
@@ -186,9 +188,10 @@ void on_message(void* cinfo, int msg_level) {
 Api g_api;
 std::once_flag g_once;
 
-// decode one in-memory JPEG into dst (rows of `stride` bytes); returns 0 or fills `why`
+// decode one in-memory JPEG into dst (rows of `stride` bytes); returns 0 or fills `why`.  `tables` (may be null): a tables-only
+// stream (TIFF's JPEGTables tag) read with jpeg_read_header(..., FALSE) in front of an abbreviated `data`, as libtiff does.
 int decode_one(const Api& api, const unsigned char* data, size_t size, int want_w, int want_h, unsigned char* dst,
-               size_t stride, char* why, size_t why_cap) {
+               size_t stride, char* why, size_t why_cap, const unsigned char* tables = nullptr, size_t tables_size = 0) {
     jpeg_decompress_struct c;
     ErrJmp err;
     memset(&c, 0, sizeof(c));
@@ -204,6 +207,10 @@ int decode_one(const Api& api, const unsigned char* data, size_t size, int want_
     }
     api.create(&c, kJpegLibVersion, sizeof(jpeg_decompress_struct));
     created = true;
+    if (tables && tables_size) {
+        api.mem_src(&c, tables, (unsigned long)tables_size);
+        if (api.read_header(&c, 0) != JPEG_HEADER_TABLES_ONLY) { snprintf(why, why_cap, "JPEGTables is not a tables-only stream"); api.destroy(&c); return -1; }
+    }
     api.mem_src(&c, data, (unsigned long)size);
     if (api.read_header(&c, 1) != JPEG_HEADER_OK) { snprintf(why, why_cap, "not a JPEG stream"); api.destroy(&c); return -1; }
     c.out_color_space = JCS_RGB;          // what PIL's convert("RGB") yields for YCbCr and greyscale streams alike
@@ -236,7 +243,7 @@ int decode_one(const Api& api, const unsigned char* data, size_t size, int want_
 // subset -- baseline Huffman, 8 bit, grey or YCbCr at 4:4:4 / 4:2:2 / 4:2:0 -- or one libjpeg warned about is refused with its
 // reason in `why` and nothing written to the slot.
 int read_one(const Api& api, const unsigned char* data, size_t size, int wh[2], int* sampling, int want_side, int want_sampling,
-             unsigned char* slot, char* why, size_t why_cap) {
+             unsigned char* slot, char* why, size_t why_cap, const unsigned char* tables = nullptr, size_t tables_size = 0) {
     jpeg_decompress_struct c;
     ErrJmp err;
     memset(&c, 0, sizeof(c));
@@ -252,8 +259,12 @@ int read_one(const Api& api, const unsigned char* data, size_t size, int wh[2], 
     }
     api.create(&c, kJpegLibVersion, sizeof(jpeg_decompress_struct));
     created = true;
-    api.mem_src(&c, data, (unsigned long)size);
 #define refuse(...) (snprintf(why, why_cap, __VA_ARGS__), api.destroy(&c), -1)
+    if (tables && tables_size) {
+        api.mem_src(&c, tables, (unsigned long)tables_size);
+        if (api.read_header(&c, 0) != JPEG_HEADER_TABLES_ONLY) return refuse("JPEGTables is not a tables-only stream");
+    }
+    api.mem_src(&c, data, (unsigned long)size);
     if (api.read_header(&c, 1) != JPEG_HEADER_OK) return refuse("not a JPEG stream");
     if (c.progressive_mode) return refuse("progressive stream");
     if (c.arith_code) return refuse("arithmetic-coded stream");
@@ -380,6 +391,30 @@ int read_file(const char* what, const char* path, std::vector<unsigned char>& bu
 }
 
 }  // namespace
+
+// ---- the in-memory "tables + stream" path (jpeg_host.h): what the file readers below and the TIFF reader share ----------
+namespace ap {
+
+int jpeg_mem_ready(char* why, size_t why_cap) {
+    std::call_once(g_once, load_api);
+    if (!g_api.ok) { snprintf(why, why_cap, "%s", g_api.why); return AP_ERR_UNSUPPORTED; }
+    return AP_OK;
+}
+
+int jpeg_mem_pixels(const unsigned char* tables, size_t tables_size, const unsigned char* data, size_t size, int want_w, int want_h,
+                    unsigned char* dst, size_t stride, char* why, size_t why_cap) {
+    if (int rc = jpeg_mem_ready(why, why_cap)) return rc;
+    return decode_one(g_api, data, size, want_w, want_h, dst, stride, why, why_cap, tables, tables_size) == 0 ? AP_OK : AP_ERR_INVALID;
+}
+
+int jpeg_mem_coefficients(const unsigned char* tables, size_t tables_size, const unsigned char* data, size_t size, int wh[2],
+                          int* sampling, int want_side, int want_sampling, unsigned char* slot, char* why, size_t why_cap) {
+    if (int rc = jpeg_mem_ready(why, why_cap)) return rc;
+    return read_one(g_api, data, size, wh, sampling, want_side, want_sampling, slot, why, why_cap, tables, tables_size) == 0
+               ? AP_OK : AP_ERR_INVALID;
+}
+
+}  // namespace ap
 
 extern "C" int ap_host_decode_jpeg_tiles(void* dst, const char* const* paths, int n, int side) {
     AP_REQUIRE(dst && (paths || n == 0) && n >= 0 && side > 0, "ap_host_decode_jpeg_tiles: bad arguments");

@@ -331,6 +331,16 @@ class PatchFeatureEmbeddingService(FeatureEmbeddingService):
         if coef_sampling is not None:
             from .. import _lib
             coef_bytes = int(_lib.load().ap_jpeg_slot_bytes(rw, coef_sampling))
+        # ... and a tile-grid backend (tiled-JPEG TIFF) ships each chunk's distinct tiles that way; the patches are gathered on the device
+        gather, tile_gather = None, None
+        probe = getattr(wsi, "tile_gather_geometry", None)
+        if coef_sampling is None and probe is not None and rw == rh:
+            gather = probe(coords[:16].tolist(), rw)
+        if gather is not None:
+            from .. import _lib
+            coef_bytes = int(_lib.load().ap_jpeg_slot_bytes(gather["ts"], gather["sampling"])) * gather["G"] ** 2
+            tile_gather = dict(geometry=gather, plan=lambda rows: wsi.tile_gather_plan(rows, gather, rw),
+                               read=lambda ids, ptr: wsi.read_tile_coefficients_into(ids, gather, ptr))
         batch = self._ring_batch(extractor, tile_hw, coef_bytes)
         pinned = self._result_buffer(slot, coords.shape[0], extractor.embedding_dim) if slot is not None else None
         feats = self._embed_device_source(coords, wsi, extractor, batch, pinned)
@@ -354,7 +364,7 @@ class PatchFeatureEmbeddingService(FeatureEmbeddingService):
                             lambda tiles, out: extractor.forward_device(_to_patch_size(tiles, ps), out),
                             extractor.embedding_dim, read_chunk=getattr(wsi, "read_tiles_into", None), out_host=pinned,
                             read_coefficients=getattr(wsi, "read_coefficients_into", None) if coef_sampling is not None else None,
-                            coef_sampling=coef_sampling)
+                            coef_sampling=coef_sampling, tile_gather=tile_gather)
 
     def _embed_device_source(self, coords: np.ndarray, wsi: IWSI, extractor, batch: int, pinned=None):
         """Backends that can materialise tiles in HBM themselves (``extract_batch_device``, e.g. the synthetic

@@ -160,6 +160,61 @@ int ap_host_openslide_open(const char* path, ap_openslide** out);
 int ap_host_openslide_read_tiles(ap_openslide* slide, const int64_t* xy, int n, int level, int w, int h, void* dst_rgb);
 void ap_host_openslide_close(ap_openslide* slide);
 
+/* ---- K0: tiled-JPEG TIFF / Aperio SVS slides, read natively (additive: AP_ABI_VERSION stays 20) -------
+ * A dependency-free, read-only reader (no libtiff, no OpenSlide; pread only, so one handle serves every decode thread at once
+ * and holds no file position).  Accepted: classic TIFF and BigTIFF in both byte orders, an IFD chain without cycles of at most
+ * 4096 IFDs, tiled IFDs with Compression 7 (JPEG), BitsPerSample 8, SamplesPerPixel 1 or 3, PlanarConfiguration 1, an optional
+ * JPEGTables stream per IFD.  Those IFDs are the LEVELS, widest first; stripped IFDs (Aperio's thumbnail, label, macro) are
+ * skipped.  A tile whose offset or byte count is 0 is a MISSING tile.  ap_host_tiff_open refuses, naming the reason
+ * (AP_ERR_UNSUPPORTED: no tiled JPEG level, another compression -- Aperio JPEG 2000 33003 / 33005, LZW, deflate, old-style
+ * JPEG --, other sample layouts; AP_ERR_INVALID: an offset, count or tile extent outside the file, a tile size that is no
+ * multiple of 16, tile counts that do not match the grid, arithmetic that would overflow, not a TIFF): the caller falls back
+ * to another backend.  The file is untrusted: every offset read from it is checked against the file size before use.
+ * Host only, no device work. */
+typedef struct ap_tiff ap_tiff;
+int ap_host_tiff_open(const char* path, ap_tiff** out);
+void ap_host_tiff_close(ap_tiff* slide);
+/* levels: the level count; resolution: double [2] = XResolution, YResolution of level 0 (0 = absent); resolution_unit: its
+ * ResolutionUnit (1 none, 2 inch -- TIFF's default --, 3 centimetre); level 0's ImageDescription, NUL terminated and truncated to
+ * description_cap, its full length in *description_bytes (description may be null with description_cap 0). */
+int ap_host_tiff_info(const ap_tiff* slide, int* levels, double* resolution, int* resolution_unit, char* description,
+                      size_t description_cap, size_t* description_bytes);
+/* geometry: int64 [8] = width, height, tile_w, tile_h, tiles_x, tiles_y, sampling, bytes of the JPEGTables stream.
+ * sampling: the AP_JPEG_* value probed from the level's first present tile, or -1 when the level's streams are outside
+ * ap_jpeg_decode_tiles' subset (progressive, RGB coded, not square, wider than 976, no usable libjpeg). */
+int ap_host_tiff_level(const ap_tiff* slide, int level, int64_t* geometry);
+/* present: uint8 [tiles_y * tiles_x], row major: 1 = the file holds the tile, 0 = a missing tile. */
+int ap_host_tiff_tile_present(const ap_tiff* slide, int level, uint8_t* present);
+/* The host pixel route: n RGB patches [h, w, 3] into consecutive slots at dst, patch i with its top-left corner at LEVEL
+ * coordinates xy[i] (HOST int64 [n, 2]).  The covered tiles are decoded by the dlopen'd libjpeg of ap_host_decode_jpeg_tiles
+ * (JPEGTables through jpeg_read_header(..., FALSE) first, then the tile stream, as libtiff and OpenSlide do; the colour space is
+ * the one libjpeg infers from the stream, PhotometricInterpretation is not consulted), each tile once per call however many
+ * patches cover it.  Pixels outside the level and pixels of missing tiles are 0; the padding of edge tiles never shows.
+ * AP_ERR_INVALID, naming level and tile, for a tile that is not tile_w x tile_h, not decodable or that libjpeg warned about;
+ * AP_ERR_UNSUPPORTED without a usable libjpeg. */
+int ap_host_tiff_read_patches(const ap_tiff* slide, int level, const int64_t* xy, int n, int w, int h, void* dst);
+/* The coefficient route (levels with sampling >= 0): entropy-decodes the m tiles tile_ids[i] = ty * tiles_x + tx (HOST int32)
+ * into consecutive ap_jpeg_slot_bytes(tile_w, sampling) slots, the slot format and the refusals of ap_host_jpeg_coefficients.
+ * A missing tile is refused too: the caller marks it absent in its gather plan instead of asking for it. */
+int ap_host_tiff_tile_coefficients(const ap_tiff* slide, int level, const int32_t* tile_ids, int m, void* slots);
+
+/* Device: patches that do not sit on the tile grid, assembled from decoded tiles (the output of ap_jpeg_decode_tiles).
+ *   tiles  uint8 [m, ts, ts, 3]      device, 16-byte aligned
+ *   plan   int32 [n, 4 + G*G]        per patch: ox, oy, vw, vh, then G*G tile slots row-major (-1 = a missing tile)
+ *   out    uint8 [n, ph, pw, 3]      device, 16-byte aligned
+ *   out[p][r][c] = (r < vh && c < vw && slot >= 0) ? tiles[slot][(oy+r) % ts][(ox+c) % ts] : 0
+ *                  with slot = plan[p][4 + ((oy+r)/ts)*G + (ox+c)/ts]
+ * 0 <= ox, oy < ts; G >= ceil((max(pw, ph) + ts - 1) / ts); vw <= pw and vh <= ph clip the patch at the level's right and
+ * bottom edge (TIFF edge tiles are stored full size; their padding must not leak).  plan_host is the HOST copy: it is checked
+ * here, before anything is uploaded or launched, and then copied to plan_dev (device, n * (4 + G*G) int32) on `stream`; it
+ * must stay unchanged until that copy has run (pinned memory keeps the call asynchronous).  One lane forms 16 output bytes
+ * from aligned loads and a byte-align step; writes nothing beyond n * ph * pw * 3.  AP_ERR_INVALID, with nothing launched, for
+ * null or misaligned pointers, n < 0, m < 0, ts / pw / ph / G <= 0, a G too small, ox / oy / vw / vh out of range, a slot >= m,
+ * tiles or (n > 1) patches whose starts are not 16-byte aligned (ts * ts * 3 or ph * pw * 3 no multiple of 16), a patch of
+ * 2^24 bytes or more.  n == 0 is AP_OK. */
+int ap_gather_patches(const uint8_t* tiles, int m, int ts, const int32_t* plan_host, int32_t* plan_dev, int n, int G, int pw, int ph,
+                      uint8_t* out, ap_stream_t stream);
+
 /* Host twin of ap_synth_tiles (below): renders n square tiles of a synthetic slide into consecutive slots of a pinned
  * staging buffer, outside the interpreter lock -- the synthetic slide's "native decoder" behind the ring's batched read
  * hook, so the host -> ring -> HBM path can be driven at full rate on the 100 000 x 100 000 slide.  xy: HOST int32 [n, 2]
