@@ -24,6 +24,17 @@ _STAIN_KEYS = ("aperio.stain", "aperio.staindescription", "openslide.stain", "ha
                "philips.stain")
 
 
+def common_level(rows: Sequence, tile_side: int) -> Optional[int]:
+    """The pyramid level the coords ``rows`` (x, y, rw, rh, lv) share when every one of them reads a ``tile_side`` square; None when
+    they are of more than one level or size, or there are none."""
+    if not rows:
+        return None
+    lv = int(rows[0][4])
+    if any(int(r[2]) != tile_side or int(r[3]) != tile_side or int(r[4]) != lv for r in rows):
+        return None
+    return lv
+
+
 class IWSI(abc.ABC):
     MPP_MIN = 0.1
     MPP_MAX = 10.0

@@ -13,7 +13,7 @@ from typing import Literal, Optional, Tuple, Union
 import numpy as np
 from PIL import Image
 
-from .iwsi import IWSI
+from .iwsi import IWSI, common_level
 
 try:  # pragma: no cover - optional dependency
     import openslide
@@ -143,8 +143,8 @@ class OpenSlideWSI(IWSI):
         self._ensure_loaded()
         if not rows:
             return True
-        lv0 = int(rows[0][4])
-        if any(int(r[2]) != tile_side or int(r[3]) != tile_side or int(r[4]) != lv0 for r in rows):
+        lv0 = common_level(rows, tile_side)
+        if lv0 is None:
             return False
         lib = _lib.load()
         handle = self._native_handle()

@@ -21,7 +21,7 @@ from typing import Literal, Optional, Tuple, Union
 import numpy as np
 from PIL import Image
 
-from .iwsi import IWSI
+from .iwsi import IWSI, common_level
 from .synth_pixels import SynthSpec, analytic_mask, render_region
 
 
@@ -163,8 +163,8 @@ class SynthWSI(IWSI):
         self._ensure_loaded()
         if not rows:
             return True
-        lv0 = int(rows[0][4])
-        if any(int(r[2]) != tile_side or int(r[3]) != tile_side or int(r[4]) != lv0 for r in rows):
+        lv0 = common_level(rows, tile_side)
+        if lv0 is None:
             return False
         if self.jpeg_dir is None:
             xy = np.ascontiguousarray([[r[0], r[1]] for r in rows], dtype=np.int32)
@@ -236,7 +236,7 @@ class SynthWSI(IWSI):
         self._ensure_loaded()
         if self.jpeg_dir is None or not rows or getattr(self, "_jpeg_coefficients", True) is False:
             return False
-        if any(int(r[2]) != tile_side or int(r[3]) != tile_side or int(r[4]) != 0 for r in rows):
+        if common_level(rows, tile_side) != 0:
             return False
         files = [os.path.join(self.jpeg_dir, f"{int(x)}_{int(y)}_{int(rw)}.jpg") for x, y, rw, rh, lv in rows]
         if not all(os.path.exists(f) for f in files):

@@ -23,7 +23,7 @@ from typing import Literal, Optional, Tuple, Union
 import numpy as np
 from PIL import Image
 
-from .iwsi import IWSI
+from .iwsi import IWSI, common_level
 from .openslide_wsi import mag_from_properties, mpp_from_properties
 
 _UNITS = {1: "none", 2: "inch", 3: "centimeter"}
@@ -153,8 +153,8 @@ class TiffWSI(IWSI):
         self._ensure_loaded()
         if not rows:
             return True
-        lv0 = int(rows[0][4])
-        if any(int(r[2]) != tile_side or int(r[3]) != tile_side or int(r[4]) != lv0 for r in rows):
+        lv0 = common_level(rows, tile_side)
+        if lv0 is None:
             return False
         xy = np.array([self._level_xy(r[0], r[1], lv0) for r in rows], dtype=np.int64)
         self.read_patches(xy, lv0, (tile_side, tile_side), dst_ptr)
@@ -191,8 +191,8 @@ class TiffWSI(IWSI):
         self._ensure_loaded()
         if not rows or not env_flag("ATLASPATCH_JPEG_DEVICE"):
             return None
-        lv = int(rows[0][4])
-        if not 0 <= lv < self.nlvl or any(int(r[4]) != lv or int(r[2]) != tile_side or int(r[3]) != tile_side for r in rows):
+        lv = common_level(rows, tile_side)
+        if lv is None or not 0 <= lv < self.nlvl:
             return None
         level = self.levels[lv]
         if level["sampling"] < 0 or level["tw"] != level["th"]:

@@ -305,17 +305,18 @@ class PatchFeatureEmbeddingService(FeatureEmbeddingService):
     # read larger than the patch size (resized on the device) shrink the batch so that a pinned slot stays <= ~0.8 GB
     _SLOT_BYTES = 2048 * 256 * 256 * 3 * 2
 
-    def _ring_batch(self, extractor, tile_hw, coef_bytes: int = 0) -> int:
-        """``coef_bytes``: size of a tile's JPEG coefficient slot when the ring also stages those (up to 3 x the RGB tile at
-        4:4:4): the larger of the two pinned slots stays within the budget."""
+    def _ring_batch(self, extractor, tile_hw, staged_bytes: int = 0) -> int:
+        """``staged_bytes``: the most pinned bytes a device route stages per tile (``pinned_row_bytes``: a JPEG coefficient slot is up
+        to 3 x the RGB tile at 4:4:4, a tile-grid route stages G x G of them): the larger of the pinned slots stays within the budget."""
         cap = min(2048, max(1, int(getattr(extractor, "max_batch", 1024))))
-        by_bytes = max(64, self._SLOT_BYTES // max(tile_hw[0] * tile_hw[1] * 3, int(coef_bytes)))
+        by_bytes = max(64, self._SLOT_BYTES // max(tile_hw[0] * tile_hw[1] * 3, int(staged_bytes)))
         return max(1, min(cap, by_bytes))
 
     def embed_matrix(self, result: ExtractionResult, wsi: IWSI, extractor: HipViTFeatureExtractor, *, slot=None) -> np.ndarray:
         """float32 [N, D] for one slide through the pinned tile ring (device pipeline).  Tiles cross the ring at
         their read size; ``cv2.resize`` to ``patch_size`` (feature_embedding.py:94-95) runs on the device."""
         from .tile_ring import TileRing
+        from .tile_routes import routes_for
         coords = read_coords(result.h5_path)
         ps = int(self.cfg.patch_size)
         if coords.shape[0] == 0:
@@ -324,24 +325,9 @@ class PatchFeatureEmbeddingService(FeatureEmbeddingService):
         if np.any(coords[:, 2] != rw) or np.any(coords[:, 3] != rh):
             raise ValueError("coords rows of one slide must share one read size")
         tile_hw = (rh, rw)
-        # ATLASPATCH_JPEG_DEVICE: a JPEG tile store ships entropy-decoded coefficients and the device does the rest of the decode
-        probe = getattr(wsi, "jpeg_coefficient_sampling", None)
-        coef_sampling = probe(coords[:16].tolist(), rw) if probe is not None and rw == rh else None
-        coef_bytes = 0
-        if coef_sampling is not None:
-            from .. import _lib
-            coef_bytes = int(_lib.load().ap_jpeg_slot_bytes(rw, coef_sampling))
-        # ... and a tile-grid backend (tiled-JPEG TIFF) ships each chunk's distinct tiles that way; the patches are gathered on the device
-        gather, tile_gather = None, None
-        probe = getattr(wsi, "tile_gather_geometry", None)
-        if coef_sampling is None and probe is not None and rw == rh:
-            gather = probe(coords[:16].tolist(), rw)
-        if gather is not None:
-            from .. import _lib
-            coef_bytes = int(_lib.load().ap_jpeg_slot_bytes(gather["ts"], gather["sampling"])) * gather["G"] ** 2
-            tile_gather = dict(geometry=gather, plan=lambda rows: wsi.tile_gather_plan(rows, gather, rw),
-                               read=lambda ids, ptr: wsi.read_tile_coefficients_into(ids, gather, ptr))
-        batch = self._ring_batch(extractor, tile_hw, coef_bytes)
+        # ATLASPATCH_JPEG_DEVICE: a JPEG tile store or a tiled-JPEG TIFF ships entropy-decoded coefficients and the device does the rest
+        routes = routes_for(wsi, coords, tile_hw)
+        batch = self._ring_batch(extractor, tile_hw, max((r.pinned_row_bytes for r in routes), default=0))
         pinned = self._result_buffer(slot, coords.shape[0], extractor.embedding_dim) if slot is not None else None
         feats = self._embed_device_source(coords, wsi, extractor, batch, pinned)
         if feats is not None:
@@ -362,9 +348,7 @@ class PatchFeatureEmbeddingService(FeatureEmbeddingService):
         with torch.cuda.device(extractor.device):
             return ring.run(coords, read,
                             lambda tiles, out: extractor.forward_device(_to_patch_size(tiles, ps), out),
-                            extractor.embedding_dim, read_chunk=getattr(wsi, "read_tiles_into", None), out_host=pinned,
-                            read_coefficients=getattr(wsi, "read_coefficients_into", None) if coef_sampling is not None else None,
-                            coef_sampling=coef_sampling, tile_gather=tile_gather)
+                            extractor.embedding_dim, read_chunk=getattr(wsi, "read_tiles_into", None), out_host=pinned, routes=routes)
 
     def _embed_device_source(self, coords: np.ndarray, wsi: IWSI, extractor, batch: int, pinned=None):
         """Backends that can materialise tiles in HBM themselves (``extract_batch_device``, e.g. the synthetic

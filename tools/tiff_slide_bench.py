@@ -19,6 +19,7 @@ from atlaspatch_amd.encoders import build_default_registry
 from atlaspatch_amd.services.extraction import coords_from_mask
 from atlaspatch_amd.services.feature_embedding import PatchFeatureEmbeddingService
 from atlaspatch_amd.services.tile_ring import JPEG_TILES, TIFF_TILES, TileRing
+from atlaspatch_amd.services.tile_routes import routes_for
 
 side = int(sys.argv[1]) if len(sys.argv) > 1 else 40000
 max_patches = int(sys.argv[2]) if len(sys.argv) > 2 else 8192
@@ -133,23 +134,13 @@ def time_kernels():
     print(json.dumps({"kernels_2048_patches": res, "sclk": clock_mhz()}), flush=True)
 
 
-def ring_rate(wsi, coords, ex, workers, kind):
-    """tiles / s of the ring + encoder over `coords`; kind: tiff | synth"""
-    rw = 256
-    coef_sampling, tile_gather, coef_bytes = None, None, 0
-    if kind == "synth":
-        coef_sampling = wsi.jpeg_coefficient_sampling(coords[:16].tolist(), rw)
-        coef_bytes = int(lib.ap_jpeg_slot_bytes(rw, coef_sampling)) if coef_sampling is not None else 0
-    else:
-        g = wsi.tile_gather_geometry(coords[:16].tolist(), rw)
-        if g is not None:
-            coef_bytes = int(lib.ap_jpeg_slot_bytes(g["ts"], g["sampling"])) * g["G"] ** 2
-            tile_gather = dict(geometry=g, plan=lambda rows: wsi.tile_gather_plan(rows, g, rw),
-                               read=lambda ids, ptr: wsi.read_tile_coefficients_into(ids, g, ptr))
-    batch = PatchFeatureEmbeddingService._ring_batch(PatchFeatureEmbeddingService, ex, (rw, rw), coef_bytes)
+def ring_rate(wsi, coords, ex, workers):
+    """tiles / s of the ring + encoder over `coords`"""
+    routes = routes_for(wsi, coords, (256, 256))
+    batch = PatchFeatureEmbeddingService._ring_batch(PatchFeatureEmbeddingService, ex, (256, 256),
+                                                     max((r.pinned_row_bytes for r in routes), default=0))
     ring = TileRing(device=dev, batch=batch, patch_size=256, slots=3, workers=workers)
-    kw = dict(read_chunk=wsi.read_tiles_into, read_coefficients=wsi.read_coefficients_into if coef_sampling is not None else None,
-              coef_sampling=coef_sampling) if kind == "synth" else dict(read_chunk=wsi.read_tiles_into, tile_gather=tile_gather)
+    kw = dict(read_chunk=wsi.read_tiles_into, routes=routes)
     read = lambda x, y, w, h, lv: wsi.extract((x, y), lv=lv, wh=(w, h))
     fwd = lambda tiles, out: ex.forward_device(tiles, out)
     try:
@@ -222,9 +213,8 @@ with tempfile.TemporaryDirectory() as tmp:
     for workers in threads:
         for device_jpeg in (0, 1):
             os.environ["ATLASPATCH_JPEG_DEVICE"] = str(device_jpeg)
-            for name, wsi, kind, rows in (("synth_store_aligned", sw, "synth", aligned), ("tiff_aligned", tw, "tiff", aligned),
-                                          ("tiff_shifted", tw, "tiff", shifted)):
-                rate, batch, counters, feats = ring_rate(wsi, rows, ex, workers, kind)
+            for name, wsi, rows in (("synth_store_aligned", sw, aligned), ("tiff_aligned", tw, aligned), ("tiff_shifted", tw, shifted)):
+                rate, batch, counters, feats = ring_rate(wsi, rows, ex, workers)
                 key = "aligned" if rows is aligned else "shifted"
                 same = None if key not in ref else bool(np.array_equal(ref[key], feats))
                 ref.setdefault(key, feats.copy())
