@@ -56,13 +56,21 @@ int tile_content_counts(const uint8_t* tiles, int n, int h, int w, int black_thr
     AP_REQUIRE(n >= 0 && h > 0 && w > 0 && ((size_t)h * w) % 16 == 0, "tile_content: %d x %d tiles (pixels per tile "
                "must be a multiple of 16)", h, w);
     AP_REQUIRE(aligned16(tiles), "tile_content: tiles must be 16-byte aligned");
+    // the kernel indexes a tile's 16-byte loads in int (gidx * 3): a tile stays below 2^31 bytes
+    AP_REQUIRE((size_t)h * w * 3 < (size_t)1 << 31, "tile_content: a %d x %d tile has 2^31 bytes or more", h, w);
     if (n == 0) return AP_OK;
     AP_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)n * 2 * sizeof(unsigned), stream));
     const int groups = (int)((size_t)h * w / 16);
     int slices = (groups + 255) / 256;
     if (slices > 4) slices = 4;
-    dim3 grid(slices, n), block(256);
-    tile_content_kernel<<<grid, block, 0, stream>>>(tiles, groups, black_thresh, sat_thresh, value_thresh, counts);
+    // the tile is the grid's y dimension (at most 65535): more tiles go in launches of 65535, each on its own tiles and counts
+    constexpr int kMaxGridY = 65535;
+    for (long long t0 = 0; t0 < n; t0 += kMaxGridY) {
+        const int nt = (int)(n - t0 < kMaxGridY ? n - t0 : kMaxGridY);
+        dim3 grid(slices, nt), block(256);
+        tile_content_kernel<<<grid, block, 0, stream>>>(tiles + (size_t)t0 * h * w * 3, groups, black_thresh, sat_thresh,
+                                                        value_thresh, counts + (size_t)t0 * 2);
+    }
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
 }

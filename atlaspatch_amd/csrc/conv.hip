@@ -258,7 +258,9 @@ int launch_conv2d(int dtype, const void* x, int n, int h, int w, int cin, const 
     }
     const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (w + 2 * pad - ksize) / stride + 1;
     const size_t M = (size_t)n * ho * wo;
-    AP_REQUIRE(M < (size_t)1 << 31 && (size_t)ksize * ksize * cin < (size_t)1 << 24, "%s: problem too large", who);
+    // the kernel forms its row indices m0 + r (r < CBM) in int: the last tile's must stay below 2^31
+    AP_REQUIRE(M <= ((size_t)1 << 31) - CBM && (size_t)ksize * ksize * cin < (size_t)1 << 24,
+               "%s: problem too large (n * Ho * Wo = %zu rows, at most 2^31 - %d)", who, M, CBM);
     if (M == 0) return AP_OK;
     ConvArgs a{x, weight, bias, resid, out, h, w, cin, ho, wo, cout, ksize, stride, pad, ksize * ksize * cin, (int)M, act};
     const size_t blocks = (M + CBM - 1) / CBM * (size_t)((cout + CBN - 1) / CBN);

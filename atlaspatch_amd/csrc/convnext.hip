@@ -171,6 +171,8 @@ int launch_layernorm_rows(int dtype, const void* x, int rows, int c, const float
     AP_REQUIRE(eps > 0.f, "layernorm_rows: eps %g", (double)eps);
     AP_REQUIRE(aligned16(x, weight, bias, out), "layernorm_rows: pointers must be 16-byte aligned");
     if (rows == 0) return AP_OK;
+    // four rows per workgroup, the row index blockIdx.x * 4 + wave in int: rows + 3 must not overflow
+    AP_REQUIRE(rows <= 0x7FFFFFFF - 3, "layernorm_rows: rows %d too many (at most 2^31 - 4)", rows);
     const unsigned blocks = (unsigned)((rows + 3) / 4);
     return dispatch_dtype("layernorm_rows", dtype, [&](auto tag) {
         using T = typename decltype(tag)::type;

@@ -349,12 +349,13 @@ extern "C" int ap_cv2_resize_u8(const uint8_t* src, int n, int h, int w, uint8_t
                "ap_cv2_resize_u8: unsupported interpolation %d", interpolation);
     if (n == 0) return AP_OK;                 // an empty batch has no buffers to check
     AP_REQUIRE(src && dst, "ap_cv2_resize_u8: null pointer");
+    const size_t total = (size_t)n * oh * ow;  // one thread per output pixel, 256 per workgroup, fewer than 2^31 workgroups
+    AP_REQUIRE((total + 255) / 256 < (size_t)1 << 31, "ap_cv2_resize_u8: %d images of %d x %d output pixels exceed the grid", n, oh, ow);
     std::shared_ptr<Entry> entry;             // keeps the tables alive through the launch below
     const int rc = get_tables(h, w, oh, ow, interpolation, &entry);
     if (rc != AP_OK) return rc;
     const Tables* t = &entry->t;
     hipStream_t s = (hipStream_t)stream;
-    const size_t total = (size_t)n * oh * ow;
     const unsigned grid = (unsigned)((total + 255) / 256);
     switch (t->mode) {
     case M_COPY:

@@ -230,6 +230,9 @@ int preproc_common(int layout, const uint8_t* src, int n, int h, int w, int top,
     } else {
         a.band = 8;
     }
+    // one workgroup per (image, band): the grid, and the kernel's img * gh + py, are int
+    AP_REQUIRE((long long)n * ((oh + a.band - 1) / a.band) <= 0x7FFFFFFFLL, "preproc: n %d x %d bands exceeds the grid", n,
+               (oh + a.band - 1) / a.band);
     int rc = get_norm_lut(mean, stdv, dtype, stream, &a.lut);
     if (rc != AP_OK) return rc;
     return dispatch_dtype("preproc", dtype, [&](auto tag) { return launch_pre<typename decltype(tag)::type>(layout, a, stream); });

@@ -193,7 +193,10 @@ extern "C" int ap_resample_u8(const uint8_t* src, int n, int h, int w, uint8_t* 
             return AP_OK;
         }
     }
+    // (n > 65535, the fused grid's y limit, arrives here too: both routes give Pillow's bytes)
     const size_t t1 = (size_t)n * h * ow, t2 = (size_t)n * oh * ow;
+    AP_REQUIRE((t1 + 255) / 256 < (size_t)1 << 31 && (t2 + 255) / 256 < (size_t)1 << 31,
+               "ap_resample_u8: %d images of %d x %d -> %d x %d exceed the grid", n, h, w, oh, ow);
     ap::resample_h_kernel<<<(unsigned)((t1 + 255) / 256), 256, 0, s>>>(src, n, h, w, ow, bounds_x, coeffs_x, ksize_x, tmp);
     ap::resample_v_kernel<<<(unsigned)((t2 + 255) / 256), 256, 0, s>>>(tmp, n, h, ow, oh, bounds_y, coeffs_y, ksize_y, dst);
     AP_HIP_CHECK(hipGetLastError());

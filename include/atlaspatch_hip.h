@@ -74,7 +74,9 @@ int ap_device_info(int device, char* name, int name_cap, int* cu_count, size_t* 
  * the cast to f16/bf16 happens after normalisation (base.py:95-99).
  *
  * src: device uint8 [n, h, w, 3] (HWC RGB).  Output window: rows crop_top..crop_top+oh,
- * cols crop_left..crop_left+ow (centre crop of torchvision ImageClassification; no resample). */
+ * cols crop_left..crop_left+ow (centre crop of torchvision ImageClassification; no resample).
+ * Offsets into src and dst are 64-bit (buffers beyond 4 GiB are fine); one workgroup per image and band of 8 rows (patch
+ * rows: ps rows), so n * bands <= 2^31 - 1 (AP_ERR_INVALID beyond, nothing launched). */
 int ap_preproc_u8hwc_to_chw(const uint8_t* src, int n, int h, int w,
                             int crop_top, int crop_left, int oh, int ow,
                             const float mean[3], const float stdv[3],
@@ -229,7 +231,9 @@ int ap_host_synth_tiles(void* dst, const int32_t* xy, int n, int side, int level
  * Bit-identical to PIL.Image.resize for uint8 RGB: horizontal then vertical pass, 22-bit fixed-point weights.
  * bounds_* : device int32 [out, 2] (first input index, tap count); coeffs_* : device int32 [out, ksize_*]
  * (the tables of Pillow's precompute_coeffs + normalize_coeffs_8bpc, built by the host);
- * src uint8 [n, h, w, 3] -> dst uint8 [n, oh, ow, 3]; tmp: device scratch of n*h*ow*3 bytes. */
+ * src uint8 [n, h, w, 3] -> dst uint8 [n, oh, ow, 3]; tmp: device scratch of n*h*ow*3 bytes.
+ * Offsets into src, tmp and dst are 64-bit.  More than 65535 images take the two-pass kernels whatever the shape (the same
+ * bytes); n*h*ow and n*oh*ow are at most 2^39 - 256 (fewer than 2^31 workgroups of 256; AP_ERR_INVALID beyond, nothing launched). */
 int ap_resample_u8(const uint8_t* src, int n, int h, int w, uint8_t* dst, int oh, int ow,
                    const int32_t* bounds_x, const int32_t* coeffs_x, int ksize_x,
                    const int32_t* bounds_y, const int32_t* coeffs_y, int ksize_y,
@@ -256,7 +260,8 @@ int ap_pillow_reduce_u8(const uint8_t* src, int h, int w, int box_x, int box_y, 
  * synchronous upload), then cached.
  * src: device uint8 [n, h, w, 3] -> dst: device uint8 [n, oh, ow, 3].  interpolation: cv2's constants.
  * flags: AP_CV_CUBIC_SCALAR = bicubic vertical pass in int32 for every element (OpenCV's scalar code); default =
- * what an x86-64 build executes (float32 vector loop for all but the last (ow * 3) % 8 elements of a row). */
+ * what an x86-64 build executes (float32 vector loop for all but the last (ow * 3) % 8 elements of a row).
+ * Offsets into src and dst are 64-bit; n * oh * ow is at most 2^39 - 256 (AP_ERR_INVALID beyond, nothing launched). */
 #define AP_CV_INTER_LINEAR 1
 #define AP_CV_INTER_CUBIC 2
 #define AP_CV_INTER_AREA 3
@@ -269,7 +274,8 @@ int ap_cv2_resize_u8(const uint8_t* src, int n, int h, int w, uint8_t* dst, int 
  * applies to every candidate tile: counts[i] = { #pixels with cv2 RGB2GRAY < black_thresh,
  * #pixels with cv2 RGB2HSV S < white_sat_thresh and V >= white_value_thresh } (OpenCV's 8-bit fixed-point
  * conversions, bit-exact).  The caller compares count / (h*w) with 0.7 like the reference.
- * tiles: device uint8 [n, h, w, 3] (16-byte aligned, h*w % 16 == 0); counts: device uint32 [n, 2]. */
+ * tiles: device uint8 [n, h, w, 3] (16-byte aligned, h*w % 16 == 0, a tile below 2^31 bytes); counts: device uint32 [n, 2].
+ * Any n: more than 65535 tiles run as several launches on `stream`; offsets into tiles are 64-bit. */
 int ap_tile_content_counts(const uint8_t* tiles, int n, int h, int w, int black_thresh,
                            int white_sat_thresh, int white_value_thresh, uint32_t* counts,
                            ap_stream_t stream);
@@ -776,7 +782,8 @@ int ap_resnet_forward_u8(ap_resnet* m, const uint8_t* patches, int n, int h, int
 /* Single operators of the ResNet forward (NHWC, T = dtype, device pointers 16-byte aligned):
  * ap_conv2d_nhwc: out[n, Ho, Wo, cout] = act(conv(x, weight) + bias[co] (+ resid)), x T [n, h, w, cin] (cin % 8 == 0),
  *   weight T [cout][ksize][ksize][cin] (cout % 64 == 0), bias f32 [cout], resid T [n, Ho, Wo, cout] or NULL, relu 0 / 1;
- *   Ho = (h + 2 pad - ksize) / stride + 1; taps outside the image are zeros.
+ *   Ho = (h + 2 pad - ksize) / stride + 1; taps outside the image are zeros.  Offsets into x, resid and out are 64-bit; the
+ *   output pixel index is an int, so n * Ho * Wo <= 2^31 - 128 (AP_ERR_INVALID beyond, nothing launched).
  * ap_maxpool3x3s2_nhwc: out T [n, (h - 1) / 2 + 1, (w - 1) / 2 + 1, c] (padding 1; padded taps ignored), c % 8 == 0.
  * ap_avgpool_nhwc: out f32 [n, c] = mean over the hw pixels of x T [n, hw, c], summed in f32. */
 int ap_conv2d_nhwc(int dtype, const void* x, int n, int h, int w, int cin, const void* weight, const float* bias, int cout,
@@ -837,7 +844,8 @@ int ap_convnext_forward_u8(ap_convnext* m, const uint8_t* patches, int n, int h,
  * ap_dwconv7_ln_nhwc: y = T(depthwise 7x7 conv (padding 3) of x T [n, h, w, c] + dw_bias), then out T [n, h, w, c] =
  *   LayerNorm over the c channels of each pixel of y (f32 statistics, eps) * ln_weight + ln_bias; dw_weight f32 [49][c]
  *   (tap-major: [(ky * 7 + kx) * c + ch]), the rest f32 [c]; c % 8 == 0; out must not alias x.
- * ap_layernorm_rows: out T [rows, c] = LayerNorm of each row of x T [rows, c] (f32 statistics, eps) * weight + bias. */
+ * ap_layernorm_rows: out T [rows, c] = LayerNorm of each row of x T [rows, c] (f32 statistics, eps) * weight + bias;
+ *   rows <= 2^31 - 4 (AP_ERR_INVALID beyond). */
 int ap_conv2d_nhwc_ex(int dtype, const void* x, int n, int h, int w, int cin, const void* weight, const float* bias, int cout,
                       int ksize, int stride, int pad, const void* resid, int act, void* out, ap_stream_t stream);
 int ap_dwconv7_ln_nhwc(int dtype, const void* x, int n, int h, int w, int c, const float* dw_weight, const float* dw_bias,

@@ -58,6 +58,17 @@ class GuardedBytes:
             self.flat[:self.start].fill_(value)
             self.flat[self.start + self.nbytes:].fill_(value)
 
+    def fill_in_steps(self, value, step=1 << 27):
+        """fill(value) for a buffer of any size: `step` bytes per torch call."""
+        for o in range(0, self.flat.numel(), step):
+            self.flat[o:o + step].fill_(value)
+
+    def guards_intact(self, value):
+        """Both guards hold ``value`` in every byte, compared where the buffer lies: nothing but two bools reaches the host
+        (``damage`` copies the whole buffer, payload included)."""
+        front, back = self.flat[:self.start], self.flat[self.start + self.nbytes:]
+        return bool((front == value).all()) and bool((back == value).all())
+
     def damage(self, value):
         return guard_damage(self.flat.cpu(), self.start, self.nbytes, value)
 

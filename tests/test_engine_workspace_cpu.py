@@ -41,6 +41,23 @@ def test_guard_checker_reports_one_flipped_byte_at_each_end_of_each_guard(value)
     assert buf.damage(value) == []
 
 
+def test_the_in_place_guard_check_agrees_with_the_guard_checker():
+    """guards_intact (no copy of the payload; what the far engine cases use) sees one flipped byte at either end of either guard
+    and nothing inside the payload; fill_in_steps is fill."""
+    buf = W.GuardedBytes(1000, "cpu")
+    buf.resize(744)
+    total, start, end = buf.flat.numel(), buf.start, buf.start + 744
+    for index in (0, start - 1, end, total - 1):
+        buf.fill_in_steps(0x3C, step=4096)
+        assert buf.untouched(0x3C) and buf.guards_intact(0x3C) and buf.damage(0x3C) == []
+        buf.flat[index] = 0x3D
+        assert not buf.guards_intact(0x3C) and len(buf.damage(0x3C)) == 1, index
+    buf.fill_in_steps(0xFF, step=7)
+    buf.flat[start] = 0
+    buf.flat[end - 1] = 0
+    assert buf.guards_intact(0xFF) and not buf.guards_intact(0x3C)
+
+
 def test_comparer_reports_one_differing_bit():
     a = torch.randn(3, 128, generator=torch.Generator().manual_seed(0))
     assert W.differing_bits(a, a.clone()) == 0

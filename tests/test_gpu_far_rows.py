@@ -35,14 +35,11 @@ from tests import far_rows as F
 from tests import gemm_reference as G
 from tests import split_f16_reference as S
 from tests import vit_ops_reference as R
-from tests.helpers import PATTERN
+from tests.far_checks import GUARD, SCRATCH, STEP, Filler, Region, _bits, _pattern_count, _poison, _same, _walk  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 DT = {"float16": torch.float16, "bfloat16": torch.bfloat16, "float32": torch.float32}
-STEP = 1 << 27                   # elements per torch call on a large buffer
-SCRATCH = 1 << 30                # bytes of a chunk's scratch operand
-GUARD = 1 << 14                  # elements of a guard band (a multiple of 128: the payload keeps the allocation's alignment)
 TAIL = 19                        # rows the ragged launch leaves out
 
 # case -> (wall seconds, peak GB allocated), first run on an MI355X; never an input to a check
@@ -84,83 +81,6 @@ def env():
 def _free():
     yield
     torch.cuda.empty_cache()
-
-
-def _bits(t):
-    return t.view({2: torch.int16, 4: torch.int32}[t.element_size()])
-
-
-def _poison(t):
-    """The NaN pattern into a contiguous tensor of any size, STEP elements per call."""
-    flat = t.view(-1)
-    for o in range(0, flat.numel(), STEP):
-        _bits(flat[o:o + STEP]).fill_(PATTERN[t.element_size()])
-    return t
-
-
-def _pattern_count(t):
-    flat, n = t.view(-1), 0
-    for o in range(0, flat.numel(), STEP):
-        n += int((_bits(flat[o:o + STEP]) == PATTERN[t.element_size()]).sum())
-    return n
-
-
-def _same(x, y):
-    """x and y (contiguous, below 2^31 elements) hold the same bits."""
-    return x.shape == y.shape and x.dtype == y.dtype and torch.equal(_bits(x), _bits(y))
-
-
-class Region:
-    """Consecutive dense [rows, width] segments of one type between two guard bands, everything filled with the NaN pattern."""
-
-    def __init__(self, dev, dtype, *shapes):
-        numel = sum(r * w for r, w in shapes)
-        self.flat = _poison(torch.empty(numel + 2 * GUARD, dtype=dtype, device=dev))
-        self.parts, off = [], GUARD
-        for r, w in shapes:
-            self.parts.append(self.flat[off:off + r * w].view(r, w))
-            off += r * w
-        self.t = self.parts[0]
-        assert self.t.data_ptr() % 16 == 0
-
-    def guards_intact(self):
-        want = PATTERN[self.flat.element_size()]
-        return bool((_bits(self.flat[:GUARD]) == want).all()) and bool((_bits(self.flat[-GUARD:]) == want).all())
-
-
-class Filler:
-    """Seeded normal values for a [rows, width] buffer, made on the device in chunks of `step` rows; any rows can be made again."""
-
-    def __init__(self, dev, dtype, rows, width, seed, scale=1.0, shift=0.0):
-        self.dev, self.dtype, self.total, self.width, self.seed, self.scale, self.shift = dev, dtype, rows, width, seed, scale, shift
-        self.step = max(256, STEP // width // 256 * 256)
-
-    def chunk(self, ci):
-        n = min(self.step, self.total - ci * self.step)
-        g = torch.Generator(device=self.dev).manual_seed(self.seed * 1000003 + ci)
-        x = torch.randn(n, self.width, generator=g, device=self.dev, dtype=torch.float32)
-        return (x * self.scale + self.shift).to(self.dtype)
-
-    def chunks(self):
-        for ci in range(-(-self.total // self.step)):
-            yield ci * self.step, min(self.total, (ci + 1) * self.step), ci
-
-    def fill(self, t):
-        for r0, r1, ci in self.chunks():
-            t[r0:r1].copy_(self.chunk(ci))
-
-    def unchanged(self, t):
-        return all(_same(t[r0:r1], self.chunk(ci)) for r0, r1, ci in self.chunks())
-
-    def rows(self, r0, r1):
-        parts = [self.chunk(ci)[max(r0, c0) - c0:min(r1, c1) - c0] for c0, c1, ci in self.chunks() if c0 < r1 and r0 < c1]
-        return torch.cat(parts) if len(parts) > 1 else parts[0].clone()
-
-
-def _walk(rows, unit_rows, row_bytes):
-    """(r0, r1) chunks of whole units (256 rows, an image) whose widest operand stays within SCRATCH bytes."""
-    per = max(1, SCRATCH // (row_bytes * unit_rows)) * unit_rows
-    return [(r0, min(rows, r0 + per)) for r0 in range(0, rows, per)]
 
 
 def _report(case, t0, extra=""):
