@@ -126,6 +126,12 @@ SIGNATURES = {
     "ap_host_jpeg_probe": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ap_host_jpeg_coefficients": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]),
     "ap_jpeg_decode_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ap_jpeg_stream_header_bytes": (C.c_size_t, []),
+    "ap_host_jpeg_stream_bound": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_size_t)]),
+    "ap_host_jpeg_streams": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_char_p), C.c_int, C.c_int,
+                                       C.c_int]),
+    "ap_jpeg_entropy_decode_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_int, C.c_void_p]),
     "ap_host_format_passports": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_void_p, C.c_int]),
     "ap_host_gather_tiles": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_size_t]),
     "ap_host_synth_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
@@ -308,6 +314,9 @@ SIGNATURES = {
     "ap_host_tiff_tile_present": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "ap_host_tiff_read_patches": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ap_host_tiff_tile_coefficients": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "ap_host_tiff_max_tile_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "ap_host_tiff_tile_streams": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.POINTER(C.c_size_t)]),
     "ap_gather_patches": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p]),
 }

@@ -251,6 +251,42 @@ class SynthWSI(IWSI):
         _lib.check(code, "ap_host_jpeg_coefficients")
         return True
 
+    def jpeg_stream_bound(self, rows, tile_side: int) -> Optional[int]:
+        """Optional IWSI capability beside ``jpeg_coefficient_sampling``, switched on by ATLASPATCH_JPEG_ENTROPY_DEVICE=1 on top of
+        ATLASPATCH_JPEG_DEVICE=1: the arena bytes one tile of this slide's JPEG store can need when its compressed stream crosses the
+        ring (``read_streams_into``) -- the store's largest file size, rounded up to 16, found without reading a tile -- else None."""
+        from ...utils.env import env_flag
+        self._ensure_loaded()
+        if self.jpeg_dir is None or not env_flag("ATLASPATCH_JPEG_DEVICE") or not env_flag("ATLASPATCH_JPEG_ENTROPY_DEVICE"):
+            return None
+        bound = getattr(self, "_jpeg_stream_bound", None)
+        if bound is None:
+            with os.scandir(self.jpeg_dir) as entries:
+                most = max((e.stat().st_size for e in entries if e.name.endswith(".jpg")), default=0)
+            bound = self._jpeg_stream_bound = (most + 15) // 16 * 16
+        return bound or None
+
+    def read_streams_into(self, rows, descs_ptr: int, arena_ptr: int, arena_cap: int, tile_side: int, sampling: int) -> Optional[int]:
+        """Stage the JPEG tiles of ``rows`` as stream descriptors at ``descs_ptr`` and unstuffed payloads in the arena at ``arena_ptr``
+        (``arena_cap`` bytes) in ONE call outside the interpreter lock (``ap_host_jpeg_streams``: no libjpeg, one pass over the bytes);
+        returns the arena bytes used, or None: a tile the store lacks, a progressive tile, restart markers, another sampling or size, a
+        side that is no multiple of the MCU size, or an arena that would overflow.  The caller then asks the next route."""
+        import ctypes as C
+        from ... import _lib
+        self._ensure_loaded()
+        if self.jpeg_dir is None or not rows or common_level(rows, tile_side) != 0:
+            return None
+        files = [os.path.join(self.jpeg_dir, f"{int(x)}_{int(y)}_{int(rw)}.jpg") for x, y, rw, rh, lv in rows]
+        if not all(os.path.exists(f) for f in files):
+            return None
+        arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
+        used = C.c_size_t()
+        code = _lib.load().ap_host_jpeg_streams(descs_ptr, arena_ptr, int(arena_cap), C.byref(used), arr, len(files), tile_side, int(sampling))
+        if code == _lib.AP_ERR_INVALID:
+            return None
+        _lib.check(code, "ap_host_jpeg_streams")
+        return int(used.value)
+
     def get_size(self, lv: int = 0) -> Tuple[int, int]:
         self._ensure_loaded()
         return self.dims[lv]

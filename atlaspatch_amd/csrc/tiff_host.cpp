@@ -22,6 +22,7 @@
 #include "ap_common.h"
 #include "jpeg_host.h"
 #include "jpeg_slot.h"
+#include "jpeg_stream.h"
 
 namespace {
 
@@ -442,6 +443,59 @@ extern "C" int ap_host_tiff_tile_coefficients(const ap_tiff* slide, int level, c
             ap::set_error("ap_host_tiff_tile_coefficients: level %d tile (%lld, %lld): %s", level, tx, ty, why);
             return rc;
         }
+    }
+    return AP_OK;
+}
+
+extern "C" size_t ap_host_tiff_max_tile_bytes(const ap_tiff* slide, int level) {
+    if (!slide || level < 0 || (size_t)level >= slide->levels.size()) return 0;
+    uint64_t most = 0;
+    for (uint64_t c : slide->levels[(size_t)level].cnt) most = std::max(most, c);
+    return (size_t)((most + 15) & ~(uint64_t)15);
+}
+
+extern "C" int ap_host_tiff_tile_streams(const ap_tiff* slide, int level, const int32_t* tile_ids, int m, void* descs, void* arena,
+                                         size_t arena_cap, size_t* arena_used) {
+    AP_REQUIRE(slide && arena_used && (m == 0 || (tile_ids && descs && arena)) && m >= 0, "ap_host_tiff_tile_streams: bad arguments");
+    AP_REQUIRE((((uintptr_t)arena | (uintptr_t)descs) & 15) == 0, "ap_host_tiff_tile_streams: descs and arena must be 16-byte aligned");
+    AP_REQUIRE(level >= 0 && (size_t)level < slide->levels.size(), "ap_host_tiff_tile_streams: level %d of %zu", level, slide->levels.size());
+    const Level& lv = slide->levels[(size_t)level];
+    AP_REQUIRE(lv.sampling >= 0, "ap_host_tiff_tile_streams: level %d is outside the device decoder's subset", level);
+    size_t used = 0;
+    *arena_used = 0;
+    ap::JpegStreamTables tables;
+    char twhy[200] = "";
+    if (ap::jpeg_stream_tables(lv.tables.data(), lv.tables.size(), &tables, twhy, sizeof(twhy)) != AP_OK) {
+        ap::set_error("ap_host_tiff_tile_streams: level %d: %s", level, twhy);
+        return AP_ERR_INVALID;
+    }
+    for (int i = 0; i < m; ++i) {
+        const int64_t id = tile_ids[i];
+        AP_REQUIRE(id >= 0 && (uint64_t)id < lv.cnt.size(), "ap_host_tiff_tile_streams: tile id %lld of %zu", (long long)id, lv.cnt.size());
+        const long long tx = (long long)((uint64_t)id % lv.tx), ty = (long long)((uint64_t)id / lv.tx);
+        AP_REQUIRE(lv.cnt[(size_t)id], "ap_host_tiff_tile_streams: level %d tile (%lld, %lld) is missing", level, tx, ty);
+        char why[200] = "";
+        int rc = AP_ERR_INVALID;
+        // the tile's bytes go straight into the arena, where its payload will start; the unstuffing pass then runs in place
+        uint64_t off = lv.off[(size_t)id], left = lv.cnt[(size_t)id];
+        unsigned char* at = (unsigned char*)arena + used;
+        if (left > arena_cap - used) snprintf(why, sizeof(why), "the arena would overflow");
+        else {
+            unsigned char* p = at;
+            while (left) {
+                const ssize_t got = pread(slide->fd, p, (size_t)left, (off_t)off);
+                if (got <= 0) break;
+                p += got; off += (uint64_t)got; left -= (uint64_t)got;
+            }
+            if (left) snprintf(why, sizeof(why), "short read");
+            else rc = ap::jpeg_stream_stage(&tables, at, (size_t)lv.cnt[(size_t)id], (int)lv.tw, lv.sampling, (ap::JpegStreamDesc*)descs + i, (unsigned char*)arena, arena_cap, &used,
+                                            why, sizeof(why));
+        }
+        if (rc != AP_OK) {
+            ap::set_error("ap_host_tiff_tile_streams: level %d tile (%lld, %lld): %s", level, tx, ty, why);
+            return rc;
+        }
+        *arena_used = used;
     }
     return AP_OK;
 }

@@ -27,7 +27,7 @@ from typing import Callable, Sequence
 import numpy as np
 import torch
 
-from .tile_routes import JPEG_TILES, TIFF_TILES, PixelRoute  # noqa: F401 -- the counters are read from here
+from .tile_routes import JPEG_STREAM_TILES, JPEG_TILES, TIFF_STREAM_TILES, TIFF_TILES, PixelRoute, batches_with_rows  # noqa: F401 -- the counters are read from here
 
 
 def _cpu_list(text: str) -> list:
@@ -191,7 +191,7 @@ class TileRing:
         longest = max(hi - lo for lo, hi in bounds)
         active = [r for r in (*routes, PixelRoute(read_tile, read_chunk)) if r.prepare(self, longest)]
 
-        def fill(slot: int, b: int):
+        def fill(slot: int, b: int, active: list):
             lo, hi = bounds[b]
             count = hi - lo
             chunk = max(1, -(-count // (4 * self.workers)))          # a few tasks per worker, not one per tile
@@ -206,59 +206,81 @@ class TileRing:
 
             return [self.pool.submit(some, s) for s in range(0, count, chunk)], count, chunk
 
-        pending = {}
-        try:
-            for b in range(min(nb, self.slots)):         # prime the ring
-                if self.free_events[b % self.slots] is not None:
-                    self.free_events[b % self.slots].synchronize()
-                    self.free_events[b % self.slots] = None
-                pending[b] = fill(b % self.slots, b)
-            for b in range(nb):
-                slot = b % self.slots
-                tasks, count, chunk = pending[b]
-                runs = merge_runs([t.result() for t in tasks], count, chunk)
-                del pending[b]
-                with torch.cuda.stream(self.copy_stream):
-                    if self.free_events[slot] is not None:           # device slots: the forward (and decode) that read them is done
-                        self.copy_stream.wait_event(self.free_events[slot])
+        def drive(order: list, active: list) -> None:
+            """The batches ``order`` through the ring, in that order, over the routes ``active``; returns with the device still busy."""
+            pending = {}
+            try:
+                for k in range(min(len(order), self.slots)):     # prime the ring
+                    if self.free_events[k % self.slots] is not None:
+                        self.free_events[k % self.slots].synchronize()
+                        self.free_events[k % self.slots] = None
+                    pending[k] = fill(k % self.slots, order[k], active)
+                for k, b in enumerate(order):
+                    slot = k % self.slots
+                    tasks, count, chunk = pending[k]
+                    runs = merge_runs([t.result() for t in tasks], count, chunk)
+                    del pending[k]
+                    with torch.cuda.stream(self.copy_stream):
+                        if self.free_events[slot] is not None:           # device slots: the forward (and decode) that read them is done
+                            self.copy_stream.wait_event(self.free_events[slot])
+                        for start, stop, route, token in runs:
+                            route.upload(slot, start, stop, token)
+                        copied = torch.cuda.Event()
+                        copied.record(self.copy_stream)
+                    compute.wait_event(copied)
+                    for route in checked:
+                        route.row0 = bounds[b][0]
                     for start, stop, route, token in runs:
-                        route.upload(slot, start, stop, token)
-                    copied = torch.cuda.Event()
-                    copied.record(self.copy_stream)
-                compute.wait_event(copied)
-                for start, stop, route, token in runs:
-                    for earlier in active[:active.index(route)]:     # the routes that were asked before it and refused
-                        earlier.refused(stop - start)
-                    route.decode(slot, start, stop, token, compute)
-                pinned_read = None
-                if any(route.decode_reads_pinned for _, _, route, _ in runs):
-                    pinned_read = torch.cuda.Event()
-                    pinned_read.record(compute)
-                forward(self.dev[slot][:count], out_dev[slot][:count])
-                lo = bounds[b][0]
-                out_host[lo:lo + count].copy_(out_dev[slot][:count], non_blocking=True)
-                done = torch.cuda.Event()
-                done.record(compute)
-                self.free_events[slot] = done
-                nxt = b + self.slots
-                if nxt < nb:
-                    # the pinned host slot may be refilled as soon as its H2D copy has completed; the device slot is
-                    # protected by the copy stream waiting on `done` above, so the CPU never waits for a forward
-                    copied.synchronize()
-                    if pinned_read is not None:                      # ... and pinned memory a decode read, once that decode has run
-                        pinned_read.synchronize()
-                    pending[nxt] = fill(slot, nxt)
-        except BaseException:
-            # a tile source failed (or the forward did): let the decode tasks that are still filling pinned slots
-            # finish before the ring is reused for the next slide, then drain the device
-            for tasks, *_ in pending.values():
-                for t in tasks:
-                    try:
-                        t.result()
-                    except Exception:  # noqa: BLE001
-                        pass
+                        for earlier in active[:active.index(route)]:     # the routes that were asked before it and refused
+                            earlier.refused(stop - start)
+                        route.decode(slot, start, stop, token, compute)
+                    pinned_read = None
+                    if any(route.decode_reads_pinned for _, _, route, _ in runs):
+                        pinned_read = torch.cuda.Event()
+                        pinned_read.record(compute)
+                    forward(self.dev[slot][:count], out_dev[slot][:count])
+                    lo = bounds[b][0]
+                    out_host[lo:lo + count].copy_(out_dev[slot][:count], non_blocking=True)
+                    done = torch.cuda.Event()
+                    done.record(compute)
+                    self.free_events[slot] = done
+                    nxt = k + self.slots
+                    if nxt < len(order):
+                        # the pinned host slot may be refilled as soon as its H2D copy has completed; the device slot is
+                        # protected by the copy stream waiting on `done` above, so the CPU never waits for a forward
+                        copied.synchronize()
+                        if pinned_read is not None:                      # ... and pinned memory a decode read, once that decode has run
+                            pinned_read.synchronize()
+                        pending[nxt] = fill(slot, order[nxt], active)
+            except BaseException:
+                # a tile source failed (or the forward did): let the decode tasks that are still filling pinned slots
+                # finish before the ring is reused for the next slide, then drain the device
+                for tasks, *_ in pending.values():
+                    for t in tasks:
+                        try:
+                            t.result()
+                        except Exception:  # noqa: BLE001
+                            pass
+                torch.cuda.synchronize(self.device)
+                raise
+
+        # routes whose device decode can flag a tile after its chunk was accepted (the stream routes; none unless their switch is set)
+        checked = [r for r in active if hasattr(r, "flagged_rows")]
+        for route in checked:
+            route.begin(n_total)
+        drive(list(range(nb)), active)
+        if checked:
+            # damage inside a tile's entropy-coded data is seen on the device only: every batch that holds a flagged tile runs again
+            # without the route that flagged it, and its features overwrite the same out_host rows; a tile that is damaged for every
+            # route ends where it always ended, in the host route
             torch.cuda.synchronize(self.device)
-            raise
+            flagged = [(r, r.flagged_rows()) for r in checked]
+            again = sorted({b for _, rows in flagged for b in batches_with_rows(rows, bounds)})
+            if again:
+                for route, rows in flagged:
+                    if rows:
+                        route.reran(sum(bounds[b][1] - bounds[b][0] for b in batches_with_rows(rows, bounds)))
+                drive(again, [r for r in active if not any(r is f and rows for f, rows in flagged)])
         torch.cuda.synchronize(self.device)
         return out_host[:n_total].numpy().copy() if own else out_host[:n_total].numpy()
 

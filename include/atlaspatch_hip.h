@@ -146,6 +146,52 @@ int ap_host_jpeg_coefficients(void* slots, const char* const* paths, int n, int 
  * an unknown sampling; n == 0 is AP_OK. */
 int ap_jpeg_decode_tiles(const void* slots, int n, int side, int sampling, uint8_t* rgb, ap_stream_t stream);
 
+/* ---- K0: the Huffman decode on the device as well (additive: AP_ABI_VERSION stays 20) ------------------------------------
+ * The host only reads a tile's bytes and walks them once; the ring carries the compressed stream.  Per tile a DESCRIPTOR of
+ * ap_jpeg_stream_header_bytes() = 2048 bytes (little endian, 16-byte aligned; csrc/jpeg_stream.h is the same layout as a struct):
+ *   bytes    0 ..  383   uint16 quant[3][64], natural order, the components' own order (a slot's first 384 bytes)
+ *   bytes  384 ..  447   uint8 huff_counts[4][16]: codes of length 1 .. 16 of the tables DC0, DC1, AC0, AC1 (raw DHT form)
+ *   bytes  448 .. 1471   uint8 huff_symbols[4][256]
+ *   bytes 1472 .. 1479   uint8 dc_sel[3], 0, ac_sel[3], 0: each component's table selectors
+ *   bytes 1480 .. 1487   uint32 ncomp, uint32 payload_bytes
+ *   bytes 1488 .. 1495   uint64 payload_offset into the arena, a multiple of 16
+ *   bytes 1496 .. 2047   zero
+ * and its PAYLOAD in a packed ARENA: the entropy-coded segment from the end of the SOS header to the marker that ends it (or
+ * the end of the stream), byte stuffing removed, 16-byte aligned, zero filled to the next multiple of 16; whatever follows the
+ * terminating marker is ignored, as libjpeg ignores it.
+ * The staging functions parse SOI, DQT, DHT, SOF0, DRI, SOS and the APPn / COM segments they skip with code of their own (no
+ * libjpeg), every segment length checked against the buffer.  Admitted: the subset of ap_host_jpeg_coefficients restricted to
+ * baseline SOF0, one scan with every component in frame order, a side that is a multiple of the MCU size (8, or 16 along a
+ * subsampled axis) and <= 976, no restart interval and no RSTn marker, Huffman tables 0 / 1 that exist and form a canonical code
+ * without over-subscription.  Everything else is refused with AP_ERR_INVALID and the reason; the refusal contract is the one of
+ * ap_host_jpeg_coefficients: the tiles before the first refused one are complete (*arena_used covers them), the descriptors
+ * from it on are untouched.  A tile that would overflow the arena is refused too.  Host only, no device work. */
+size_t ap_jpeg_stream_header_bytes(void);
+/* bytes: the largest file size among paths, rounded up to 16: n times that is an arena no n of these tiles overflow. */
+int ap_host_jpeg_stream_bound(const char* const* paths, int n, size_t* bytes);
+/* The JPEG tile store.  descs: n descriptors; arena (16-byte aligned, arena_cap bytes): each file is read straight to where its
+ * payload will start and unstuffed in place; *arena_used: the bytes of the arena that hold payloads afterwards. */
+int ap_host_jpeg_streams(void* descs, void* arena, size_t arena_cap, size_t* arena_used, const char* const* paths, int n, int side,
+                         int sampling);
+/* Device: descs (n descriptors) and arena (arena_bytes bytes), both device, 16-byte aligned -> slots: exactly the coefficient
+ * slots of ap_jpeg_slot_bytes(side, sampling) pitch that ap_host_jpeg_coefficients fills (quantisers copied in, every coefficient
+ * the stream does not code zero, DC values accumulated; bytes 384 .. 511 are padding and unspecified), so ap_jpeg_decode_tiles and
+ * ap_gather_patches run unchanged behind it.  status (device int32 [n]): 0, or the reason the tile's slot is NOT to be used:
+ * AP_JPEG_ENTROPY_BAD_CODE (bits no code matches), _BAD_INDEX (a run past coefficient 63: libjpeg folds it, this decoder flags it),
+ * _EXHAUSTED (bits ran out before the last block), _LEFTOVER (whole bytes left after it), _BAD_DESCRIPTOR (a field outside its
+ * bounds: component count, selectors, tables, or a payload that does not lie inside arena_bytes).  One workgroup per tile;
+ * self-synchronising parallel Huffman decode over subsequences of subsequence_bits (0 = the default 1024; else a multiple of 32
+ * in [32, 2^20]; a payload of more than 4096 subsequences gets longer ones).  On any input it reads nothing beyond n descriptors
+ * and arena_bytes and writes nothing beyond n slots and n status words.  AP_ERR_INVALID for null or misaligned pointers, n < 0, a
+ * side above 976 or no multiple of the MCU size, an unknown sampling, a bad subsequence_bits; n == 0 is AP_OK. */
+#define AP_JPEG_ENTROPY_BAD_CODE 1
+#define AP_JPEG_ENTROPY_BAD_INDEX 2
+#define AP_JPEG_ENTROPY_EXHAUSTED 3
+#define AP_JPEG_ENTROPY_LEFTOVER 4
+#define AP_JPEG_ENTROPY_BAD_DESCRIPTOR 5
+int ap_jpeg_entropy_decode_tiles(const void* descs, const void* arena, size_t arena_bytes, int n, int side, int sampling, void* slots,
+                                 int32_t* status, int subsequence_bits, ap_stream_t stream);
+
 /* The same for a slide OpenSlide can open (the reference's production tile source): core/wsi/openslide_wsi.py:184-205 reads
  * one region per call in the interpreter -- openslide-python's read_region (premultiplied ARGB -> RGBA in its C helper, a
  * PIL image) + .convert("RGB") + np.array.  ap_host_openslide_read_tiles reads n regions of w x h pixels at `level` with
@@ -199,6 +245,13 @@ int ap_host_tiff_read_patches(const ap_tiff* slide, int level, const int64_t* xy
  * into consecutive ap_jpeg_slot_bytes(tile_w, sampling) slots, the slot format and the refusals of ap_host_jpeg_coefficients.
  * A missing tile is refused too: the caller marks it absent in its gather plan instead of asking for it. */
 int ap_host_tiff_tile_coefficients(const ap_tiff* slide, int level, const int32_t* tile_ids, int m, void* slots);
+/* The stream route, the twin of ap_host_tiff_tile_coefficients for ap_jpeg_entropy_decode_tiles: every tile is read by pread
+ * straight into the arena and staged as ap_host_jpeg_streams stages a file, the level's JPEGTables parsed once per call.
+ * ap_host_tiff_max_tile_bytes: the level's largest TileByteCounts entry rounded up to 16 (0 on bad arguments): m times that is an
+ * arena no m tiles of the level overflow. */
+size_t ap_host_tiff_max_tile_bytes(const ap_tiff* slide, int level);
+int ap_host_tiff_tile_streams(const ap_tiff* slide, int level, const int32_t* tile_ids, int m, void* descs, void* arena,
+                              size_t arena_cap, size_t* arena_used);
 
 /* Device: patches that do not sit on the tile grid, assembled from decoded tiles (the output of ap_jpeg_decode_tiles).
  *   tiles  uint8 [m, ts, ts, 3]      device, 16-byte aligned
