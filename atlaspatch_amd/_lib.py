@@ -17,6 +17,7 @@ AP_ERR_CAPACITY = -6
 AP_ERR_UNSUPPORTED = -4
 AP_ERR_INVALID = -1
 AP_JPEG_GRAY, AP_JPEG_444, AP_JPEG_422, AP_JPEG_420 = 0, 1, 2, 3     # sampling of a JPEG coefficient slot
+AP_JPEG_RGB = 4                  # three 1 x 1 components coded as R, G, B (no colour transform); device side: the *_ex entries take it
 
 # Stream capture (the SAM2 hipGraph) must not overlap synchronous HIP calls on the legacy stream from other threads (the
 # encoder built on a side thread uploads weights with hipMemcpy): both sides hold this lock for their critical section.
@@ -123,15 +124,19 @@ SIGNATURES = {
     "ap_host_inflate_tiles": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_size_t]),
     "ap_host_decode_jpeg_tiles": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int]),
     "ap_jpeg_slot_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ap_jpeg_slot_bytes_ex": (C.c_size_t, [C.c_int, C.c_int]),
     "ap_host_jpeg_probe": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ap_host_jpeg_coefficients": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]),
     "ap_jpeg_decode_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ap_jpeg_decode_tiles_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ap_jpeg_stream_header_bytes": (C.c_size_t, []),
     "ap_host_jpeg_stream_bound": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_size_t)]),
     "ap_host_jpeg_streams": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_char_p), C.c_int, C.c_int,
                                        C.c_int]),
     "ap_jpeg_entropy_decode_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                C.c_int, C.c_void_p]),
+    "ap_jpeg_entropy_decode_tiles_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_int, C.c_void_p]),
     "ap_host_format_passports": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_void_p, C.c_int]),
     "ap_host_gather_tiles": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_size_t]),
     "ap_host_synth_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,

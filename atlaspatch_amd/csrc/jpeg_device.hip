@@ -2,7 +2,9 @@
 //
 // libjpeg's JDCT_ISLOW decode with fancy upsampling, restated in integers: dequantise -> 8 x 8 inverse DCT (columns, then
 // rows, 13-bit constants) -> range limit -> h2v1 / h2v2 triangle upsampling of the chroma planes -> YCbCr -> RGB.  Bit-equal
-// to libjpeg-turbo (and so to Pillow) on every baseline stream the host reader (jpeg_host.cpp) admits.
+// to libjpeg-turbo (and so to Pillow) on every baseline stream the host reader (jpeg_host.cpp) admits.  AP_JPEG_RGB is the 4:4:4
+// form without the last stage: three 1 x 1 components that ARE R, G, B (a TIFF level tagged Photometric 2, a stream libjpeg infers as
+// RGB) go through IDCT, + 128 and the range limit per component and are interleaved as they are, which is what libjpeg's copy does.
 //
 // One workgroup = one tile x one band of 16 luma rows.  The band's blocks go through LDS in chunks of 64:
 //   A  16-byte loads of coefficient rows and quantiser rows, product -> d[block][64] (int32)
@@ -92,6 +94,8 @@ __global__ __launch_bounds__(256) void jpeg_decode_kernel(const DecodeArgs p) {
     const int tile = blockIdx.x / p.bands, band = blockIdx.x - tile * p.bands;
     const uint8_t* const slot = p.slots + (size_t)tile * p.slot_bytes;
     constexpr bool k420 = SAMPLING == AP_JPEG_420;
+    constexpr bool kRgb = SAMPLING == AP_JPEG_RGB;          // planes 0, 1, 2 hold R, G, B: the 4:4:4 reads, no colour transform
+    constexpr bool kFull = SAMPLING == AP_JPEG_444 || kRgb; // "chroma" planes at full resolution
     constexpr int kComps = SAMPLING == AP_JPEG_GRAY ? 1 : 3;
 
     // the band's block rows per component: [br0, br0 + nrows); rowbase = the block row that sits at LDS plane row 0
@@ -186,7 +190,7 @@ __global__ __launch_bounds__(256) void jpeg_decode_kernel(const DecodeArgs p) {
             const int ly = u / gpr, x0 = (u - ly * gpr) << 4;
             const u32x4 yv = *(const u32x4*)(planeY + ly * p.py + x0);
             int cb[16], cr[16];
-            if (SAMPLING == AP_JPEG_444) {
+            if (kFull) {
                 const u32x4 bv = *(const u32x4*)(cbp + ly * p.pc + x0), rv = *(const u32x4*)(crp + ly * p.pc + x0);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) { cb[i] = byte_of(bv, i); cr[i] = byte_of(rv, i); }
@@ -232,7 +236,8 @@ __global__ __launch_bounds__(256) void jpeg_decode_kernel(const DecodeArgs p) {
             for (int i = 0; i < 16; ++i) {
                 const int y = byte_of(yv, i);
                 int R = y, Gc = y, B = y;
-                if (SAMPLING != AP_JPEG_GRAY) ycc_to_rgb(y, cb[i] - 128, cr[i] - 128, R, Gc, B);
+                if (kRgb) { Gc = cb[i]; B = cr[i]; }
+                else if (SAMPLING != AP_JPEG_GRAY) ycc_to_rgb(y, cb[i] - 128, cr[i] - 128, R, Gc, B);
                 pack_rgb(w, i, R, Gc, B);
             }
             u32x4* o = (u32x4*)(p.rgb + (size_t)(g0 + (long long)ly * p.side + x0) * 3);
@@ -262,7 +267,7 @@ __global__ __launch_bounds__(256) void jpeg_decode_kernel(const DecodeArgs p) {
                     R = Gc = B = y;
                 } else {
                     int cb, cr;
-                    if (SAMPLING == AP_JPEG_444) {
+                    if (kFull) {
                         cb = cbp[ly * p.pc + x];
                         cr = crp[ly * p.pc + x];
                     } else if (SAMPLING == AP_JPEG_422) {
@@ -299,7 +304,8 @@ __global__ __launch_bounds__(256) void jpeg_decode_kernel(const DecodeArgs p) {
                             }
                         }
                     }
-                    ycc_to_rgb(y, cb - 128, cr - 128, R, Gc, B);
+                    if (kRgb) { R = y; Gc = cb; B = cr; }
+                    else ycc_to_rgb(y, cb - 128, cr - 128, R, Gc, B);
                 }
                 if (!full) {
                     uint8_t* o = p.rgb + (size_t)(g + i) * 3;
@@ -321,7 +327,7 @@ __global__ __launch_bounds__(256) void jpeg_decode_kernel(const DecodeArgs p) {
 }  // namespace
 }  // namespace ap
 
-extern "C" int ap_jpeg_decode_tiles(const void* slots, int n, int side, int sampling, uint8_t* rgb, ap_stream_t stream) {
+extern "C" int ap_jpeg_decode_tiles_ex(const void* slots, int n, int side, int sampling, uint8_t* rgb, ap_stream_t stream) {
     using namespace ap;
     AP_REQUIRE(slots && rgb, "ap_jpeg_decode_tiles: null pointer");
     AP_REQUIRE(n >= 0 && side > 0, "ap_jpeg_decode_tiles: bad n %d or side %d", n, side);
@@ -352,8 +358,15 @@ extern "C" int ap_jpeg_decode_tiles(const void* slots, int n, int side, int samp
         case AP_JPEG_GRAY: hipLaunchKernelGGL(jpeg_decode_kernel<AP_JPEG_GRAY>, grid, block, lds, s, a); break;
         case AP_JPEG_444: hipLaunchKernelGGL(jpeg_decode_kernel<AP_JPEG_444>, grid, block, lds, s, a); break;
         case AP_JPEG_422: hipLaunchKernelGGL(jpeg_decode_kernel<AP_JPEG_422>, grid, block, lds, s, a); break;
+        case AP_JPEG_RGB: hipLaunchKernelGGL(jpeg_decode_kernel<AP_JPEG_RGB>, grid, block, lds, s, a); break;
         default: hipLaunchKernelGGL(jpeg_decode_kernel<AP_JPEG_420>, grid, block, lds, s, a); break;
     }
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
+}
+
+// the four codes this entry was published with; AP_JPEG_RGB stays an unknown sampling here
+extern "C" int ap_jpeg_decode_tiles(const void* slots, int n, int side, int sampling, uint8_t* rgb, ap_stream_t stream) {
+    AP_REQUIRE(sampling != AP_JPEG_RGB, "ap_jpeg_decode_tiles: bad side %d or sampling %d (AP_JPEG_RGB: ap_jpeg_decode_tiles_ex)", side, sampling);
+    return ap_jpeg_decode_tiles_ex(slots, n, side, sampling, rgb, stream);
 }

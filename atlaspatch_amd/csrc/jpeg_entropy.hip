@@ -62,8 +62,8 @@ __global__ __launch_bounds__(kEntropyLanes) void jpeg_entropy_kernel(EntropyArgs
 }  // namespace
 }  // namespace ap
 
-extern "C" int ap_jpeg_entropy_decode_tiles(const void* descs, const void* arena, size_t arena_bytes, int n, int side, int sampling,
-                                            void* slots, int32_t* status, int subsequence_bits, ap_stream_t stream) {
+extern "C" int ap_jpeg_entropy_decode_tiles_ex(const void* descs, const void* arena, size_t arena_bytes, int n, int side, int sampling,
+                                               void* slots, int32_t* status, int subsequence_bits, ap_stream_t stream) {
     using namespace ap;
     AP_REQUIRE(descs && arena && slots && status, "ap_jpeg_entropy_decode_tiles: null pointer");
     AP_REQUIRE(n >= 0, "ap_jpeg_entropy_decode_tiles: bad n %d", n);
@@ -93,4 +93,11 @@ extern "C" int ap_jpeg_entropy_decode_tiles(const void* descs, const void* arena
     hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)n), dim3(kEntropyLanes), 0, (hipStream_t)stream, a);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
+}
+
+// the four codes this entry was published with; AP_JPEG_RGB stays an unknown sampling here
+extern "C" int ap_jpeg_entropy_decode_tiles(const void* descs, const void* arena, size_t arena_bytes, int n, int side, int sampling,
+                                            void* slots, int32_t* status, int subsequence_bits, ap_stream_t stream) {
+    AP_REQUIRE(sampling != AP_JPEG_RGB, "ap_jpeg_entropy_decode_tiles: bad side %d or sampling %d (AP_JPEG_RGB: ap_jpeg_entropy_decode_tiles_ex)", side, sampling);
+    return ap_jpeg_entropy_decode_tiles_ex(descs, arena, arena_bytes, n, side, sampling, slots, status, subsequence_bits, stream);
 }

@@ -190,8 +190,11 @@ std::once_flag g_once;
 
 // decode one in-memory JPEG into dst (rows of `stride` bytes); returns 0 or fills `why`.  `tables` (may be null): a tables-only
 // stream (TIFF's JPEGTables tag) read with jpeg_read_header(..., FALSE) in front of an abbreviated `data`, as libtiff does.
+// `colour`: ap::kJpegColourInfer leaves libjpeg's inference alone; ap::kJpegColourRgb (a TIFF level tagged Photometric 2) overrides it
+// for a three-component stream: the components are R, G, B whatever the markers say, and libjpeg copies them.
 int decode_one(const Api& api, const unsigned char* data, size_t size, int want_w, int want_h, unsigned char* dst,
-               size_t stride, char* why, size_t why_cap, const unsigned char* tables = nullptr, size_t tables_size = 0) {
+               size_t stride, char* why, size_t why_cap, const unsigned char* tables = nullptr, size_t tables_size = 0,
+               int colour = ap::kJpegColourInfer) {
     jpeg_decompress_struct c;
     ErrJmp err;
     memset(&c, 0, sizeof(c));
@@ -213,6 +216,7 @@ int decode_one(const Api& api, const unsigned char* data, size_t size, int want_
     }
     api.mem_src(&c, data, (unsigned long)size);
     if (api.read_header(&c, 1) != JPEG_HEADER_OK) { snprintf(why, why_cap, "not a JPEG stream"); api.destroy(&c); return -1; }
+    if (colour == ap::kJpegColourRgb && c.num_components == 3) c.jpeg_color_space = JCS_RGB;
     c.out_color_space = JCS_RGB;          // what PIL's convert("RGB") yields for YCbCr and greyscale streams alike
     api.start(&c);
     if ((int)c.output_width != want_w || (int)c.output_height != want_h || c.output_components != 3) {
@@ -240,10 +244,13 @@ int decode_one(const Api& api, const unsigned char* data, size_t size, int want_
 // The entropy-decoded half of a decode: header checks, then (slot != nullptr) libjpeg's Huffman decoder behind
 // jpeg_read_coefficients and a copy of every component's quantisation table and blocks into `slot` (jpeg_slot.h).  Fills
 // wh / sampling from the header; slot == nullptr stops there (ap_host_jpeg_probe).  A stream outside the device decoder's
-// subset -- baseline Huffman, 8 bit, grey or YCbCr at 4:4:4 / 4:2:2 / 4:2:0 -- or one libjpeg warned about is refused with its
-// reason in `why` and nothing written to the slot.
+// subset -- baseline Huffman, 8 bit, grey, YCbCr at 4:4:4 / 4:2:2 / 4:2:0, or RGB coded at 1 x 1 -- or one libjpeg warned about is
+// refused with its reason in `why` and nothing written to the slot.  A three-component stream is RGB coded when libjpeg infers so
+// (Adobe transform 0, or ids 'R' 'G' 'B' without a JFIF / Adobe marker) or, under ap::kJpegColourRgb, because the container says so.
+// An RGB-coded stream with a subsampled component is refused before anything else, with *sampling = ap::kJpegRgbSubsampled.
 int read_one(const Api& api, const unsigned char* data, size_t size, int wh[2], int* sampling, int want_side, int want_sampling,
-             unsigned char* slot, char* why, size_t why_cap, const unsigned char* tables = nullptr, size_t tables_size = 0) {
+             unsigned char* slot, char* why, size_t why_cap, const unsigned char* tables = nullptr, size_t tables_size = 0,
+             int colour = ap::kJpegColourInfer) {
     jpeg_decompress_struct c;
     ErrJmp err;
     memset(&c, 0, sizeof(c));
@@ -266,16 +273,26 @@ int read_one(const Api& api, const unsigned char* data, size_t size, int wh[2], 
     }
     api.mem_src(&c, data, (unsigned long)size);
     if (api.read_header(&c, 1) != JPEG_HEADER_OK) return refuse("not a JPEG stream");
+    const jpeg_component_info* comp = (const jpeg_component_info*)c.comp_info;
+    const bool rgb = comp && c.num_components == 3 && (colour == ap::kJpegColourRgb || c.jpeg_color_space == JCS_RGB);
+    if (rgb)
+        for (int ci = 0; ci < 3; ++ci)
+            if (comp[ci].h_samp_factor != 1 || comp[ci].v_samp_factor != 1) {
+                *sampling = ap::kJpegRgbSubsampled;
+                return refuse("RGB-coded stream whose component %d has sampling factors %dx%d: only 1x1 components are read", ci,
+                              comp[ci].h_samp_factor, comp[ci].v_samp_factor);
+            }
     if (c.progressive_mode) return refuse("progressive stream");
     if (c.arith_code) return refuse("arithmetic-coded stream");
     if (c.data_precision != 8) return refuse("%d-bit samples", c.data_precision);
-    const jpeg_component_info* comp = (const jpeg_component_info*)c.comp_info;
     const bool grey = c.num_components == 1 && c.jpeg_color_space == JCS_GRAYSCALE;
-    if (!comp || !(grey || (c.num_components == 3 && c.jpeg_color_space == JCS_YCbCr)))
-        return refuse("%d components in colour space %d: neither greyscale nor YCbCr", c.num_components, c.jpeg_color_space);
+    if (!comp || !(grey || rgb || (c.num_components == 3 && c.jpeg_color_space == JCS_YCbCr)))
+        return refuse("%d components in colour space %d: none of greyscale, YCbCr, RGB", c.num_components, c.jpeg_color_space);
     int found = -1;
     if (grey) {
         if (comp[0].h_samp_factor == 1 && comp[0].v_samp_factor == 1) found = AP_JPEG_GRAY;
+    } else if (rgb) {
+        found = AP_JPEG_RGB;
     } else if (comp[1].h_samp_factor == 1 && comp[1].v_samp_factor == 1 && comp[2].h_samp_factor == 1 && comp[2].v_samp_factor == 1) {
         const int h = comp[0].h_samp_factor, v = comp[0].v_samp_factor;
         found = h == 1 && v == 1 ? AP_JPEG_444 : h == 2 && v == 1 ? AP_JPEG_422 : h == 2 && v == 2 ? AP_JPEG_420 : -1;
@@ -287,6 +304,9 @@ int read_one(const Api& api, const unsigned char* data, size_t size, int wh[2], 
     wh[1] = (int)c.image_height;
     *sampling = found;
     if (!slot) { api.destroy(&c); return 0; }
+    if (found != want_sampling && (found == AP_JPEG_RGB || want_sampling == AP_JPEG_RGB))
+        return refuse("%s stream (sampling %d) asked for as %s (sampling %d)", rgb ? "RGB-coded" : grey ? "greyscale" : "YCbCr", found,
+                      want_sampling == AP_JPEG_RGB ? "RGB coded" : "greyscale / YCbCr", want_sampling);
     if (found != want_sampling) return refuse("sampling %d, expected %d", found, want_sampling);
     if (wh[0] != want_side || wh[1] != want_side) return refuse("tile is %d x %d, expected %d x %d", wh[0], wh[1], want_side, want_side);
     ap::JpegGeom g;
@@ -402,15 +422,15 @@ int jpeg_mem_ready(char* why, size_t why_cap) {
 }
 
 int jpeg_mem_pixels(const unsigned char* tables, size_t tables_size, const unsigned char* data, size_t size, int want_w, int want_h,
-                    unsigned char* dst, size_t stride, char* why, size_t why_cap) {
+                    unsigned char* dst, size_t stride, char* why, size_t why_cap, int colour) {
     if (int rc = jpeg_mem_ready(why, why_cap)) return rc;
-    return decode_one(g_api, data, size, want_w, want_h, dst, stride, why, why_cap, tables, tables_size) == 0 ? AP_OK : AP_ERR_INVALID;
+    return decode_one(g_api, data, size, want_w, want_h, dst, stride, why, why_cap, tables, tables_size, colour) == 0 ? AP_OK : AP_ERR_INVALID;
 }
 
 int jpeg_mem_coefficients(const unsigned char* tables, size_t tables_size, const unsigned char* data, size_t size, int wh[2],
-                          int* sampling, int want_side, int want_sampling, unsigned char* slot, char* why, size_t why_cap) {
+                          int* sampling, int want_side, int want_sampling, unsigned char* slot, char* why, size_t why_cap, int colour) {
     if (int rc = jpeg_mem_ready(why, why_cap)) return rc;
-    return read_one(g_api, data, size, wh, sampling, want_side, want_sampling, slot, why, why_cap, tables, tables_size) == 0
+    return read_one(g_api, data, size, wh, sampling, want_side, want_sampling, slot, why, why_cap, tables, tables_size, colour) == 0
                ? AP_OK : AP_ERR_INVALID;
 }
 
@@ -446,10 +466,13 @@ extern "C" int ap_host_decode_jpeg_tiles(void* dst, const char* const* paths, in
     return AP_OK;
 }
 
-extern "C" size_t ap_jpeg_slot_bytes(int side, int sampling) {
+extern "C" size_t ap_jpeg_slot_bytes_ex(int side, int sampling) {
     ap::JpegGeom g;
     return ap::jpeg_geom(side, sampling, &g) ? g.bytes : 0;
 }
+
+// the four codes this entry was published with; AP_JPEG_RGB stays an unknown sampling here
+extern "C" size_t ap_jpeg_slot_bytes(int side, int sampling) { return sampling == AP_JPEG_RGB ? 0 : ap_jpeg_slot_bytes_ex(side, sampling); }
 
 extern "C" int ap_host_jpeg_probe(const char* path, int* width, int* height, int* sampling) {
     AP_REQUIRE(path && width && height && sampling, "ap_host_jpeg_probe: null pointer");
@@ -474,7 +497,7 @@ extern "C" int ap_host_jpeg_probe(const char* path, int* width, int* height, int
 
 extern "C" int ap_host_jpeg_coefficients(void* slots, const char* const* paths, int n, int side, int sampling) {
     AP_REQUIRE(slots && (paths || n == 0) && n >= 0, "ap_host_jpeg_coefficients: bad arguments");
-    const size_t stride = ap_jpeg_slot_bytes(side, sampling);
+    const size_t stride = ap_jpeg_slot_bytes_ex(side, sampling);
     AP_REQUIRE(stride, "ap_host_jpeg_coefficients: bad side %d or sampling %d", side, sampling);
     std::call_once(g_once, load_api);
     if (!g_api.ok) {

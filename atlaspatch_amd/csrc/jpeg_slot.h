@@ -22,11 +22,12 @@ struct JpegGeom {
     size_t bytes;          // slot stride
 };
 
-// sampling: AP_JPEG_GRAY 0 / AP_JPEG_444 1 / AP_JPEG_422 2 / AP_JPEG_420 3
+// sampling: AP_JPEG_GRAY 0 / AP_JPEG_444 1 / AP_JPEG_422 2 / AP_JPEG_420 3 / AP_JPEG_RGB 4 (three 1 x 1 components coded as R, G, B:
+// the geometry of 4:4:4, "luma" and "chroma" then read "R" and "G, B")
 __host__ __device__ inline bool jpeg_geom(int side, int sampling, JpegGeom* g) {
-    if (side <= 0 || side > kJpegMaxSide || sampling < 0 || sampling > 3) return false;
+    if (side <= 0 || side > kJpegMaxSide || sampling < 0 || sampling > 4) return false;
     g->ncomp = sampling == 0 ? 1 : 3;
-    g->hmax = sampling >= 2 ? 2 : 1;
+    g->hmax = sampling == 2 || sampling == 3 ? 2 : 1;
     g->vmax = sampling == 3 ? 2 : 1;
     size_t off = kJpegSlotHeader;
     for (int c = 0; c < 3; ++c) {

@@ -58,7 +58,9 @@ int jpeg_stream_tables(const unsigned char* tables, size_t tables_size, JpegStre
 // stream `data`.  The payload goes to arena + *used, which must be 16-byte aligned; `data` may BE arena + *used (bytes read
 // straight into the arena: the unstuffing pass then runs in place).  AP_OK: *desc filled, *used advanced to the next multiple of 16
 // behind the payload.  AP_ERR_INVALID: refused, the reason in `why`, *desc and *used untouched.  No libjpeg, callable from any thread.
+// `colour`: jpeg_host.h's kJpegColourInfer (0) or kJpegColourRgb (1: the container says the three components are R, G, B).
 int jpeg_stream_stage(const JpegStreamTables* preset, const unsigned char* data, size_t size, int want_side, int want_sampling,
-                      JpegStreamDesc* desc, unsigned char* arena, size_t arena_cap, size_t* used, char* why, size_t why_cap);
+                      JpegStreamDesc* desc, unsigned char* arena, size_t arena_cap, size_t* used, char* why, size_t why_cap,
+                      int colour = 0);
 
 }  // namespace ap

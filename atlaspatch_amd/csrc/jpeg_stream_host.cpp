@@ -4,12 +4,14 @@
 // The input is untrusted: every segment length is checked against the buffer before a byte of the segment is read.  What is admitted
 // is the coefficient reader's subset (jpeg_host.cpp: read_one) restricted to what ap_jpeg_entropy_decode_tiles takes; everything else
 // is refused with its reason, and the caller's next route (coefficients, then pixels) takes the tile:
-//   baseline sequential Huffman (SOF0), 8 bit; one scan with every component, in frame order; greyscale, or YCbCr at 4:4:4 / 4:2:2
-//   (2x1) / 4:2:0 (2x2) with 1x1 chroma; the requested side and sampling; a side that is a multiple of the MCU size and <= 976; no
-//   restart interval and no RSTn marker; Huffman tables 0 / 1 that exist and form a canonical code the way libjpeg checks it
-//   (jdhuff.c: jpeg_make_d_derived_tbl), DC categories <= 15.
-// The colour space is inferred as libjpeg does (jdapimin.c: default_decompress_parms): JFIF -> YCbCr; Adobe transform 0 -> RGB, which
-// is refused; neither: component ids 'R' 'G' 'B' -> RGB, refused.
+//   baseline sequential Huffman (SOF0), 8 bit; one scan with every component, in frame order; greyscale, YCbCr at 4:4:4 / 4:2:2
+//   (2x1) / 4:2:0 (2x2) with 1x1 chroma, or RGB coded with three 1x1 components; the requested side and sampling; a side that is a
+//   multiple of the MCU size and <= 976; no restart interval and no RSTn marker; Huffman tables 0 / 1 that exist and form a
+//   canonical code the way libjpeg checks it (jdhuff.c: jpeg_make_d_derived_tbl), DC categories <= 15.
+// The colour space is inferred as libjpeg does (jdapimin.c: default_decompress_parms): JFIF -> YCbCr; Adobe transform 0 -> RGB;
+// neither: component ids 'R' 'G' 'B' -> RGB -- unless the container decides it (jpeg_host.h: kJpegColourRgb, a TIFF level tagged
+// Photometric 2: RGB whatever the markers say).  RGB is admitted when AP_JPEG_RGB was asked for and refused under any other code;
+// a YCbCr stream asked for as AP_JPEG_RGB is refused.
 //
 // The entropy-coded segment is walked once, memchr from FF to FF: FF 00 -> FF, FF FF -> fill, FF D0..D7 -> refused, any other marker
 // (or the end of the buffer: a truncated tile, which the device flags) ends it.  Destination <= source, so the pass runs in place when
@@ -18,6 +20,7 @@
 #include <cstdio>
 #include <cstring>
 #include "ap_common.h"
+#include "jpeg_host.h"
 #include "jpeg_slot.h"
 #include "jpeg_stream.h"
 
@@ -157,7 +160,7 @@ int jpeg_stream_tables(const unsigned char* tables, size_t tables_size, JpegStre
 }
 
 int jpeg_stream_stage(const JpegStreamTables* preset, const unsigned char* data, size_t size, int want_side, int want_sampling,
-                      JpegStreamDesc* desc, unsigned char* arena, size_t arena_cap, size_t* used, char* why, size_t why_cap) {
+                      JpegStreamDesc* desc, unsigned char* arena, size_t arena_cap, size_t* used, char* why, size_t why_cap, int colour) {
     constexpr int kInvalid = AP_ERR_INVALID;
     Tables t;
     if (preset) t = *preset;
@@ -230,12 +233,18 @@ int jpeg_stream_stage(const JpegStreamTables* preset, const unsigned char* data,
         if (f.h[0] == 1 && f.v[0] == 1) found = 0;
     } else {
         bool rgb = false;
-        if (t.jfif) rgb = false;
+        if (colour == kJpegColourRgb) rgb = true;
+        else if (t.jfif) rgb = false;
         else if (t.adobe) rgb = t.adobe_transform == 0;
         else rgb = f.id[0] == 'R' && f.id[1] == 'G' && f.id[2] == 'B';
-        if (rgb) return refuse("3 components coded as RGB, not YCbCr");
-        if (f.h[1] == 1 && f.v[1] == 1 && f.h[2] == 1 && f.v[2] == 1)
+        if (rgb) {
+            if (want_sampling != AP_JPEG_RGB) return refuse("3 components coded as RGB, not YCbCr");
+            for (int c = 0; c < 3; ++c)
+                if (f.h[c] != 1 || f.v[c] != 1) return refuse("RGB-coded stream with a component sampled %ldx%ld: only 1x1 components are read", f.h[c], f.v[c]);
+            found = AP_JPEG_RGB;
+        } else if (f.h[1] == 1 && f.v[1] == 1 && f.h[2] == 1 && f.v[2] == 1)
             found = f.h[0] == 1 && f.v[0] == 1 ? 1 : f.h[0] == 2 && f.v[0] == 1 ? 2 : f.h[0] == 2 && f.v[0] == 2 ? 3 : -1;
+        if (!rgb && want_sampling == AP_JPEG_RGB && found >= 0) return refuse("YCbCr stream (sampling %ld) asked for as RGB coded", found);
     }
     if (found < 0) return refuse("sampling factors %ldx%ld are none of 4:4:4, 4:2:2 (2x1), 4:2:0 (2x2), greyscale", f.h[0], f.v[0]);
     if (found != want_sampling) return refuse("sampling %ld, expected %ld", found, want_sampling);
@@ -320,7 +329,7 @@ extern "C" int ap_host_jpeg_streams(void* descs, void* arena, size_t arena_cap, 
                                     int side, int sampling) {
     AP_REQUIRE(descs && arena && arena_used && (paths || n == 0) && n >= 0, "ap_host_jpeg_streams: bad arguments");
     AP_REQUIRE(((uintptr_t)arena & 15) == 0 && ((uintptr_t)descs & 15) == 0, "ap_host_jpeg_streams: descs and arena must be 16-byte aligned");
-    AP_REQUIRE(ap_jpeg_slot_bytes(side, sampling), "ap_host_jpeg_streams: bad side %d or sampling %d", side, sampling);
+    AP_REQUIRE(ap_jpeg_slot_bytes_ex(side, sampling), "ap_host_jpeg_streams: bad side %d or sampling %d", side, sampling);
     size_t used = 0;
     *arena_used = 0;
     for (int i = 0; i < n; ++i) {

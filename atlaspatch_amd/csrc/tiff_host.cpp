@@ -8,6 +8,9 @@
 // (ap_host_tiff_tile_coefficients).  Levels are the tiled IFDs with Compression 7, widest first; stripped IFDs (Aperio's
 // thumbnail, label and macro) are skipped, as OpenSlide's aperio / generic-tiff drivers treat them as associated images.
 //
+// Colour model, per level, by libtiff's rule: SamplesPerPixel 3 with PhotometricInterpretation 2 makes the tiles' components R, G, B
+// whatever their markers say (AP_JPEG_RGB on every route); any other value, or no tag, leaves the inference to libjpeg as for a file.
+//
 // The file is untrusted input: every offset, count and extent read from it is checked against the file size before use, and
 // every product is checked for overflow.  A file outside the accepted subset is refused at open with the reason.
 #include <fcntl.h>
@@ -40,6 +43,8 @@ struct Level {
     double xres = 0, yres = 0;
     int resunit = 0;
     int sampling = -1;
+    bool rgb = false;                              // SamplesPerPixel 3 with PhotometricInterpretation 2: the tiles' components are R, G, B
+    int colour() const { return rgb ? ap::kJpegColourRgb : ap::kJpegColourInfer; }
 };
 
 struct Entry {
@@ -166,7 +171,7 @@ struct Parser {
 
     // one IFD -> a level (tiled = true) or nothing (a stripped image)
     bool level(const std::vector<Entry>& entries, Level& lv, bool& tiled) {
-        uint64_t compression = 1, spp = 1, planar = 1, unit = 2;
+        uint64_t compression = 1, spp = 1, planar = 1, unit = 2, photometric = ~0ull;
         std::vector<uint64_t> bps;
         const Entry *offs = nullptr, *cnts = nullptr, *tables = nullptr, *desc = nullptr, *xres = nullptr, *yres = nullptr;
         tiled = false;
@@ -179,6 +184,9 @@ struct Parser {
                 case 257: if (!one(e, lv.h, "ImageLength")) return false; break;
                 case 258: if (!uints(e, 8, bps, "BitsPerSample")) return false; break;
                 case 259: if (!one(e, compression, "Compression")) return false; break;
+                case 262:                                             // another type or count: the tag counts as absent
+                    if ((e.type == 1 || e.type == 3 || e.type == 4) && e.count == 1 && !one(e, photometric, "PhotometricInterpretation")) return false;
+                    break;
                 case 270: desc = &e; break;
                 case 277: if (!one(e, spp, "SamplesPerPixel")) return false; break;
                 case 282: xres = &e; break;
@@ -239,25 +247,34 @@ struct Parser {
         if (xres && !rational(*xres, lv.xres, "XResolution")) return false;
         if (yres && !rational(*yres, lv.yres, "YResolution")) return false;
         lv.resunit = (int)std::min<uint64_t>(unit, 65535);
+        // libtiff's rule (tif_jpeg.c: JPEGPreDecode): only Photometric 6 lets libjpeg convert YCbCr; under 2 the components are handed
+        // out as R, G, B whatever the stream's markers say.  Any other value, or no tag, keeps libjpeg's inference.
+        lv.rgb = spp == 3 && photometric == 2;
         return true;
     }
 
-    // sampling of the level's first present tile, or -1 when the stream is outside ap_jpeg_decode_tiles' subset
-    void probe(Level& lv) {
+    // sampling of the level's first present tile, or -1 when the stream is outside ap_jpeg_decode_tiles' subset.  An RGB level
+    // (Photometric 2) reports AP_JPEG_RGB or -1, and is refused (false) when that tile has a subsampled component: libtiff rejects
+    // such a file ("Improper JPEG sampling factors"), and no route of this reader decodes it as libtiff would.
+    bool probe(Level& lv) {
         lv.sampling = -1;
-        if (lv.tw != lv.th || lv.tw > (uint64_t)kDeviceMaxSide) return;
+        const bool device = lv.tw == lv.th && lv.tw <= (uint64_t)kDeviceMaxSide;
+        if (!device && !lv.rgb) return true;
         for (size_t i = 0; i < lv.off.size(); ++i) {
             if (!lv.cnt[i]) continue;
             std::vector<unsigned char> buf((size_t)lv.cnt[i]);
-            if (!read(lv.off[i], buf.data(), lv.cnt[i])) return;
+            if (!read(lv.off[i], buf.data(), lv.cnt[i])) return true;
             int wh[2] = {0, 0}, found = -1;
-            char w2[200];
-            if (ap::jpeg_mem_coefficients(lv.tables.empty() ? nullptr : lv.tables.data(), lv.tables.size(), buf.data(), buf.size(), wh,
-                                          &found, 0, 0, nullptr, w2, sizeof(w2)) == AP_OK &&
-                wh[0] == (int)lv.tw && wh[1] == (int)lv.th)
+            char w2[200] = "";
+            const int rc = ap::jpeg_mem_coefficients(lv.tables.empty() ? nullptr : lv.tables.data(), lv.tables.size(), buf.data(), buf.size(),
+                                                     wh, &found, 0, 0, nullptr, w2, sizeof(w2), lv.colour());
+            if (rc != AP_OK && lv.rgb && found == ap::kJpegRgbSubsampled)
+                return fail(AP_ERR_UNSUPPORTED, "level tagged PhotometricInterpretation 2 (RGB) holds a subsampled tile: %s", w2);
+            if (rc == AP_OK && device && wh[0] == (int)lv.tw && wh[1] == (int)lv.th && lv.rgb == (found == AP_JPEG_RGB))   // RGB-inferred tiles outside an RGB level: -1
                 lv.sampling = found;
-            return;
+            return true;
         }
+        return true;
     }
 
     bool parse() {
@@ -297,7 +314,8 @@ struct Parser {
         }
         if (t.levels.empty()) return fail(AP_ERR_UNSUPPORTED, "no tiled JPEG level (a stripped TIFF is not read)");
         std::stable_sort(t.levels.begin(), t.levels.end(), [](const Level& a, const Level& b) { return a.w > b.w; });
-        for (Level& lv : t.levels) probe(lv);
+        for (Level& lv : t.levels)
+            if (!probe(lv)) return false;
         return true;
     }
 };
@@ -404,7 +422,7 @@ extern "C" int ap_host_tiff_read_patches(const ap_tiff* slide, int level, const 
                     int rc = AP_ERR_INVALID;
                     if (!read_tile(slide, lv, (size_t)id, stream)) snprintf(why, sizeof(why), "short read");
                     else rc = ap::jpeg_mem_pixels(lv.tables.empty() ? nullptr : lv.tables.data(), lv.tables.size(), stream.data(), stream.size(),
-                                                  (int)tw, (int)th, px.data(), tile_row, why, sizeof(why));
+                                                  (int)tw, (int)th, px.data(), tile_row, why, sizeof(why), lv.colour());
                     if (rc != AP_OK) {
                         ap::set_error("ap_host_tiff_read_patches: level %d tile (%lld, %lld): %s", level, (long long)tx, (long long)ty, why);
                         return rc;
@@ -426,7 +444,7 @@ extern "C" int ap_host_tiff_tile_coefficients(const ap_tiff* slide, int level, c
     AP_REQUIRE(level >= 0 && (size_t)level < slide->levels.size(), "ap_host_tiff_tile_coefficients: level %d of %zu", level, slide->levels.size());
     const Level& lv = slide->levels[(size_t)level];
     AP_REQUIRE(lv.sampling >= 0, "ap_host_tiff_tile_coefficients: level %d is outside the device decoder's subset", level);
-    const size_t stride = ap_jpeg_slot_bytes((int)lv.tw, lv.sampling);
+    const size_t stride = ap_jpeg_slot_bytes_ex((int)lv.tw, lv.sampling);
     AP_REQUIRE(stride, "ap_host_tiff_tile_coefficients: bad side %d or sampling %d", (int)lv.tw, lv.sampling);
     std::vector<unsigned char> stream;
     for (int i = 0; i < m; ++i) {
@@ -438,7 +456,8 @@ extern "C" int ap_host_tiff_tile_coefficients(const ap_tiff* slide, int level, c
         int wh[2], found, rc = AP_ERR_INVALID;
         if (!read_tile(slide, lv, (size_t)id, stream)) snprintf(why, sizeof(why), "short read");
         else rc = ap::jpeg_mem_coefficients(lv.tables.empty() ? nullptr : lv.tables.data(), lv.tables.size(), stream.data(), stream.size(), wh,
-                                            &found, (int)lv.tw, lv.sampling, (unsigned char*)slots + (size_t)i * stride, why, sizeof(why));
+                                            &found, (int)lv.tw, lv.sampling, (unsigned char*)slots + (size_t)i * stride, why, sizeof(why),
+                                            lv.colour());
         if (rc != AP_OK) {
             ap::set_error("ap_host_tiff_tile_coefficients: level %d tile (%lld, %lld): %s", level, tx, ty, why);
             return rc;
@@ -489,7 +508,7 @@ extern "C" int ap_host_tiff_tile_streams(const ap_tiff* slide, int level, const 
             }
             if (left) snprintf(why, sizeof(why), "short read");
             else rc = ap::jpeg_stream_stage(&tables, at, (size_t)lv.cnt[(size_t)id], (int)lv.tw, lv.sampling, (ap::JpegStreamDesc*)descs + i, (unsigned char*)arena, arena_cap, &used,
-                                            why, sizeof(why));
+                                            why, sizeof(why), lv.colour());
         }
         if (rc != AP_OK) {
             ap::set_error("ap_host_tiff_tile_streams: level %d tile (%lld, %lld): %s", level, tx, ty, why);

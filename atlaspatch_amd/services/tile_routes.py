@@ -110,7 +110,7 @@ class CoefficientRoute:
 
     def __init__(self, wsi, sampling: int, tile_side: int) -> None:
         self.wsi, self.sampling, self.side, self.lib = wsi, int(sampling), int(tile_side), _lib.load()
-        self.pinned_row_bytes = int(self.lib.ap_jpeg_slot_bytes(self.side, self.sampling))
+        self.pinned_row_bytes = int(self.lib.ap_jpeg_slot_bytes_ex(self.side, self.sampling))
 
     def prepare(self, ring, max_rows: int) -> bool:
         """False when ap_jpeg_decode_tiles cannot take the ring's tiles: not this route's squares, too wide, or tile starts that are not
@@ -131,9 +131,9 @@ class CoefficientRoute:
         self.buf.dev[slot][start:stop].copy_(self.buf.host[slot][start:stop], non_blocking=True)
 
     def decode(self, slot: int, start: int, stop: int, token, stream) -> None:
-        _lib.check(self.lib.ap_jpeg_decode_tiles(self.buf.dev[slot][start:stop].data_ptr(), stop - start, self.side, self.sampling,
+        _lib.check(self.lib.ap_jpeg_decode_tiles_ex(self.buf.dev[slot][start:stop].data_ptr(), stop - start, self.side, self.sampling,
                                                  self.ring.dev[slot][start:stop].data_ptr(), int(stream.cuda_stream)),
-                   "ap_jpeg_decode_tiles")
+                   "ap_jpeg_decode_tiles_ex")
         JPEG_TILES["device"] += stop - start
 
     def refused(self, n: int) -> None:
@@ -188,7 +188,7 @@ class StreamRoute:
     def __init__(self, wsi, sampling: int, tile_side: int, bound: int) -> None:
         self.wsi, self.sampling, self.side, self.bound, self.lib = wsi, int(sampling), int(tile_side), int(bound), _lib.load()
         self.header = int(self.lib.ap_jpeg_stream_header_bytes())
-        self.slot_bytes = int(self.lib.ap_jpeg_slot_bytes(self.side, self.sampling))
+        self.slot_bytes = int(self.lib.ap_jpeg_slot_bytes_ex(self.side, self.sampling))
         self.pinned_row_bytes = self.header + self.bound
         self.log, self.row0 = StatusLog(), 0
 
@@ -225,11 +225,11 @@ class StreamRoute:
     def decode(self, slot: int, start: int, stop: int, used: int, stream) -> None:
         buf, n, ptr = self.buf, stop - start, int(stream.cuda_stream)
         coef = buf.coef[slot][start:stop].data_ptr()
-        _lib.check(self.lib.ap_jpeg_entropy_decode_tiles(buf.desc_dev[slot][start:stop].data_ptr(), buf.arena_dev[slot][start * self.bound:].data_ptr(),
+        _lib.check(self.lib.ap_jpeg_entropy_decode_tiles_ex(buf.desc_dev[slot][start:stop].data_ptr(), buf.arena_dev[slot][start * self.bound:].data_ptr(),
                                                          used, n, self.side, self.sampling, coef, buf.status[slot][start:stop].data_ptr(), 0, ptr),
-                   "ap_jpeg_entropy_decode_tiles")
-        _lib.check(self.lib.ap_jpeg_decode_tiles(coef, n, self.side, self.sampling, self.ring.dev[slot][start:stop].data_ptr(), ptr),
-                   "ap_jpeg_decode_tiles")
+                   "ap_jpeg_entropy_decode_tiles_ex")
+        _lib.check(self.lib.ap_jpeg_decode_tiles_ex(coef, n, self.side, self.sampling, self.ring.dev[slot][start:stop].data_ptr(), ptr),
+                   "ap_jpeg_decode_tiles_ex")
         self.log.note(self.row0 + start, n, self.row0 + start, self.row0 + stop, buf.status[slot][start:stop])
         JPEG_STREAM_TILES["device"] += n
 
@@ -314,8 +314,8 @@ class StreamTiles:
         coef, status = buf.dev[slot][first:].data_ptr(), buf.status[slot][first:first + m]
         if m == 0:                       # a chunk whose patches cover no present tile
             return coef
-        _lib.check(r.lib.ap_jpeg_entropy_decode_tiles(buf.desc_dev[slot][first:].data_ptr(), buf.arena_dev[slot][first * self.bound:].data_ptr(),
-                                                      used, m, r.ts, r.sampling, coef, status.data_ptr(), 0, ptr), "ap_jpeg_entropy_decode_tiles")
+        _lib.check(r.lib.ap_jpeg_entropy_decode_tiles_ex(buf.desc_dev[slot][first:].data_ptr(), buf.arena_dev[slot][first * self.bound:].data_ptr(),
+                                                      used, m, r.ts, r.sampling, coef, status.data_ptr(), 0, ptr), "ap_jpeg_entropy_decode_tiles_ex")
         self.log.note((r.row0 + start) * r.per_row, m, r.row0 + start, r.row0 + stop, status)
         return coef
 
@@ -334,7 +334,7 @@ class TileGridRoute:
         self.wsi, self.geometry, self.side, self.lib = wsi, geometry, int(tile_side), _lib.load()
         self.ts, self.sampling, self.G = int(geometry["ts"]), int(geometry["sampling"]), int(geometry["G"])
         self.per_row = self.G * self.G
-        self.slot_bytes = int(self.lib.ap_jpeg_slot_bytes(self.ts, self.sampling))
+        self.slot_bytes = int(self.lib.ap_jpeg_slot_bytes_ex(self.ts, self.sampling))
         self.source = StreamTiles(self, stream_bound) if stream_bound else CoefficientTiles(self)
         self.pinned_row_bytes = self.source.row_bytes * self.per_row
         self.row0 = 0
@@ -382,8 +382,8 @@ class TileGridRoute:
     def decode(self, slot: int, start: int, stop: int, token, stream) -> None:
         ring, buf, ptr, (m, staged) = self.ring, self.buf, int(stream.cuda_stream), token
         cache = self._tiles(buf.cache, slot, start).data_ptr()
-        _lib.check(self.lib.ap_jpeg_decode_tiles(self.source.slots(slot, start, stop, m, staged, ptr), m, self.ts, self.sampling, cache, ptr),
-                   "ap_jpeg_decode_tiles")
+        _lib.check(self.lib.ap_jpeg_decode_tiles_ex(self.source.slots(slot, start, stop, m, staged, ptr), m, self.ts, self.sampling, cache, ptr),
+                   "ap_jpeg_decode_tiles_ex")
         _lib.check(self.lib.ap_gather_patches(cache, m, self.ts, buf.plan_host[slot][start:].data_ptr(), buf.plan_dev[slot][start:].data_ptr(),
                                               stop - start, self.G, ring.tw, ring.th, ring.dev[slot][start:].data_ptr(), ptr),
                    "ap_gather_patches")

@@ -118,7 +118,10 @@ int ap_host_decode_jpeg_tiles(void* dst, const char* const* paths, int n, int si
  * are independent per block and exactly defined in integers.  The host half (libjpeg-turbo's jpeg_read_coefficients, same
  * dlopen'd libjpeg.so.8 as above) delivers a tile's quantised coefficients in a SLOT; the device half turns n slots into the
  * RGB tiles ap_host_decode_jpeg_tiles / PIL's Image.open(...).convert("RGB") give, bit for bit (libjpeg's JDCT_ISLOW with
- * fancy upsampling, restated).  Subset: baseline Huffman, 8 bit, greyscale or YCbCr at one of the samplings below.
+ * fancy upsampling, restated).  Subset: baseline Huffman, 8 bit, greyscale, YCbCr at one of the samplings below, or three 1 x 1
+ * components coded as R, G, B (AP_JPEG_RGB: the slot and the geometry of 4:4:4, decoded without the colour transform).  A FILE is RGB
+ * coded when libjpeg infers so (Adobe marker with transform 0, or ids 'R' 'G' 'B' without a JFIF / Adobe marker); a TIFF TILE when its
+ * level is tagged PhotometricInterpretation 2, whatever its markers say (libtiff's rule, below).
  *
  * A slot is self-contained and ap_jpeg_slot_bytes(side, sampling) long (a multiple of 128; 0 on bad arguments):
  *   uint16 quant[3][64]   natural order, the components' own order, padded to 512 bytes
@@ -129,22 +132,33 @@ int ap_host_decode_jpeg_tiles(void* dst, const char* const* paths, int n, int si
 #define AP_JPEG_444 1
 #define AP_JPEG_422 2                     /* luma 2x1 */
 #define AP_JPEG_420 3                     /* luma 2x2 */
+#define AP_JPEG_RGB 4                     /* three 1x1 components coded as R, G, B: the slot of 4:4:4, no colour transform */
 size_t ap_jpeg_slot_bytes(int side, int sampling);
+/* AP_JPEG_RGB came after the three entries that are handed a sampling and no stream to read it from -- ap_jpeg_slot_bytes,
+ * ap_jpeg_decode_tiles, ap_jpeg_entropy_decode_tiles -- were published with "an unknown sampling is refused" for every code but the
+ * first four.  They keep that contract to the letter (AP_JPEG_RGB: 0 / AP_ERR_INVALID).  Their *_ex twins have the same signatures
+ * and the same behaviour and take all five codes; the host entries (probe, coefficients, streams, the TIFF reader), which report or
+ * check the code against a stream, take AP_JPEG_RGB as they are.  A caller that handles RGB-coded tiles calls the *_ex entries. */
+size_t ap_jpeg_slot_bytes_ex(int side, int sampling);
 /* Header of one file: its size and sampling.  AP_ERR_INVALID for a stream outside the subset (the message names the file
  * and the reason), AP_ERR_UNSUPPORTED without a usable libjpeg.  Host only. */
 int ap_host_jpeg_probe(const char* path, int* width, int* height, int* sampling);
 /* Reads n files and entropy-decodes them into consecutive slots at `slots` (host memory, e.g. the ring's pinned staging
  * buffer), one call per chunk outside the interpreter lock.  AP_ERR_INVALID, naming the file and the reason, for a stream
- * that is progressive, arithmetic coded, not 8 bit, not grey / YCbCr, of another sampling than `sampling`, not side x side,
+ * that is progressive, arithmetic coded, not 8 bit, not grey / YCbCr / RGB, of another sampling than `sampling` (a YCbCr stream asked
+ * for as AP_JPEG_RGB and an RGB-coded one asked for as anything else included), RGB coded with a subsampled component, not side x side,
  * or that libjpeg warned about (truncated / corrupt): that tile's slot and the slots after it are left untouched, the ones
  * before it are complete.  AP_ERR_UNSUPPORTED without a usable libjpeg.  Host only, no device work. */
 int ap_host_jpeg_coefficients(void* slots, const char* const* paths, int n, int side, int sampling);
 /* Device half: slots (device, 16-byte aligned, n slots at ap_jpeg_slot_bytes pitch) -> rgb uint8 [n, side, side, 3] (device,
  * 16-byte aligned).  Dequantise, inverse DCT, range limit, fancy upsampling, colour conversion in one kernel; no workspace.
+ * AP_JPEG_RGB (ap_jpeg_decode_tiles_ex only): the components are written as R, G, B as they come out of the range limit, which is
+ * what libjpeg's copy gives.
  * Reads nothing beyond n * slot_bytes and writes nothing beyond n * side * side * 3.  AP_ERR_INVALID for null or misaligned
  * pointers, side <= 0, a side whose band does not fit one workgroup's 64 KB of LDS (every sampling takes side <= 976), n < 0,
  * an unknown sampling; n == 0 is AP_OK. */
 int ap_jpeg_decode_tiles(const void* slots, int n, int side, int sampling, uint8_t* rgb, ap_stream_t stream);
+int ap_jpeg_decode_tiles_ex(const void* slots, int n, int side, int sampling, uint8_t* rgb, ap_stream_t stream);   /* + AP_JPEG_RGB */
 
 /* ---- K0: the Huffman decode on the device as well (additive: AP_ABI_VERSION stays 20) ------------------------------------
  * The host only reads a tile's bytes and walks them once; the ring carries the compressed stream.  Per tile a DESCRIPTOR of
@@ -160,7 +174,9 @@ int ap_jpeg_decode_tiles(const void* slots, int n, int side, int sampling, uint8
  * the end of the stream), byte stuffing removed, 16-byte aligned, zero filled to the next multiple of 16; whatever follows the
  * terminating marker is ignored, as libjpeg ignores it.
  * The staging functions parse SOI, DQT, DHT, SOF0, DRI, SOS and the APPn / COM segments they skip with code of their own (no
- * libjpeg), every segment length checked against the buffer.  Admitted: the subset of ap_host_jpeg_coefficients restricted to
+ * libjpeg), every segment length checked against the buffer; the colour model of a three-component stream is inferred from JFIF /
+ * Adobe markers and component ids exactly as libjpeg infers it.  Admitted: the subset of ap_host_jpeg_coefficients (AP_JPEG_RGB
+ * included: an RGB-coded stream when, and only when, that code is asked for) restricted to
  * baseline SOF0, one scan with every component in frame order, a side that is a multiple of the MCU size (8, or 16 along a
  * subsampled axis) and <= 976, no restart interval and no RSTn marker, Huffman tables 0 / 1 that exist and form a canonical code
  * without over-subscription.  Everything else is refused with AP_ERR_INVALID and the reason; the refusal contract is the one of
@@ -191,6 +207,8 @@ int ap_host_jpeg_streams(void* descs, void* arena, size_t arena_cap, size_t* are
 #define AP_JPEG_ENTROPY_BAD_DESCRIPTOR 5
 int ap_jpeg_entropy_decode_tiles(const void* descs, const void* arena, size_t arena_bytes, int n, int side, int sampling, void* slots,
                                  int32_t* status, int subsequence_bits, ap_stream_t stream);
+int ap_jpeg_entropy_decode_tiles_ex(const void* descs, const void* arena, size_t arena_bytes, int n, int side, int sampling, void* slots,
+                                    int32_t* status, int subsequence_bits, ap_stream_t stream);                     /* + AP_JPEG_RGB */
 
 /* The same for a slide OpenSlide can open (the reference's production tile source): core/wsi/openslide_wsi.py:184-205 reads
  * one region per call in the interpreter -- openslide-python's read_region (premultiplied ARGB -> RGBA in its C helper, a
@@ -229,14 +247,20 @@ int ap_host_tiff_info(const ap_tiff* slide, int* levels, double* resolution, int
                       size_t description_cap, size_t* description_bytes);
 /* geometry: int64 [8] = width, height, tile_w, tile_h, tiles_x, tiles_y, sampling, bytes of the JPEGTables stream.
  * sampling: the AP_JPEG_* value probed from the level's first present tile, or -1 when the level's streams are outside
- * ap_jpeg_decode_tiles' subset (progressive, RGB coded, not square, wider than 976, no usable libjpeg). */
+ * ap_jpeg_decode_tiles' subset (progressive, not square, wider than 976, no usable libjpeg, RGB-inferred streams in a level that is
+ * not tagged RGB).  COLOUR MODEL, per level, by libtiff's rule: SamplesPerPixel 3 with PhotometricInterpretation (tag 262) = 2 makes
+ * the level RGB CODED -- its tiles' three components are R, G, B whatever the streams' markers and component ids say, on every
+ * route -- and it reports AP_JPEG_RGB (or -1).  Such a level whose first present tile has a subsampled component is refused at open
+ * (AP_ERR_UNSUPPORTED, naming the sampling factors; libtiff rejects it with "Improper JPEG sampling factors").  Any other value of
+ * the tag, or none, leaves the colour model to libjpeg's inference from the stream, as for a file. */
 int ap_host_tiff_level(const ap_tiff* slide, int level, int64_t* geometry);
 /* present: uint8 [tiles_y * tiles_x], row major: 1 = the file holds the tile, 0 = a missing tile. */
 int ap_host_tiff_tile_present(const ap_tiff* slide, int level, uint8_t* present);
 /* The host pixel route: n RGB patches [h, w, 3] into consecutive slots at dst, patch i with its top-left corner at LEVEL
  * coordinates xy[i] (HOST int64 [n, 2]).  The covered tiles are decoded by the dlopen'd libjpeg of ap_host_decode_jpeg_tiles
- * (JPEGTables through jpeg_read_header(..., FALSE) first, then the tile stream, as libtiff and OpenSlide do; the colour space is
- * the one libjpeg infers from the stream, PhotometricInterpretation is not consulted), each tile once per call however many
+ * (JPEGTables through jpeg_read_header(..., FALSE) first, then the tile stream, as libtiff and OpenSlide do; in an RGB-coded level
+ * jpeg_color_space is set to JCS_RGB before the decode starts, so libjpeg copies the components; elsewhere the colour space is the
+ * one libjpeg infers from the stream), each tile once per call however many
  * patches cover it.  Pixels outside the level and pixels of missing tiles are 0; the padding of edge tiles never shows.
  * AP_ERR_INVALID, naming level and tile, for a tile that is not tile_w x tile_h, not decodable or that libjpeg warned about;
  * AP_ERR_UNSUPPORTED without a usable libjpeg. */

@@ -13,6 +13,8 @@
 // entropy-coded segment; the staged descriptor with each of its fields (payload length and offset, component count, selectors, code counts) set to values outside its bounds.  A damaged
 // input must end flagged, refused, or -- where libjpeg reads the same bytes without a warning -- with libjpeg's slot; both subsequence
 // lengths must agree on status, and on the slot when the status is 0.  Exits 1 on any disagreement, 0 otherwise.
+// Every file is also asked for under each of the other sampling codes, AP_JPEG_RGB included (a YCbCr file as RGB and an RGB-coded file
+// -- Adobe transform 0, or ids 'R' 'G' 'B' -- as 4:4:4 must be refused); an RGB-coded file is staged and decoded at AP_JPEG_RGB.
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -73,7 +75,7 @@ static bool same_slot(const uint8_t* a, const uint8_t* b, size_t bytes) {
 // one staged tile through both subsequence lengths; `want`: libjpeg's slot for the same bytes, or null
 static void decode_both(const char* what, const JpegStreamDesc* desc, const uint8_t* arena, size_t arena_bytes, int side, int sampling,
                         const uint8_t* want, bool must_pass) {
-    const size_t bytes = ap_jpeg_slot_bytes(side, sampling);
+    const size_t bytes = ap_jpeg_slot_bytes_ex(side, sampling);
     uint8_t* s32 = (uint8_t*)malloc(bytes);
     uint8_t* sdef = (uint8_t*)malloc(bytes);
     memset(s32, 0x5A, bytes);
@@ -104,7 +106,7 @@ static void check_stream(const char* what, const std::vector<uint8_t>& stream, i
     FILE* f = fopen(scratch, "wb");
     if (!f || fwrite(stream.data(), 1, stream.size(), f) != stream.size()) { fprintf(stderr, "cannot write %s\n", scratch); exit(3); }
     fclose(f);
-    const size_t bytes = ap_jpeg_slot_bytes(side, sampling);
+    const size_t bytes = ap_jpeg_slot_bytes_ex(side, sampling);
     uint8_t* want = (uint8_t*)malloc(bytes);
     const bool libjpeg_ok = ap_host_jpeg_coefficients(want, &scratch, 1, side, sampling) == AP_OK;
     size_t bound = 0;
@@ -157,7 +159,7 @@ int main(int argc, char** argv) {
         char what[600];
         if (probe != AP_OK || w != h) {
             // outside the subset already at its header: every sampling must refuse it
-            for (int s = 0; s < 4; ++s) { snprintf(what, sizeof(what), "%s as sampling %d", path, s); check_stream(what, stream, 16, s, scratch, false); }
+            for (int s = 0; s <= AP_JPEG_RGB; ++s) { snprintf(what, sizeof(what), "%s as sampling %d", path, s); check_stream(what, stream, 16, s, scratch, false); }
             continue;
         }
         const int side = w;
@@ -169,7 +171,7 @@ int main(int argc, char** argv) {
         check_stream(path, stream, side, sampling, scratch, false);
         const bool staged = (size_t)g_refused == before;
         if (staged && !in_subset) { printf("FAIL %s: staged although its side is no multiple of the MCU size\n", path); ++g_failures; }
-        for (int s = 0; s < 4; ++s)
+        for (int s = 0; s <= AP_JPEG_RGB; ++s)
             if (s != sampling) { snprintf(what, sizeof(what), "%s as sampling %d", path, s); check_stream(what, stream, side, s, scratch, false); }
         if (!staged) continue;
         snprintf(what, sizeof(what), "%s (must pass)", path);

@@ -60,7 +60,7 @@ int main(int argc, char** argv) {
             (ap_host_tiff_read_patches(t, lv, &xy[0][0], 5, side, side, px) == AP_OK ? patches_ok : patches_failed)++;
             free(px);
             if (g[6] >= 0) {
-                const size_t bytes = ap_jpeg_slot_bytes((int)g[2], (int)g[6]);
+                const size_t bytes = ap_jpeg_slot_bytes_ex((int)g[2], (int)g[6]);
                 const int32_t ids[3] = {0, (int32_t)(tiles - 1), (int32_t)(tiles / 2)};
                 for (int k = 0; k < 3; ++k) {
                     unsigned char* slot = (unsigned char*)malloc(bytes);
