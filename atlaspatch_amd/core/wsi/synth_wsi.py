@@ -152,13 +152,20 @@ class SynthWSI(IWSI):
                                                    out.data_ptr(), _lib.current_stream_ptr(device)), "ap_synth_region")
         return out
 
+    def _store_files(self, rows, kind: str = ".jpg"):
+        """The tile store's files of ``rows`` as the ``char*`` array the native readers take, or None when the store lacks one of them."""
+        import ctypes as C
+        files = [os.path.join(self.jpeg_dir, f"{int(x)}_{int(y)}_{int(rw)}{kind}") for x, y, rw, rh, lv in rows]
+        if not all(os.path.exists(f) for f in files):
+            return None
+        return (C.c_char_p * len(files))(*[f.encode() for f in files])
+
     def read_tiles_into(self, rows, dst_ptr: int, tile_side: int) -> bool:
         """Optional IWSI capability (native batched host decode): decode the tiles of ``rows`` (x, y, rw, rh, lv) into
         consecutive ``tile_side^2 * 3``-byte slots at ``dst_ptr`` in ONE call outside the interpreter lock, or return
         False when this backend cannot (the caller then reads tile by tile).  The deflate tile store is inflated by
         ``ap_host_inflate_tiles``; a plain synthetic slide is rendered by ``ap_host_synth_tiles`` (the C twin of
         ``render_region``) -- both stand in for a real format's native tile decoder."""
-        import ctypes as C
         from ... import _lib
         self._ensure_loaded()
         if not rows:
@@ -176,22 +183,20 @@ class SynthWSI(IWSI):
                                                        ell.ctypes.data, ell.shape[0]), "ap_host_synth_tiles")
             return True
         lib = _lib.load()
-        stems = [os.path.join(self.jpeg_dir, f"{int(x)}_{int(y)}_{int(rw)}") for x, y, rw, rh, lv in rows]
         if lv0 != 0:
             return False
         kind = getattr(self, "_store_kind", None)
         if kind is None:                                   # one probe per slide: the store holds one kind of file
-            kind = self._store_kind = ".z" if os.path.exists(stems[0] + ".z") else ".jpg"
+            kind = self._store_kind = ".z" if self._store_files(rows[:1], ".z") else ".jpg"
         if kind == ".jpg" and getattr(self, "_jpeg_native", True) is False:
             return False
-        files = [s + kind for s in stems]
-        if not all(os.path.exists(f) for f in files):      # a tile the store does not hold is rendered by the per-tile path
+        arr = self._store_files(rows, kind)
+        if arr is None:                                    # a tile the store does not hold is rendered by the per-tile path
             return False
-        arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
         if kind == ".z":
-            _lib.check(lib.ap_host_inflate_tiles(dst_ptr, arr, len(stems), tile_side * tile_side * 3), "ap_host_inflate_tiles")
+            _lib.check(lib.ap_host_inflate_tiles(dst_ptr, arr, len(rows), tile_side * tile_side * 3), "ap_host_inflate_tiles")
             return True
-        code = lib.ap_host_decode_jpeg_tiles(dst_ptr, arr, len(stems), tile_side)
+        code = lib.ap_host_decode_jpeg_tiles(dst_ptr, arr, len(rows), tile_side)
         if code == _lib.AP_ERR_UNSUPPORTED:                # no usable libjpeg on this host: per-tile Pillow decode
             self._jpeg_native = False
             return False
@@ -231,18 +236,14 @@ class SynthWSI(IWSI):
         at ``dst_ptr`` in ONE call outside the interpreter lock (``ap_host_jpeg_coefficients``), or return False: a tile the
         store lacks, a progressive or damaged tile, another sampling or size, or no libjpeg.  The caller then reads that
         chunk as pixels (``read_tiles_into``, then tile by tile), which decodes, renders or raises as it always did."""
-        import ctypes as C
         from ... import _lib
         self._ensure_loaded()
         if self.jpeg_dir is None or not rows or getattr(self, "_jpeg_coefficients", True) is False:
             return False
-        if common_level(rows, tile_side) != 0:
+        arr = self._store_files(rows) if common_level(rows, tile_side) == 0 else None
+        if arr is None:
             return False
-        files = [os.path.join(self.jpeg_dir, f"{int(x)}_{int(y)}_{int(rw)}.jpg") for x, y, rw, rh, lv in rows]
-        if not all(os.path.exists(f) for f in files):
-            return False
-        arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
-        code = _lib.load().ap_host_jpeg_coefficients(dst_ptr, arr, len(files), tile_side, int(sampling))
+        code = _lib.load().ap_host_jpeg_coefficients(dst_ptr, arr, len(rows), tile_side, int(sampling))
         if code == _lib.AP_ERR_UNSUPPORTED:
             self._jpeg_coefficients = False
             return False
@@ -274,14 +275,11 @@ class SynthWSI(IWSI):
         import ctypes as C
         from ... import _lib
         self._ensure_loaded()
-        if self.jpeg_dir is None or not rows or common_level(rows, tile_side) != 0:
+        arr = self._store_files(rows) if self.jpeg_dir is not None and rows and common_level(rows, tile_side) == 0 else None
+        if arr is None:
             return None
-        files = [os.path.join(self.jpeg_dir, f"{int(x)}_{int(y)}_{int(rw)}.jpg") for x, y, rw, rh, lv in rows]
-        if not all(os.path.exists(f) for f in files):
-            return None
-        arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
         used = C.c_size_t()
-        code = _lib.load().ap_host_jpeg_streams(descs_ptr, arena_ptr, int(arena_cap), C.byref(used), arr, len(files), tile_side, int(sampling))
+        code = _lib.load().ap_host_jpeg_streams(descs_ptr, arena_ptr, int(arena_cap), C.byref(used), arr, len(rows), tile_side, int(sampling))
         if code == _lib.AP_ERR_INVALID:
             return None
         _lib.check(code, "ap_host_jpeg_streams")

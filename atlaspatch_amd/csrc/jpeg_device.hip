@@ -26,6 +26,8 @@ constexpr int kChunk = 64;              // blocks per LDS pass
 constexpr int kBlkStride = 72;          // dwords per block in d: 8 blocks of a wave's column pass land in 64 different banks
 constexpr int kDBytes = kChunk * kBlkStride * 4;
 constexpr int kLdsLimit = 64 * 1024;
+// jpeg_slot.h's kJpegDeviceMaxSide is the widest side the LDS sum of ap_jpeg_decode_tiles_ex admits at its worst sampling (4:4:4 / RGB)
+static_assert(kDBytes + 48 * kJpegDeviceMaxSide <= kLdsLimit && kDBytes + 48 * (kJpegDeviceMaxSide + 8) > kLdsLimit, "kJpegDeviceMaxSide");
 
 struct DecodeArgs {
     const uint8_t* slots;

@@ -71,8 +71,8 @@ extern "C" int ap_jpeg_entropy_decode_tiles_ex(const void* descs, const void* ar
                "ap_jpeg_entropy_decode_tiles: descs, arena and slots must be 16-byte aligned");
     JpegGeom g;
     AP_REQUIRE(jpeg_geom(side, sampling, &g), "ap_jpeg_entropy_decode_tiles: bad side %d or sampling %d", side, sampling);
-    AP_REQUIRE(side <= kJpegEntropyMaxSide && side % (8 * g.hmax) == 0 && side % (8 * g.vmax) == 0,
-               "ap_jpeg_entropy_decode_tiles: side %d is above %d or no multiple of the MCU size", side, kJpegEntropyMaxSide);
+    AP_REQUIRE(side <= kJpegDeviceMaxSide && side % (8 * g.hmax) == 0 && side % (8 * g.vmax) == 0,
+               "ap_jpeg_entropy_decode_tiles: side %d is above %d or no multiple of the MCU size", side, kJpegDeviceMaxSide);
     if (subsequence_bits == 0) subsequence_bits = kEntropyDefaultBits;
     AP_REQUIRE(subsequence_bits >= 32 && subsequence_bits % 32 == 0 && subsequence_bits <= (1 << 20),
                "ap_jpeg_entropy_decode_tiles: subsequence_bits %d is no multiple of 32 in [32, 2^20]", subsequence_bits);

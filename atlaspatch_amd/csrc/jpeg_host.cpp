@@ -188,13 +188,15 @@ void on_message(void* cinfo, int msg_level) {
 Api g_api;
 std::once_flag g_once;
 
-// decode one in-memory JPEG into dst (rows of `stride` bytes); returns 0 or fills `why`.  `tables` (may be null): a tables-only
-// stream (TIFF's JPEGTables tag) read with jpeg_read_header(..., FALSE) in front of an abbreviated `data`, as libtiff does.
-// `colour`: ap::kJpegColourInfer leaves libjpeg's inference alone; ap::kJpegColourRgb (a TIFF level tagged Photometric 2) overrides it
-// for a three-component stream: the components are R, G, B whatever the markers say, and libjpeg copies them.
-int decode_one(const Api& api, const unsigned char* data, size_t size, int want_w, int want_h, unsigned char* dst,
-               size_t stride, char* why, size_t why_cap, const unsigned char* tables = nullptr, size_t tables_size = 0,
-               int colour = ap::kJpegColourInfer) {
+// One libjpeg session over an in-memory stream: the error manager, the setjmp target, create, the tables-only header (`tables`, may be
+// null: TIFF's JPEGTables tag, read with jpeg_read_header(..., FALSE) in front of an abbreviated `data`, as libtiff does), the main
+// header, `body(c, warned)`, destroy on every exit.  A libjpeg error inside the body longjmps back into this frame, which is still
+// live; so the body holds nothing with a destructor.  The body returns 0, or -1 with its reason in `why`; `warned()` refuses (true,
+// reason in `why`) once libjpeg has warned.  WHEN it is asked is the body's: a decode asks behind its last byte, the probe never does
+// (a header libjpeg warns about -- junk in front of a marker, an unknown JFIF version -- still says what the stream is).
+template <class Body>
+int session(const Api& api, const unsigned char* tables, size_t tables_size, const unsigned char* data, size_t size, char* why,
+            size_t why_cap, Body body) {
     jpeg_decompress_struct c;
     ErrJmp err;
     memset(&c, 0, sizeof(c));
@@ -210,131 +212,100 @@ int decode_one(const Api& api, const unsigned char* data, size_t size, int want_
     }
     api.create(&c, kJpegLibVersion, sizeof(jpeg_decompress_struct));
     created = true;
-    if (tables && tables_size) {
-        api.mem_src(&c, tables, (unsigned long)tables_size);
-        if (api.read_header(&c, 0) != JPEG_HEADER_TABLES_ONLY) { snprintf(why, why_cap, "JPEGTables is not a tables-only stream"); api.destroy(&c); return -1; }
-    }
-    api.mem_src(&c, data, (unsigned long)size);
-    if (api.read_header(&c, 1) != JPEG_HEADER_OK) { snprintf(why, why_cap, "not a JPEG stream"); api.destroy(&c); return -1; }
-    if (colour == ap::kJpegColourRgb && c.num_components == 3) c.jpeg_color_space = JCS_RGB;
-    c.out_color_space = JCS_RGB;          // what PIL's convert("RGB") yields for YCbCr and greyscale streams alike
-    api.start(&c);
-    if ((int)c.output_width != want_w || (int)c.output_height != want_h || c.output_components != 3) {
-        snprintf(why, why_cap, "tile is %u x %u x %d, expected %d x %d x 3", c.output_width, c.output_height,
-                 c.output_components, want_w, want_h);
-        api.destroy(&c);
-        return -1;
-    }
-    while (c.output_scanline < c.output_height) {
-        JSAMPROW rows[4];
-        const JDIMENSION left = c.output_height - c.output_scanline, nrows = left < 4 ? left : 4;
-        for (JDIMENSION r = 0; r < nrows; ++r) rows[r] = dst + (size_t)(c.output_scanline + r) * stride;
-        api.read_scanlines(&c, rows, nrows);
-    }
-    api.finish(&c);
-    const long warnings = err.pub.num_warnings;
+    const auto warned = [&] {
+        if (err.pub.num_warnings <= 0) return false;
+        snprintf(why, why_cap, "libjpeg reported %ld warning(s): truncated or corrupt JPEG stream", err.pub.num_warnings);
+        return true;
+    };
+    int rc = -1;
+    if (tables && tables_size && (api.mem_src(&c, tables, (unsigned long)tables_size), api.read_header(&c, 0) != JPEG_HEADER_TABLES_ONLY))
+        snprintf(why, why_cap, "JPEGTables is not a tables-only stream");
+    else if (api.mem_src(&c, data, (unsigned long)size), api.read_header(&c, 1) != JPEG_HEADER_OK)
+        snprintf(why, why_cap, "not a JPEG stream");
+    else
+        rc = body(c, warned);
     api.destroy(&c);
-    if (warnings > 0) {
-        snprintf(why, why_cap, "libjpeg reported %ld warning(s): truncated or corrupt JPEG stream", warnings);
-        return -1;
-    }
-    return 0;
+    return rc;
+}
+
+#define refuse(...) (snprintf(why, why_cap, __VA_ARGS__), -1)
+
+// decode one in-memory JPEG into dst (rows of `stride` bytes); returns 0 or fills `why`.
+// `colour`: ap::kJpegColourInfer leaves libjpeg's inference alone; ap::kJpegColourRgb (a TIFF level tagged Photometric 2) overrides it
+// for a three-component stream: the components are R, G, B whatever the markers say, and libjpeg copies them.
+int decode_one(const Api& api, const unsigned char* data, size_t size, int want_w, int want_h, unsigned char* dst,
+               size_t stride, char* why, size_t why_cap, const unsigned char* tables = nullptr, size_t tables_size = 0,
+               int colour = ap::kJpegColourInfer) {
+    return session(api, tables, tables_size, data, size, why, why_cap, [&](jpeg_decompress_struct& c, const auto& warned) {
+        if (colour == ap::kJpegColourRgb && c.num_components == 3) c.jpeg_color_space = JCS_RGB;
+        c.out_color_space = JCS_RGB;          // what PIL's convert("RGB") yields for YCbCr and greyscale streams alike
+        api.start(&c);
+        if ((int)c.output_width != want_w || (int)c.output_height != want_h || c.output_components != 3)
+            return refuse("tile is %u x %u x %d, expected %d x %d x 3", c.output_width, c.output_height, c.output_components, want_w, want_h);
+        while (c.output_scanline < c.output_height) {
+            JSAMPROW rows[4];
+            const JDIMENSION left = c.output_height - c.output_scanline, nrows = left < 4 ? left : 4;
+            for (JDIMENSION r = 0; r < nrows; ++r) rows[r] = dst + (size_t)(c.output_scanline + r) * stride;
+            api.read_scanlines(&c, rows, nrows);
+        }
+        api.finish(&c);
+        return warned() ? -1 : 0;
+    });
 }
 
 // The entropy-decoded half of a decode: header checks, then (slot != nullptr) libjpeg's Huffman decoder behind
 // jpeg_read_coefficients and a copy of every component's quantisation table and blocks into `slot` (jpeg_slot.h).  Fills
 // wh / sampling from the header; slot == nullptr stops there (ap_host_jpeg_probe).  A stream outside the device decoder's
-// subset -- baseline Huffman, 8 bit, grey, YCbCr at 4:4:4 / 4:2:2 / 4:2:0, or RGB coded at 1 x 1 -- or one libjpeg warned about is
+// subset -- jpeg_host.h: jpeg_classify, and of libjpeg's own fields baseline Huffman at 8 bit -- or one libjpeg warned about is
 // refused with its reason in `why` and nothing written to the slot.  A three-component stream is RGB coded when libjpeg infers so
 // (Adobe transform 0, or ids 'R' 'G' 'B' without a JFIF / Adobe marker) or, under ap::kJpegColourRgb, because the container says so.
 // An RGB-coded stream with a subsampled component is refused before anything else, with *sampling = ap::kJpegRgbSubsampled.
 int read_one(const Api& api, const unsigned char* data, size_t size, int wh[2], int* sampling, int want_side, int want_sampling,
              unsigned char* slot, char* why, size_t why_cap, const unsigned char* tables = nullptr, size_t tables_size = 0,
              int colour = ap::kJpegColourInfer) {
-    jpeg_decompress_struct c;
-    ErrJmp err;
-    memset(&c, 0, sizeof(c));
-    c.err = api.std_error(&err.pub);
-    err.pub.error_exit = on_error;
-    err.pub.emit_message = on_message;
-    err.text[0] = 0;
-    volatile bool created = false;
-    if (setjmp(err.jb)) {
-        snprintf(why, why_cap, "libjpeg: %s", err.text);
-        if (created) api.destroy(&c);
-        return -1;
-    }
-    api.create(&c, kJpegLibVersion, sizeof(jpeg_decompress_struct));
-    created = true;
-#define refuse(...) (snprintf(why, why_cap, __VA_ARGS__), api.destroy(&c), -1)
-    if (tables && tables_size) {
-        api.mem_src(&c, tables, (unsigned long)tables_size);
-        if (api.read_header(&c, 0) != JPEG_HEADER_TABLES_ONLY) return refuse("JPEGTables is not a tables-only stream");
-    }
-    api.mem_src(&c, data, (unsigned long)size);
-    if (api.read_header(&c, 1) != JPEG_HEADER_OK) return refuse("not a JPEG stream");
-    const jpeg_component_info* comp = (const jpeg_component_info*)c.comp_info;
-    const bool rgb = comp && c.num_components == 3 && (colour == ap::kJpegColourRgb || c.jpeg_color_space == JCS_RGB);
-    if (rgb)
-        for (int ci = 0; ci < 3; ++ci)
-            if (comp[ci].h_samp_factor != 1 || comp[ci].v_samp_factor != 1) {
-                *sampling = ap::kJpegRgbSubsampled;
-                return refuse("RGB-coded stream whose component %d has sampling factors %dx%d: only 1x1 components are read", ci,
-                              comp[ci].h_samp_factor, comp[ci].v_samp_factor);
+    return session(api, tables, tables_size, data, size, why, why_cap, [&](jpeg_decompress_struct& c, const auto& warned) {
+        const jpeg_component_info* comp = (const jpeg_component_info*)c.comp_info;
+        const int nc = c.num_components, space = c.jpeg_color_space;
+        int hv[3][2] = {{0, 0}, {0, 0}, {0, 0}};
+        for (int ci = 0; comp && ci < nc && ci < 3; ++ci) hv[ci][0] = comp[ci].h_samp_factor, hv[ci][1] = comp[ci].v_samp_factor;
+        const ap::JpegModel model = !comp ? ap::kJpegOtherModel : nc == 1 && space == JCS_GRAYSCALE ? ap::kJpegGrey :
+                                    nc == 3 && (colour == ap::kJpegColourRgb || space == JCS_RGB) ? ap::kJpegRgbCoded :
+                                    nc == 3 && space == JCS_YCbCr ? ap::kJpegYCbCr : ap::kJpegOtherModel;
+        ap::JpegGeom g;
+        const bool taken = ap::jpeg_classify(nc, hv, model, (int)c.image_width, (int)c.image_height, want_side, want_sampling,
+                                             slot ? &g : nullptr, sampling, why, why_cap);
+        if (*sampling == ap::kJpegRgbSubsampled) return -1;
+        // what only libjpeg's fields say stands in front of the shared refusals
+        if (c.progressive_mode) return refuse("progressive stream");
+        if (c.arith_code) return refuse("arithmetic-coded stream");
+        if (c.data_precision != 8) return refuse("%d-bit samples", c.data_precision);
+        if (!taken) return -1;                // `why` still holds jpeg_classify's reason: none of the three above wrote over it
+        wh[0] = (int)c.image_width;
+        wh[1] = (int)c.image_height;
+        if (!slot) return 0;
+        jvirt_barray_ptr* arrays = api.read_coefficients(&c);
+        if (!arrays) return refuse("jpeg_read_coefficients suspended");
+        // jpeg_read_coefficients has consumed the stream up to its EOI marker, so every warning is in by now.  No
+        // jpeg_finish_decompress before the copy: it releases the image pool, which holds comp_info and the coefficient arrays.
+        if (warned()) return -1;
+        const jpeg_memory_mgr* mem = (const jpeg_memory_mgr*)c.mem;
+        for (int ci = 0; ci < g.ncomp; ++ci)
+            if ((int)comp[ci].width_in_blocks != g.wb[ci] || (int)comp[ci].height_in_blocks != g.hb[ci] || !comp[ci].quant_table)
+                return refuse("component %d: %u x %u blocks (expected %d x %d) or no quantisation table", ci, comp[ci].width_in_blocks,
+                              comp[ci].height_in_blocks, g.wb[ci], g.hb[ci]);
+        memset(slot, 0, ap::kJpegSlotHeader);
+        for (int ci = 0; ci < g.ncomp; ++ci) {
+            memcpy(slot + (size_t)ci * 128, comp[ci].quant_table->quantval, 128);
+            const size_t row_bytes = (size_t)g.wb[ci] * sizeof(JBLOCK);
+            for (int r = 0; r < g.hb[ci]; ++r) {
+                JBLOCKARRAY rows = mem->access_virt_barray(&c, arrays[ci], (JDIMENSION)r, 1, 0);
+                memcpy(slot + g.off[ci] + (size_t)r * row_bytes, rows[0], row_bytes);
             }
-    if (c.progressive_mode) return refuse("progressive stream");
-    if (c.arith_code) return refuse("arithmetic-coded stream");
-    if (c.data_precision != 8) return refuse("%d-bit samples", c.data_precision);
-    const bool grey = c.num_components == 1 && c.jpeg_color_space == JCS_GRAYSCALE;
-    if (!comp || !(grey || rgb || (c.num_components == 3 && c.jpeg_color_space == JCS_YCbCr)))
-        return refuse("%d components in colour space %d: none of greyscale, YCbCr, RGB", c.num_components, c.jpeg_color_space);
-    int found = -1;
-    if (grey) {
-        if (comp[0].h_samp_factor == 1 && comp[0].v_samp_factor == 1) found = AP_JPEG_GRAY;
-    } else if (rgb) {
-        found = AP_JPEG_RGB;
-    } else if (comp[1].h_samp_factor == 1 && comp[1].v_samp_factor == 1 && comp[2].h_samp_factor == 1 && comp[2].v_samp_factor == 1) {
-        const int h = comp[0].h_samp_factor, v = comp[0].v_samp_factor;
-        found = h == 1 && v == 1 ? AP_JPEG_444 : h == 2 && v == 1 ? AP_JPEG_422 : h == 2 && v == 2 ? AP_JPEG_420 : -1;
-    }
-    if (found < 0)
-        return refuse("sampling factors %dx%d%s are none of 4:4:4, 4:2:2 (2x1), 4:2:0 (2x2), greyscale", comp[0].h_samp_factor,
-                      comp[0].v_samp_factor, grey ? "" : " (or subsampled luma / oversampled chroma)");
-    wh[0] = (int)c.image_width;
-    wh[1] = (int)c.image_height;
-    *sampling = found;
-    if (!slot) { api.destroy(&c); return 0; }
-    if (found != want_sampling && (found == AP_JPEG_RGB || want_sampling == AP_JPEG_RGB))
-        return refuse("%s stream (sampling %d) asked for as %s (sampling %d)", rgb ? "RGB-coded" : grey ? "greyscale" : "YCbCr", found,
-                      want_sampling == AP_JPEG_RGB ? "RGB coded" : "greyscale / YCbCr", want_sampling);
-    if (found != want_sampling) return refuse("sampling %d, expected %d", found, want_sampling);
-    if (wh[0] != want_side || wh[1] != want_side) return refuse("tile is %d x %d, expected %d x %d", wh[0], wh[1], want_side, want_side);
-    ap::JpegGeom g;
-    if (!ap::jpeg_geom(want_side, want_sampling, &g)) return refuse("bad side %d", want_side);
-    jvirt_barray_ptr* arrays = api.read_coefficients(&c);
-    if (!arrays) return refuse("jpeg_read_coefficients suspended");
-    // jpeg_read_coefficients has consumed the stream up to its EOI marker, so every warning is in by now.  No
-    // jpeg_finish_decompress before the copy: it releases the image pool, which holds comp_info and the coefficient arrays.
-    if (err.pub.num_warnings > 0)
-        return refuse("libjpeg reported %ld warning(s): truncated or corrupt JPEG stream", err.pub.num_warnings);
-    const jpeg_memory_mgr* mem = (const jpeg_memory_mgr*)c.mem;
-    for (int ci = 0; ci < g.ncomp; ++ci)
-        if ((int)comp[ci].width_in_blocks != g.wb[ci] || (int)comp[ci].height_in_blocks != g.hb[ci] || !comp[ci].quant_table)
-            return refuse("component %d: %u x %u blocks (expected %d x %d) or no quantisation table", ci, comp[ci].width_in_blocks,
-                          comp[ci].height_in_blocks, g.wb[ci], g.hb[ci]);
-    memset(slot, 0, ap::kJpegSlotHeader);
-    for (int ci = 0; ci < g.ncomp; ++ci) {
-        memcpy(slot + (size_t)ci * 128, comp[ci].quant_table->quantval, 128);
-        const size_t row_bytes = (size_t)g.wb[ci] * sizeof(JBLOCK);
-        for (int r = 0; r < g.hb[ci]; ++r) {
-            JBLOCKARRAY rows = mem->access_virt_barray(&c, arrays[ci], (JDIMENSION)r, 1, 0);
-            memcpy(slot + g.off[ci] + (size_t)r * row_bytes, rows[0], row_bytes);
         }
-    }
-    api.destroy(&c);
-    return 0;
-#undef refuse
+        return 0;
+    });
 }
+#undef refuse
 
 // 8 x 8 grey JFIF (all pixels 128): the load-time self-check of the restated declarations
 const unsigned char kProbe[] = {
@@ -410,6 +381,13 @@ int read_file(const char* what, const char* path, std::vector<unsigned char>& bu
     return AP_OK;
 }
 
+// the library, loaded and self-checked once; the message names the entry that asked
+int ready(const char* what) {
+    std::call_once(g_once, load_api);
+    if (!g_api.ok) { ap::set_error("%s: %s", what, g_api.why); return AP_ERR_UNSUPPORTED; }
+    return AP_OK;
+}
+
 }  // namespace
 
 // ---- the in-memory "tables + stream" path (jpeg_host.h): what the file readers below and the TIFF reader share ----------
@@ -438,26 +416,14 @@ int jpeg_mem_coefficients(const unsigned char* tables, size_t tables_size, const
 
 extern "C" int ap_host_decode_jpeg_tiles(void* dst, const char* const* paths, int n, int side) {
     AP_REQUIRE(dst && (paths || n == 0) && n >= 0 && side > 0, "ap_host_decode_jpeg_tiles: bad arguments");
-    std::call_once(g_once, load_api);
-    if (!g_api.ok) {
-        ap::set_error("ap_host_decode_jpeg_tiles: %s", g_api.why);
-        return AP_ERR_UNSUPPORTED;
-    }
+    if (int rc = ready("ap_host_decode_jpeg_tiles")) return rc;
     std::vector<unsigned char> buf;
     const size_t tile_bytes = (size_t)side * side * 3;
     for (int i = 0; i < n; ++i) {
         AP_REQUIRE(paths[i], "ap_host_decode_jpeg_tiles: null path %d", i);
-        FILE* f = fopen(paths[i], "rb");
-        AP_REQUIRE(f, "ap_host_decode_jpeg_tiles: cannot open %s", paths[i]);
-        fseek(f, 0, SEEK_END);
-        const long size = ftell(f);
-        fseek(f, 0, SEEK_SET);
-        buf.resize(size > 0 ? (size_t)size : 1);
-        const size_t got = size > 0 ? fread(buf.data(), 1, (size_t)size, f) : 0;
-        fclose(f);
-        AP_REQUIRE(size > 0 && got == (size_t)size, "ap_host_decode_jpeg_tiles: short read of %s", paths[i]);
+        if (int rc = read_file("ap_host_decode_jpeg_tiles", paths[i], buf)) return rc;
         char why[200] = "";
-        if (decode_one(g_api, buf.data(), (size_t)size, side, side, (unsigned char*)dst + (size_t)i * tile_bytes,
+        if (decode_one(g_api, buf.data(), buf.size(), side, side, (unsigned char*)dst + (size_t)i * tile_bytes,
                        (size_t)side * 3, why, sizeof(why)) != 0) {
             ap::set_error("ap_host_decode_jpeg_tiles: %s: %s", paths[i], why);
             return AP_ERR_INVALID;
@@ -476,11 +442,7 @@ extern "C" size_t ap_jpeg_slot_bytes(int side, int sampling) { return sampling =
 
 extern "C" int ap_host_jpeg_probe(const char* path, int* width, int* height, int* sampling) {
     AP_REQUIRE(path && width && height && sampling, "ap_host_jpeg_probe: null pointer");
-    std::call_once(g_once, load_api);
-    if (!g_api.ok) {
-        ap::set_error("ap_host_jpeg_probe: %s", g_api.why);
-        return AP_ERR_UNSUPPORTED;
-    }
+    if (int rc = ready("ap_host_jpeg_probe")) return rc;
     std::vector<unsigned char> buf;
     if (int rc = read_file("ap_host_jpeg_probe", path, buf)) return rc;
     char why[200] = "";
@@ -499,11 +461,7 @@ extern "C" int ap_host_jpeg_coefficients(void* slots, const char* const* paths, 
     AP_REQUIRE(slots && (paths || n == 0) && n >= 0, "ap_host_jpeg_coefficients: bad arguments");
     const size_t stride = ap_jpeg_slot_bytes_ex(side, sampling);
     AP_REQUIRE(stride, "ap_host_jpeg_coefficients: bad side %d or sampling %d", side, sampling);
-    std::call_once(g_once, load_api);
-    if (!g_api.ok) {
-        ap::set_error("ap_host_jpeg_coefficients: %s", g_api.why);
-        return AP_ERR_UNSUPPORTED;
-    }
+    if (int rc = ready("ap_host_jpeg_coefficients")) return rc;
     std::vector<unsigned char> buf;
     for (int i = 0; i < n; ++i) {
         AP_REQUIRE(paths[i], "ap_host_jpeg_coefficients: null path %d", i);

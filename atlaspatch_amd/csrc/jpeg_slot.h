@@ -12,6 +12,12 @@ namespace ap {
 
 constexpr int kJpegSlotHeader = 512;
 constexpr int kJpegMaxSide = 65535;        // what a JPEG frame header can say
+// The widest tile the device decoders take.  ap_jpeg_decode_tiles keeps a 16-row band of a tile in one workgroup's LDS
+// (jpeg_device.hip: lds = kDBytes + 16 * py + 2 * crows * pc, checked against kLdsLimit = 64 KB).  The worst sampling is 4:4:4 / RGB,
+// where py = pc = side rounded up to 8 and crows = 16: 18432 + 48 * 976 = 65280 fits, 18432 + 48 * 984 = 65664 does not
+// (jpeg_device.hip asserts just that).  The stream stager, the entropy launch and the TIFF reader's level probe hold tiles to it,
+// because the slots they make are for that decoder.
+constexpr int kJpegDeviceMaxSide = 976;
 
 struct JpegGeom {
     int ncomp;

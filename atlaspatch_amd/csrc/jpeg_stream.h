@@ -22,7 +22,6 @@ namespace ap {
 
 constexpr int kJpegStreamHeader = 2048;
 constexpr uint32_t kJpegStreamMaxPayload = (1u << 20) - 16;     // a bit position fits 23 bits (jpeg_entropy_core.h packs it so)
-constexpr int kJpegEntropyMaxSide = 976;                        // ap_jpeg_decode_tiles' limit, which the slots are for
 
 struct JpegStreamDesc {
     uint16_t quant[3][64];

@@ -2,11 +2,11 @@
 // of its own -- no libjpeg -- that turns a tile's JPEG stream into the descriptor and the unstuffed payload of jpeg_stream.h.
 //
 // The input is untrusted: every segment length is checked against the buffer before a byte of the segment is read.  What is admitted
-// is the coefficient reader's subset (jpeg_host.cpp: read_one) restricted to what ap_jpeg_entropy_decode_tiles takes; everything else
+// is the subset both readers share (jpeg_host.h: jpeg_classify, the one statement of it) restricted to what ap_jpeg_entropy_decode_tiles takes; everything else
 // is refused with its reason, and the caller's next route (coefficients, then pixels) takes the tile:
 //   baseline sequential Huffman (SOF0), 8 bit; one scan with every component, in frame order; greyscale, YCbCr at 4:4:4 / 4:2:2
 //   (2x1) / 4:2:0 (2x2) with 1x1 chroma, or RGB coded with three 1x1 components; the requested side and sampling; a side that is a
-//   multiple of the MCU size and <= 976; no restart interval and no RSTn marker; Huffman tables 0 / 1 that exist and form a
+//   multiple of the MCU size and <= 976 (jpeg_slot.h: kJpegDeviceMaxSide); no restart interval and no RSTn marker; Huffman tables 0 / 1 that exist and form a
 //   canonical code the way libjpeg checks it (jdhuff.c: jpeg_make_d_derived_tbl), DC categories <= 15.
 // The colour space is inferred as libjpeg does (jdapimin.c: default_decompress_parms): JFIF -> YCbCr; Adobe transform 0 -> RGB;
 // neither: component ids 'R' 'G' 'B' -> RGB -- unless the container decides it (jpeg_host.h: kJpegColourRgb, a TIFF level tagged
@@ -36,7 +36,7 @@ using Tables = JpegStreamTables;
 struct Frame {
     bool seen = false;
     int width = 0, height = 0, ncomp = 0;
-    int id[3], h[3], v[3], tq[3];
+    int id[3], tq[3], hv[3][2] = {{0, 0}, {0, 0}, {0, 0}};
 };
 
 struct Walk {
@@ -129,6 +129,18 @@ bool read_app(int m, const unsigned char* p, size_t len, Tables& t) {
     return true;
 }
 
+// a table segment (DQT, DHT, APPn, DRI, COM) into t: 1 = taken, 0 = another marker, -1 = refused, the reason in w.why
+int table_segment(Walk& w, int m, const unsigned char* p, size_t len, Tables& t) {
+    if (m == 0xDB) return read_dqt(w, p, len, t) ? 1 : -1;
+    if (m == 0xC4) return read_dht(w, p, len, t) ? 1 : -1;
+    if (m >= 0xE0 && m <= 0xEF) return read_app(m, p, len, t), 1;
+    if (m == 0xFE) return 1;
+    if (m != 0xDD) return 0;
+    if (len != 2) return w.fail("DRI: segment length"), -1;
+    t.restart = (p[0] << 8) | p[1];
+    return 1;
+}
+
 // the tables-only stream of TIFF's JPEGTables: SOI, table segments, EOI
 bool read_tables(Walk& w, Tables& t) {
     int m;
@@ -141,12 +153,9 @@ bool read_tables(Walk& w, Tables& t) {
         const unsigned char* p;
         size_t len;
         if (!w.segment(m, &p, &len)) return false;
-        if (m == 0xDB) { if (!read_dqt(w, p, len, t)) return false; }
-        else if (m == 0xC4) { if (!read_dht(w, p, len, t)) return false; }
-        else if (m >= 0xE0 && m <= 0xEF) read_app(m, p, len, t);
-        else if (m == 0xDD) { if (len != 2) return w.fail("DRI: segment length"); t.restart = (p[0] << 8) | p[1]; }
-        else if (m == 0xFE) {}
-        else return w.fail("JPEGTables is not a tables-only stream: marker %02lX", m);
+        const int took = table_segment(w, m, p, len, t);
+        if (took < 0) return false;
+        if (!took) return w.fail("JPEGTables is not a tables-only stream: marker %02lX", m);
     }
 }
 
@@ -179,13 +188,8 @@ int jpeg_stream_stage(const JpegStreamTables* preset, const unsigned char* data,
         const unsigned char* p;
         size_t len;
         if (!w.segment(m, &p, &len)) return kInvalid;
-        if (m == 0xDB) { if (!read_dqt(w, p, len, t)) return kInvalid; continue; }
-        if (m == 0xC4) { if (!read_dht(w, p, len, t)) return kInvalid; continue; }
-        if (m >= 0xE0 && m <= 0xEF) { read_app(m, p, len, t); continue; }
-        if (m == 0xFE) continue;
-        if (m == 0xDD) {
-            if (len != 2) return refuse("DRI: segment length");
-            t.restart = (p[0] << 8) | p[1];
+        if (const int took = table_segment(w, m, p, len, t)) {
+            if (took < 0) return kInvalid;
             continue;
         }
         if (m == 0xC2 || m == 0xC6 || m == 0xCA || m == 0xCE) return refuse("progressive stream");
@@ -202,8 +206,8 @@ int jpeg_stream_stage(const JpegStreamTables* preset, const unsigned char* data,
             if (len != 6 + 3 * (size_t)f.ncomp) return refuse("SOF0: segment length");
             for (int c = 0; c < f.ncomp; ++c) {
                 f.id[c] = p[6 + 3 * c];
-                f.h[c] = p[7 + 3 * c] >> 4;
-                f.v[c] = p[7 + 3 * c] & 15;
+                f.hv[c][0] = p[7 + 3 * c] >> 4;
+                f.hv[c][1] = p[7 + 3 * c] & 15;
                 f.tq[c] = p[8 + 3 * c];
                 if (f.tq[c] > 3) return refuse("SOF0: quantisation table %ld", f.tq[c]);
             }
@@ -226,32 +230,15 @@ int jpeg_stream_stage(const JpegStreamTables* preset, const unsigned char* data,
         if (tail[0] != 0 || tail[1] != 63 || tail[2] != 0) return refuse("SOS: not a full sequential scan");
         break;
     }
-    // ---- what the frame says against what was asked for
-    int found = -1;
-    if (f.ncomp == 1) {
-        // libjpeg decodes a one-component frame with its sampling factors taken as 1 x 1 whatever they say; the reader wants them said
-        if (f.h[0] == 1 && f.v[0] == 1) found = 0;
-    } else {
-        bool rgb = false;
-        if (colour == kJpegColourRgb) rgb = true;
-        else if (t.jfif) rgb = false;
-        else if (t.adobe) rgb = t.adobe_transform == 0;
-        else rgb = f.id[0] == 'R' && f.id[1] == 'G' && f.id[2] == 'B';
-        if (rgb) {
-            if (want_sampling != AP_JPEG_RGB) return refuse("3 components coded as RGB, not YCbCr");
-            for (int c = 0; c < 3; ++c)
-                if (f.h[c] != 1 || f.v[c] != 1) return refuse("RGB-coded stream with a component sampled %ldx%ld: only 1x1 components are read", f.h[c], f.v[c]);
-            found = AP_JPEG_RGB;
-        } else if (f.h[1] == 1 && f.v[1] == 1 && f.h[2] == 1 && f.v[2] == 1)
-            found = f.h[0] == 1 && f.v[0] == 1 ? 1 : f.h[0] == 2 && f.v[0] == 1 ? 2 : f.h[0] == 2 && f.v[0] == 2 ? 3 : -1;
-        if (!rgb && want_sampling == AP_JPEG_RGB && found >= 0) return refuse("YCbCr stream (sampling %ld) asked for as RGB coded", found);
-    }
-    if (found < 0) return refuse("sampling factors %ldx%ld are none of 4:4:4, 4:2:2 (2x1), 4:2:0 (2x2), greyscale", f.h[0], f.v[0]);
-    if (found != want_sampling) return refuse("sampling %ld, expected %ld", found, want_sampling);
-    if (f.width != want_side || f.height != want_side) return refuse("tile is %ld x %ld, not the expected square", f.width, f.height);
+    // ---- what the frame says against what was asked for: the readers' shared rule (jpeg_host.h).  The colour model of a three-component
+    // frame is this reader's own inference, or the container's word
+    const bool rgb = colour == kJpegColourRgb || (t.jfif ? false : t.adobe ? t.adobe_transform == 0 : f.id[0] == 'R' && f.id[1] == 'G' && f.id[2] == 'B');
     JpegGeom g;
-    if (!jpeg_geom(want_side, want_sampling, &g)) return refuse("bad side %ld", want_side);
-    if (want_side > kJpegEntropyMaxSide) return refuse("side %ld is above the device decoder's %ld", want_side, kJpegEntropyMaxSide);
+    int found;
+    if (!jpeg_classify(f.ncomp, f.hv, f.ncomp == 1 ? kJpegGrey : rgb ? kJpegRgbCoded : kJpegYCbCr, f.width, f.height, want_side, want_sampling,
+                       &g, &found, why, why_cap))
+        return kInvalid;
+    if (want_side > kJpegDeviceMaxSide) return refuse("side %ld is above the device decoder's %ld", want_side, kJpegDeviceMaxSide);
     if (want_side % (8 * g.hmax) || want_side % (8 * g.vmax)) return refuse("side %ld is no multiple of the MCU size", want_side);
     if (t.restart) return refuse("restart interval %ld", (long)t.restart);
     for (int c = 0; c < f.ncomp; ++c)

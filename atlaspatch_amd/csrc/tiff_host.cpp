@@ -33,7 +33,6 @@ constexpr uint64_t kMaxIfds = 4096;
 constexpr uint64_t kMaxTiles = 1ull << 26;         // per level
 constexpr uint64_t kMaxTables = 1ull << 20;
 constexpr uint64_t kMaxDescription = 1ull << 20;
-constexpr int kDeviceMaxSide = 976;                // ap_jpeg_decode_tiles: the widest tile whose band fits a workgroup's LDS
 
 struct Level {
     uint64_t w = 0, h = 0, tw = 0, th = 0, tx = 0, ty = 0;
@@ -52,6 +51,17 @@ struct Entry {
     uint64_t count = 0;
     unsigned char value[8] = {0};                  // the value / offset field as stored
 };
+
+// pread exactly n bytes at offset off into dst
+bool pread_all(int fd, uint64_t off, void* dst, uint64_t n) {
+    unsigned char* p = (unsigned char*)dst;
+    while (n) {
+        const ssize_t got = pread(fd, p, (size_t)n, (off_t)off);
+        if (got <= 0) return false;
+        p += got; off += (uint64_t)got; n -= (uint64_t)got;
+    }
+    return true;
+}
 
 size_t type_size(unsigned type) {
     switch (type) {
@@ -88,14 +98,7 @@ struct Parser {
         return false;
     }
     bool read(uint64_t off, void* dst, uint64_t n) const {
-        if (off > t.size || n > t.size - off) return false;
-        unsigned char* p = (unsigned char*)dst;
-        while (n) {
-            const ssize_t got = pread(t.fd, p, (size_t)n, (off_t)off);
-            if (got <= 0) return false;
-            p += got; off += (uint64_t)got; n -= (uint64_t)got;
-        }
-        return true;
+        return off <= t.size && n <= t.size - off && pread_all(t.fd, off, dst, n);
     }
     uint64_t uint_at(const unsigned char* p, size_t bytes) const {
         uint64_t v = 0;
@@ -258,7 +261,7 @@ struct Parser {
     // such a file ("Improper JPEG sampling factors"), and no route of this reader decodes it as libtiff would.
     bool probe(Level& lv) {
         lv.sampling = -1;
-        const bool device = lv.tw == lv.th && lv.tw <= (uint64_t)kDeviceMaxSide;
+        const bool device = lv.tw == lv.th && lv.tw <= (uint64_t)ap::kJpegDeviceMaxSide;
         if (!device && !lv.rgb) return true;
         for (size_t i = 0; i < lv.off.size(); ++i) {
             if (!lv.cnt[i]) continue;
@@ -322,14 +325,7 @@ struct Parser {
 
 bool read_tile(const ap_tiff* t, const Level& lv, size_t id, std::vector<unsigned char>& buf) {
     buf.resize((size_t)lv.cnt[id]);
-    uint64_t off = lv.off[id], n = lv.cnt[id];
-    unsigned char* p = buf.data();
-    while (n) {
-        const ssize_t got = pread(t->fd, p, (size_t)n, (off_t)off);
-        if (got <= 0) return false;
-        p += got; off += (uint64_t)got; n -= (uint64_t)got;
-    }
-    return true;
+    return pread_all(t->fd, lv.off[id], buf.data(), lv.cnt[id]);
 }
 
 }  // namespace
@@ -496,20 +492,12 @@ extern "C" int ap_host_tiff_tile_streams(const ap_tiff* slide, int level, const 
         char why[200] = "";
         int rc = AP_ERR_INVALID;
         // the tile's bytes go straight into the arena, where its payload will start; the unstuffing pass then runs in place
-        uint64_t off = lv.off[(size_t)id], left = lv.cnt[(size_t)id];
+        const uint64_t bytes = lv.cnt[(size_t)id];
         unsigned char* at = (unsigned char*)arena + used;
-        if (left > arena_cap - used) snprintf(why, sizeof(why), "the arena would overflow");
-        else {
-            unsigned char* p = at;
-            while (left) {
-                const ssize_t got = pread(slide->fd, p, (size_t)left, (off_t)off);
-                if (got <= 0) break;
-                p += got; off += (uint64_t)got; left -= (uint64_t)got;
-            }
-            if (left) snprintf(why, sizeof(why), "short read");
-            else rc = ap::jpeg_stream_stage(&tables, at, (size_t)lv.cnt[(size_t)id], (int)lv.tw, lv.sampling, (ap::JpegStreamDesc*)descs + i, (unsigned char*)arena, arena_cap, &used,
-                                            why, sizeof(why), lv.colour());
-        }
+        if (bytes > arena_cap - used) snprintf(why, sizeof(why), "the arena would overflow");
+        else if (!pread_all(slide->fd, lv.off[(size_t)id], at, bytes)) snprintf(why, sizeof(why), "short read");
+        else rc = ap::jpeg_stream_stage(&tables, at, (size_t)bytes, (int)lv.tw, lv.sampling, (ap::JpegStreamDesc*)descs + i, (unsigned char*)arena,
+                                        arena_cap, &used, why, sizeof(why), lv.colour());
         if (rc != AP_OK) {
             ap::set_error("ap_host_tiff_tile_streams: level %d tile (%lld, %lld): %s", level, tx, ty, why);
             return rc;

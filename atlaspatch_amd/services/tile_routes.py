@@ -11,10 +11,15 @@ A route has one shape, and ``TileRing.run`` knows nothing else about it:
     decode_reads_pinned                       decode reads pinned memory on the compute stream (the ring keeps the CPU off it until then)
     pinned_row_bytes                          device routes: pinned bytes staged per coords row (sizes the ring's batch)
     begin(n_total), row0, flagged_rows(), reran(n)   optional: a route whose device decode can FLAG a tile after the chunk was accepted
-                                              (the stream routes; ``TileRing.run`` runs the batches that hold such a tile again without it)
+                                              (``TileRing.run`` runs the batches that hold such a tile again without it)
 
 ``PixelRoute`` ends every ring's list and never refuses; ``routes_for`` asks a slide backend for the device routes in front of it.
-Each route's offset arithmetic lives in that route, once.
+
+How JPEG tiles are staged, uploaded and made into coefficient slots is said once, in two TILE SOURCES that own no buffers and know no
+route: ``CoefficientTiles`` (the host did the Huffman decode) and ``StreamTiles`` (the device does; this source can flag).  Their users are
+``CoefficientRoute`` / ``StreamRoute`` (a JPEG tile store: one tile per row, decoded straight into the device tile slot) and ``TileGridRoute``
+(``G * G`` tile slots per row, plus plan, cache and gather).  A route multiplies a row index by its tile slots per row; every other offset
+is the source's, and so is the flag protocol.
 """
 from __future__ import annotations
 
@@ -40,7 +45,7 @@ TIFF_TILES = {"device": 0, "host": 0, "patches": 0}
 # "flagged" = tiles the device decoder flagged, "rerun" = tiles / patches of the batches that were run again without the route.
 JPEG_STREAM_TILES = {"device": 0, "refused": 0, "flagged": 0, "rerun": 0}
 TIFF_STREAM_TILES = {"device": 0, "patches": 0, "refused": 0, "flagged": 0, "rerun": 0}
-# ap_jpeg_decode_tiles holds a band of a tile in one workgroup's LDS: the widest tile it takes at every sampling
+# csrc/jpeg_slot.h: kJpegDeviceMaxSide, the widest tile ap_jpeg_decode_tiles takes at every sampling (a band of it lies in one workgroup's LDS)
 _JPEG_DEVICE_MAX_SIDE = 976
 
 
@@ -102,44 +107,6 @@ class PixelRoute:
         pass
 
 
-class CoefficientRoute:
-    """A JPEG tile store (``jpeg_coefficient_sampling`` / ``read_coefficients_into``): a tile's entropy-decoded coefficient slot crosses
-    PCIe in place of its pixels and ``ap_jpeg_decode_tiles`` writes the tile into the device tile slot."""
-    merges = True
-    decode_reads_pinned = False
-
-    def __init__(self, wsi, sampling: int, tile_side: int) -> None:
-        self.wsi, self.sampling, self.side, self.lib = wsi, int(sampling), int(tile_side), _lib.load()
-        self.pinned_row_bytes = int(self.lib.ap_jpeg_slot_bytes_ex(self.side, self.sampling))
-
-    def prepare(self, ring, max_rows: int) -> bool:
-        """False when ap_jpeg_decode_tiles cannot take the ring's tiles: not this route's squares, too wide, or tile starts that are not
-        16-byte aligned."""
-        side, nbytes = self.side, self.pinned_row_bytes
-        if (ring.th, ring.tw) != (side, side) or side > _JPEG_DEVICE_MAX_SIDE or (side * side * 3) % 16 or nbytes == 0:
-            return False
-        self.ring = ring
-        self.buf = _buffers(ring, self, (self.sampling, nbytes), ring.batch, lambda: dict(
-            host=[torch.empty((ring.batch, nbytes), dtype=torch.uint8, pin_memory=True) for _ in range(ring.slots)],
-            dev=[torch.empty((ring.batch, nbytes), dtype=torch.uint8, device=ring.device) for _ in range(ring.slots)]))
-        return True
-
-    def fill(self, slot: int, start: int, rows: list):
-        return self.wsi.read_coefficients_into(rows, self.buf.host[slot][start:].data_ptr(), self.side, self.sampling) or None
-
-    def upload(self, slot: int, start: int, stop: int, token) -> None:
-        self.buf.dev[slot][start:stop].copy_(self.buf.host[slot][start:stop], non_blocking=True)
-
-    def decode(self, slot: int, start: int, stop: int, token, stream) -> None:
-        _lib.check(self.lib.ap_jpeg_decode_tiles_ex(self.buf.dev[slot][start:stop].data_ptr(), stop - start, self.side, self.sampling,
-                                                 self.ring.dev[slot][start:stop].data_ptr(), int(stream.cuda_stream)),
-                   "ap_jpeg_decode_tiles_ex")
-        JPEG_TILES["device"] += stop - start
-
-    def refused(self, n: int) -> None:
-        JPEG_TILES["host"] += n
-
-
 class StatusLog:
     """What a stream route remembers of a slide's device decodes: every launch's status words, copied into one pinned int32 array behind
     the batch, and which coords rows each launch stood for.  ``flagged_rows`` is read once the slide's batches are through."""
@@ -177,232 +144,248 @@ def batches_with_rows(rows, bounds) -> list:
     return [b for b, (lo, hi) in enumerate(bounds) if np.searchsorted(rows, hi) > np.searchsorted(rows, lo)]
 
 
-class StreamRoute:
-    """A JPEG tile store whose backend also stages streams (``jpeg_stream_bound`` / ``read_streams_into``): a tile's descriptor and
-    unstuffed entropy-coded segment cross PCIe, ``ap_jpeg_entropy_decode_tiles`` turns them into coefficient slots in HBM and
-    ``ap_jpeg_decode_tiles`` into the tile.  A chunk owns ``bound`` arena bytes per row and its descriptors' offsets are relative to its
-    share, so chunks never merge.  The token is the chunk's used arena bytes."""
-    merges = False
-    decode_reads_pinned = False
+class _TileSource:
+    """How JPEG tiles are staged in pinned memory, uploaded and turned into coefficient slots (``ap_jpeg_slot_bytes``) in HBM, for a tile
+    store and a tile grid alike.  Its methods take the route's buffer set ``buf`` (the lists ``make`` returns, one tensor per ring slot)
+    and ``first``, the chunk's first TILE SLOT in them.  ``stage`` wraps the backend's ``read_*_into`` for the chunk's items (coords rows
+    of a store, tile ids of a grid); ``counters`` is the dictionary the source's tiles are counted in."""
 
-    def __init__(self, wsi, sampling: int, tile_side: int, bound: int) -> None:
-        self.wsi, self.sampling, self.side, self.bound, self.lib = wsi, int(sampling), int(tile_side), int(bound), _lib.load()
-        self.header = int(self.lib.ap_jpeg_stream_header_bytes())
-        self.slot_bytes = int(self.lib.ap_jpeg_slot_bytes_ex(self.side, self.sampling))
-        self.pinned_row_bytes = self.header + self.bound
-        self.log, self.row0 = StatusLog(), 0
+    def __init__(self, lib, side: int, sampling: int, counters: dict, stage) -> None:
+        self.lib, self.side, self.sampling, self.counters, self.stage = lib, int(side), int(sampling), counters, stage
+        self.slot_bytes = int(lib.ap_jpeg_slot_bytes_ex(self.side, self.sampling))
 
-    def prepare(self, ring, max_rows: int) -> bool:
-        side, bound = self.side, self.bound
-        if (ring.th, ring.tw) != (side, side) or side > _JPEG_DEVICE_MAX_SIDE or (side * side * 3) % 16 or self.slot_bytes == 0 \
-                or bound <= 0 or bound % 16:
-            return False
-        self.ring = ring
-        n, dev = ring.batch, ring.device
-        self.buf = _buffers(ring, self, (self.sampling, self.slot_bytes, bound), n, lambda: dict(
-            desc_host=[torch.empty((n, self.header), dtype=torch.uint8, pin_memory=True) for _ in range(ring.slots)],
-            arena_host=[torch.empty((n * bound,), dtype=torch.uint8, pin_memory=True) for _ in range(ring.slots)],
-            desc_dev=[torch.empty((n, self.header), dtype=torch.uint8, device=dev) for _ in range(ring.slots)],
-            arena_dev=[torch.empty((n * bound,), dtype=torch.uint8, device=dev) for _ in range(ring.slots)],
-            coef=[torch.empty((n, self.slot_bytes), dtype=torch.uint8, device=dev) for _ in range(ring.slots)],
-            status=[torch.empty((n,), dtype=torch.int32, device=dev) for _ in range(ring.slots)]))
-        return True
-
-    def begin(self, n_total: int) -> None:
-        self.log.begin(n_total)
-
-    def fill(self, slot: int, start: int, rows: list):
-        """A chunk that would overflow its arena share is refused by the stager, like every other stream it does not take."""
-        return self.wsi.read_streams_into(rows, self.buf.desc_host[slot][start:].data_ptr(),
-                                          self.buf.arena_host[slot][start * self.bound:].data_ptr(), len(rows) * self.bound, self.side,
-                                          self.sampling)
-
-    def upload(self, slot: int, start: int, stop: int, used: int) -> None:
-        at = start * self.bound
-        self.buf.desc_dev[slot][start:stop].copy_(self.buf.desc_host[slot][start:stop], non_blocking=True)
-        self.buf.arena_dev[slot][at:at + used].copy_(self.buf.arena_host[slot][at:at + used], non_blocking=True)
-
-    def decode(self, slot: int, start: int, stop: int, used: int, stream) -> None:
-        buf, n, ptr = self.buf, stop - start, int(stream.cuda_stream)
-        coef = buf.coef[slot][start:stop].data_ptr()
-        _lib.check(self.lib.ap_jpeg_entropy_decode_tiles_ex(buf.desc_dev[slot][start:stop].data_ptr(), buf.arena_dev[slot][start * self.bound:].data_ptr(),
-                                                         used, n, self.side, self.sampling, coef, buf.status[slot][start:stop].data_ptr(), 0, ptr),
-                   "ap_jpeg_entropy_decode_tiles_ex")
-        _lib.check(self.lib.ap_jpeg_decode_tiles_ex(coef, n, self.side, self.sampling, self.ring.dev[slot][start:stop].data_ptr(), ptr),
-                   "ap_jpeg_decode_tiles_ex")
-        self.log.note(self.row0 + start, n, self.row0 + start, self.row0 + stop, buf.status[slot][start:stop])
-        JPEG_STREAM_TILES["device"] += n
-
-    def refused(self, n: int) -> None:
-        JPEG_STREAM_TILES["refused"] += n
-
-    def flagged_rows(self) -> list:
-        tiles, rows = self.log.flagged()
-        JPEG_STREAM_TILES["flagged"] += tiles
-        return rows
-
-    def reran(self, n: int) -> None:
-        JPEG_STREAM_TILES["rerun"] += n
+    def usable(self) -> bool:
+        """False when ap_jpeg_decode_tiles cannot take the tiles: too wide, or tile starts that are not 16-byte aligned."""
+        return 0 < self.side <= _JPEG_DEVICE_MAX_SIDE and (self.side * self.side * 3) % 16 == 0 and self.slot_bytes > 0
 
 
-class CoefficientTiles:
-    """``TileGridRoute``'s tile source when the host does the Huffman decode: coefficient slots are staged, copied and used as they are."""
-    counters, flags = TIFF_TILES, False
-
-    def __init__(self, route) -> None:
-        self.r = route
-        self.row_bytes = route.slot_bytes
+class CoefficientTiles(_TileSource):
+    """The host does the Huffman decode (``stage(items, slots_ptr) -> bool``): coefficient slots are staged, copied and used as they
+    are.  Nothing in a slot says where it lies, so adjacent chunks of a store may be uploaded and decoded as one run."""
+    flags, merges = False, True
+    row_bytes = property(lambda self: self.slot_bytes)
 
     def key(self) -> tuple:
         return ()
 
     def make(self, ring, tiles: int) -> dict:
-        nbytes = self.r.slot_bytes
-        return dict(host=[torch.empty((tiles, nbytes), dtype=torch.uint8, pin_memory=True) for _ in range(ring.slots)],
-                    dev=[torch.empty((tiles, nbytes), dtype=torch.uint8, device=ring.device) for _ in range(ring.slots)])
+        return dict(host=[torch.empty((tiles, self.slot_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(ring.slots)],
+                    dev=[torch.empty((tiles, self.slot_bytes), dtype=torch.uint8, device=ring.device) for _ in range(ring.slots)])
 
-    def fill(self, ids, slot: int, start: int, rows: int):
-        r = self.r
-        return r.wsi.read_tile_coefficients_into(ids, r.geometry, r._tiles(r.buf.host, slot, start).data_ptr()) or None
+    def fill(self, buf, slot: int, first: int, items, share: int):
+        return self.stage(items, buf.host[slot][first:].data_ptr()) or None
 
-    def upload(self, slot: int, start: int, m: int, staged) -> None:
-        r = self.r
-        r._tiles(r.buf.dev, slot, start)[:m].copy_(r._tiles(r.buf.host, slot, start)[:m], non_blocking=True)
+    def upload(self, buf, slot: int, first: int, m: int, staged) -> None:
+        buf.dev[slot][first:first + m].copy_(buf.host[slot][first:first + m], non_blocking=True)
 
-    def slots(self, slot: int, start: int, stop: int, m: int, staged, ptr: int) -> int:
-        return self.r._tiles(self.r.buf.dev, slot, start).data_ptr()
+    def slots(self, buf, slot: int, first: int, m: int, staged, ptr: int, where) -> int:
+        return buf.dev[slot][first:].data_ptr()
 
 
-class StreamTiles:
-    """``TileGridRoute``'s tile source when the device does the Huffman decode too (``tile_stream_bound`` / ``read_tile_streams_into``):
-    descriptors and a packed arena are staged and copied, ``ap_jpeg_entropy_decode_tiles`` makes the coefficient slots in HBM."""
-    counters, flags = TIFF_STREAM_TILES, True
+class StreamTiles(_TileSource):
+    """The device does the Huffman decode too (``stage(items, descs_ptr, arena_ptr, arena_cap) -> used | None``): a tile's descriptor and
+    unstuffed entropy-coded segment are staged and copied, ``ap_jpeg_entropy_decode_tiles`` makes the coefficient slots in HBM.  A chunk
+    owns ``bound`` arena bytes for each of its tile slots and its descriptors' offsets are relative to that share, so chunks never
+    merge; what ``fill`` returns is the share's used bytes.  The decode can FLAG a tile after its chunk was accepted: the source keeps
+    the status words (``StatusLog``) and is the ring's re-run protocol, which its route hands through."""
+    flags, merges = True, False
+    row_bytes = property(lambda self: self.header + self.bound)
 
-    def __init__(self, route, bound: int) -> None:
-        self.r, self.bound = route, int(bound)
-        self.header = int(route.lib.ap_jpeg_stream_header_bytes())
-        self.row_bytes = self.header + self.bound
-        self.log = StatusLog()
+    def __init__(self, lib, side: int, sampling: int, counters: dict, stage, bound: int) -> None:
+        super().__init__(lib, side, sampling, counters, stage)
+        self.bound, self.header, self.log = int(bound), int(lib.ap_jpeg_stream_header_bytes()), StatusLog()
+
+    def usable(self) -> bool:
+        return super().usable() and self.bound > 0 and self.bound % 16 == 0
 
     def key(self) -> tuple:
         return (self.bound,)
 
     def make(self, ring, tiles: int) -> dict:
-        dev, nbytes = ring.device, self.r.slot_bytes
-        return dict(desc_host=[torch.empty((tiles, self.header), dtype=torch.uint8, pin_memory=True) for _ in range(ring.slots)],
-                    arena_host=[torch.empty((tiles * self.bound,), dtype=torch.uint8, pin_memory=True) for _ in range(ring.slots)],
-                    desc_dev=[torch.empty((tiles, self.header), dtype=torch.uint8, device=dev) for _ in range(ring.slots)],
-                    arena_dev=[torch.empty((tiles * self.bound,), dtype=torch.uint8, device=dev) for _ in range(ring.slots)],
-                    dev=[torch.empty((tiles, nbytes), dtype=torch.uint8, device=dev) for _ in range(ring.slots)],
-                    status=[torch.empty((tiles,), dtype=torch.int32, device=dev) for _ in range(ring.slots)])
+        def pair(name, shape, dtype=torch.uint8):
+            return {name + "_host": [torch.empty(shape, dtype=dtype, pin_memory=True) for _ in range(ring.slots)],
+                    name + "_dev": [torch.empty(shape, dtype=dtype, device=ring.device) for _ in range(ring.slots)]}
+        return dict(**pair("desc", (tiles, self.header)), **pair("arena", (tiles * self.bound,)),
+                    dev=[torch.empty((tiles, self.slot_bytes), dtype=torch.uint8, device=ring.device) for _ in range(ring.slots)],
+                    status=[torch.empty((tiles,), dtype=torch.int32, device=ring.device) for _ in range(ring.slots)])
 
-    def fill(self, ids, slot: int, start: int, rows: int):
-        """The chunk's arena share is ``bound`` bytes for each of its rows' G * G tile slots; the stager refuses what would overflow it."""
-        r, first = self.r, start * self.r.per_row
-        return r.wsi.read_tile_streams_into(ids, r.geometry, r.buf.desc_host[slot][first:].data_ptr(),
-                                            r.buf.arena_host[slot][first * self.bound:].data_ptr(), rows * r.per_row * self.bound)
+    def fill(self, buf, slot: int, first: int, items, share: int):
+        """The chunk's arena share is ``bound`` bytes for each of its ``share`` tile slots; the stager refuses what would overflow it."""
+        return self.stage(items, buf.desc_host[slot][first:].data_ptr(), buf.arena_host[slot][first * self.bound:].data_ptr(), share * self.bound)
 
-    def upload(self, slot: int, start: int, m: int, used: int) -> None:
-        buf, first = self.r.buf, start * self.r.per_row
+    def upload(self, buf, slot: int, first: int, m: int, used: int) -> None:
         at = first * self.bound
         buf.desc_dev[slot][first:first + m].copy_(buf.desc_host[slot][first:first + m], non_blocking=True)
         buf.arena_dev[slot][at:at + used].copy_(buf.arena_host[slot][at:at + used], non_blocking=True)
 
-    def slots(self, slot: int, start: int, stop: int, m: int, used: int, ptr: int) -> int:
-        r, first = self.r, start * self.r.per_row
-        buf = r.buf
+    def slots(self, buf, slot: int, first: int, m: int, used: int, ptr: int, where) -> int:
+        """``where`` = (the chunk's first tile slot of the whole slide, its first coords row, the row behind its last): the log's entry."""
         coef, status = buf.dev[slot][first:].data_ptr(), buf.status[slot][first:first + m]
         if m == 0:                       # a chunk whose patches cover no present tile
             return coef
-        _lib.check(r.lib.ap_jpeg_entropy_decode_tiles_ex(buf.desc_dev[slot][first:].data_ptr(), buf.arena_dev[slot][first * self.bound:].data_ptr(),
-                                                      used, m, r.ts, r.sampling, coef, status.data_ptr(), 0, ptr), "ap_jpeg_entropy_decode_tiles_ex")
-        self.log.note((r.row0 + start) * r.per_row, m, r.row0 + start, r.row0 + stop, status)
+        _lib.check(self.lib.ap_jpeg_entropy_decode_tiles_ex(buf.desc_dev[slot][first:].data_ptr(), buf.arena_dev[slot][first * self.bound:].data_ptr(),
+                                                         used, m, self.side, self.sampling, coef, status.data_ptr(), 0, ptr),
+                   "ap_jpeg_entropy_decode_tiles_ex")
+        self.log.note(where[0], m, where[1], where[2], status)
         return coef
 
+    def begin(self, tiles: int) -> None:
+        self.log.begin(tiles)
 
-class TileGridRoute:
+    def flagged_rows(self) -> list:
+        tiles, rows = self.log.flagged()
+        self.counters["flagged"] += tiles
+        return rows
+
+    def reran(self, n: int) -> None:
+        self.counters["rerun"] += n
+
+
+class _SourceRoute:
+    """What the routes that ship JPEG tiles through a tile source share.  ``per_row`` is the tile slots a coords row owns in the
+    source's buffers; ``row0`` is the first coords row of the batch in flight, set by the ring on the routes it checks for flags."""
+    per_row, row0 = 1, 0
+
+    def _set_source(self, source) -> None:
+        self.source, self.lib, self.sampling, self.slot_bytes = source, source.lib, source.sampling, source.slot_bytes
+        self.pinned_row_bytes = source.row_bytes * self.per_row
+
+    # The ring's re-run protocol is the source's.  Over a source that cannot flag (``CoefficientTiles``) reading one of the three raises
+    # that source's AttributeError, so the route has them exactly when its source has: ``hasattr(route, "flagged_rows")`` asks the source.
+    flagged_rows = property(lambda self: self.source.flagged_rows)
+    reran = property(lambda self: self.source.reran)
+
+    @property
+    def begin(self):
+        begin = self.source.begin
+        return lambda n_total: begin(n_total * self.per_row)        # the ring counts coords rows, the source tile slots
+
+    def _where(self, start: int, stop: int) -> tuple:
+        return (self.row0 + start) * self.per_row, self.row0 + start, self.row0 + stop
+
+    def refused(self, n: int) -> None:
+        self.source.counters["refused" if self.source.flags else "host"] += n
+
+
+class _StoreRoute(_SourceRoute):
+    """A JPEG tile store: the tile-grid case with one tile per coords row and nothing to gather.  The source's coefficient slots are
+    decoded by ``ap_jpeg_decode_tiles`` straight into the ring's device tile slot; the token is what the source staged."""
+    decode_reads_pinned = False
+    merges = property(lambda self: self.source.merges)
+
+    def prepare(self, ring, max_rows: int) -> bool:
+        side, source = self.side, self.source
+        if (ring.th, ring.tw) != (side, side) or not source.usable():
+            return False
+        self.ring = ring
+        self.buf = _buffers(ring, self, (side, self.sampling, self.slot_bytes) + source.key(), ring.batch, lambda: source.make(ring, ring.batch))
+        return True
+
+    def fill(self, slot: int, start: int, rows: list):
+        return self.source.fill(self.buf, slot, start, rows, len(rows))
+
+    def upload(self, slot: int, start: int, stop: int, staged) -> None:
+        self.source.upload(self.buf, slot, start, stop - start, staged)
+
+    def decode(self, slot: int, start: int, stop: int, staged, stream) -> None:
+        n, ptr = stop - start, int(stream.cuda_stream)
+        coef = self.source.slots(self.buf, slot, start, n, staged, ptr, self._where(start, stop))
+        _lib.check(self.lib.ap_jpeg_decode_tiles_ex(coef, n, self.side, self.sampling, self.ring.dev[slot][start:stop].data_ptr(), ptr),
+                   "ap_jpeg_decode_tiles_ex")
+        self.source.counters["device"] += n
+
+
+class CoefficientRoute(_StoreRoute):
+    """A JPEG tile store (``jpeg_coefficient_sampling`` / ``read_coefficients_into``) through ``CoefficientTiles``: a tile's
+    entropy-decoded coefficient slot crosses PCIe in place of its pixels."""
+
+    def __init__(self, wsi, sampling: int, tile_side: int) -> None:
+        self.side = int(tile_side)
+
+        def stage(rows, slots):
+            return wsi.read_coefficients_into(rows, slots, self.side, self.sampling)
+        self._set_source(CoefficientTiles(_lib.load(), tile_side, sampling, JPEG_TILES, stage))
+
+
+class StreamRoute(_StoreRoute):
+    """A JPEG tile store whose backend also stages streams (``jpeg_stream_bound`` / ``read_streams_into``) through ``StreamTiles``: a
+    tile's descriptor and unstuffed entropy-coded segment cross PCIe."""
+
+    def __init__(self, wsi, sampling: int, tile_side: int, bound: int) -> None:
+        self.side, self.bound = int(tile_side), int(bound)
+
+        def stage(rows, descs, arena, cap):
+            return wsi.read_streams_into(rows, descs, arena, cap, self.side, self.sampling)
+        self._set_source(StreamTiles(_lib.load(), tile_side, sampling, JPEG_STREAM_TILES, stage, bound))
+
+
+class TileGridRoute(_SourceRoute):
     """A tile-grid backend (tiled-JPEG TIFF: ``tile_gather_geometry`` / ``tile_gather_plan`` and a tile source).  Per chunk the distinct
-    covered tiles cross PCIe the way the SOURCE stages them -- ``CoefficientTiles``: coefficient slots (``read_tile_coefficients_into``);
-    ``StreamTiles``: compressed streams that ``ap_jpeg_entropy_decode_tiles`` turns into slots (``read_tile_streams_into``) --,
-    ``ap_jpeg_decode_tiles`` decodes each once into a device tile cache and ``ap_gather_patches`` assembles the chunk's patches into the
-    device tile slot.  The token is (the chunk's distinct-tile count, what the source staged); a chunk owns the ``G * G`` tile slots of
-    each of its rows, and its plan's slot indices are local to it, so chunks never merge."""
+    covered tiles cross PCIe the way the SOURCE stages them -- ``CoefficientTiles`` (``read_tile_coefficients_into``) or, given a
+    ``stream_bound``, ``StreamTiles`` (``read_tile_streams_into``) --, ``ap_jpeg_decode_tiles`` decodes each once into a device tile
+    cache and ``ap_gather_patches`` assembles the chunk's patches into the device tile slot.  The token is (the chunk's distinct-tile
+    count, what the source staged); a chunk owns the ``G * G`` tile slots of each of its rows, and its plan's slot indices are local
+    to it, so chunks never merge."""
     merges = False
     decode_reads_pinned = True           # ap_gather_patches uploads the pinned plan itself
 
     def __init__(self, wsi, geometry: dict, tile_side: int, stream_bound: int = 0) -> None:
-        self.wsi, self.geometry, self.side, self.lib = wsi, geometry, int(tile_side), _lib.load()
-        self.ts, self.sampling, self.G = int(geometry["ts"]), int(geometry["sampling"]), int(geometry["G"])
+        self.wsi, self.geometry, self.side = wsi, geometry, int(tile_side)
+        self.ts, self.G = int(geometry["ts"]), int(geometry["G"])
         self.per_row = self.G * self.G
-        self.slot_bytes = int(self.lib.ap_jpeg_slot_bytes_ex(self.ts, self.sampling))
-        self.source = StreamTiles(self, stream_bound) if stream_bound else CoefficientTiles(self)
-        self.pinned_row_bytes = self.source.row_bytes * self.per_row
-        self.row0 = 0
-        if self.source.flags:            # only a source whose decode can flag a tile gives the route the ring's re-run protocol
-            self.begin, self.flagged_rows, self.reran = self._begin, self._flagged_rows, self._reran
+        lib, sampling = _lib.load(), int(geometry["sampling"])
+        if stream_bound:
+            def stage(ids, descs, arena, cap):
+                return wsi.read_tile_streams_into(ids, geometry, descs, arena, cap)
+            self._set_source(StreamTiles(lib, self.ts, sampling, TIFF_STREAM_TILES, stage, stream_bound))
+        else:
+            def stage(ids, slots):
+                return wsi.read_tile_coefficients_into(ids, geometry, slots)
+            self._set_source(CoefficientTiles(lib, self.ts, sampling, TIFF_TILES, stage))
 
     def prepare(self, ring, max_rows: int) -> bool:
         """False when ap_jpeg_decode_tiles / ap_gather_patches cannot take this geometry on this ring."""
-        ts, G, nbytes = self.ts, self.G, self.slot_bytes
-        if ts > _JPEG_DEVICE_MAX_SIDE or (ts * ts * 3) % 16 or (ring.th * ring.tw * 3) % 16 or G * ts < max(ring.th, ring.tw) + ts - 1 \
-                or nbytes == 0:
+        ts, G, source = self.ts, self.G, self.source
+        if not source.usable() or (ring.th * ring.tw * 3) % 16 or G * ts < max(ring.th, ring.tw) + ts - 1:
             return False
         self.ring = ring
         tiles = max_rows * self.per_row
         self.plan_np = None              # views of the plans: nothing of an earlier run is held while new buffers are made
-        self.buf = _buffers(ring, self, (ts, self.sampling, G, nbytes) + self.source.key(), max_rows, lambda: dict(
+        self.buf = _buffers(ring, self, (ts, self.sampling, G, self.slot_bytes) + source.key(), max_rows, lambda: dict(
             cache=[torch.empty((tiles, ts, ts, 3), dtype=torch.uint8, device=ring.device) for _ in range(ring.slots)],
             plan_host=[torch.empty((max_rows, 4 + G * G), dtype=torch.int32, pin_memory=True) for _ in range(ring.slots)],
             plan_dev=[torch.empty((max_rows, 4 + G * G), dtype=torch.int32, device=ring.device) for _ in range(ring.slots)],
-            **self.source.make(ring, tiles)), kind=(TileGridRoute, type(self.source)))
+            **source.make(ring, tiles)), kind=(TileGridRoute, type(source)))
         self.plan_np = [p.numpy() for p in self.buf.plan_host]
         return True
-
-    def _tiles(self, buffers, slot: int, start: int):
-        """The tile slots of the chunk that starts at row ``start``, open-ended."""
-        return buffers[slot][start * self.per_row:]
 
     def fill(self, slot: int, start: int, rows: list):
         planned = self.wsi.tile_gather_plan(rows, self.geometry, self.side)
         if planned is None:
             return None
         ids, plan = planned
-        m = int(ids.shape[0])
-        if m > len(rows) * self.per_row:
+        m, share = int(ids.shape[0]), len(rows) * self.per_row
+        if m > share:
             return None
-        staged = self.source.fill(ids, slot, start, len(rows))
+        staged = self.source.fill(self.buf, slot, start * self.per_row, ids, share)
         if staged is None:
             return None
         self.plan_np[slot][start:start + len(rows)] = plan
         return m, staged
 
     def upload(self, slot: int, start: int, stop: int, token) -> None:
-        self.source.upload(slot, start, *token)
+        self.source.upload(self.buf, slot, start * self.per_row, *token)
 
     def decode(self, slot: int, start: int, stop: int, token, stream) -> None:
-        ring, buf, ptr, (m, staged) = self.ring, self.buf, int(stream.cuda_stream), token
-        cache = self._tiles(buf.cache, slot, start).data_ptr()
-        _lib.check(self.lib.ap_jpeg_decode_tiles_ex(self.source.slots(slot, start, stop, m, staged, ptr), m, self.ts, self.sampling, cache, ptr),
-                   "ap_jpeg_decode_tiles_ex")
+        ring, buf, ptr, (m, staged), first = self.ring, self.buf, int(stream.cuda_stream), token, start * self.per_row
+        cache = buf.cache[slot][first:].data_ptr()
+        coef = self.source.slots(buf, slot, first, m, staged, ptr, self._where(start, stop))
+        _lib.check(self.lib.ap_jpeg_decode_tiles_ex(coef, m, self.ts, self.sampling, cache, ptr), "ap_jpeg_decode_tiles_ex")
         _lib.check(self.lib.ap_gather_patches(cache, m, self.ts, buf.plan_host[slot][start:].data_ptr(), buf.plan_dev[slot][start:].data_ptr(),
                                               stop - start, self.G, ring.tw, ring.th, ring.dev[slot][start:].data_ptr(), ptr),
                    "ap_gather_patches")
         self.source.counters["device"] += m
         self.source.counters["patches"] += stop - start
-
-    def refused(self, n: int) -> None:
-        self.source.counters["refused" if self.source.flags else "host"] += n
-
-    def _begin(self, n_total: int) -> None:
-        self.source.log.begin(n_total * self.per_row)
-
-    def _flagged_rows(self) -> list:
-        tiles, rows = self.source.log.flagged()
-        TIFF_STREAM_TILES["flagged"] += tiles
-        return rows
-
-    def _reran(self, n: int) -> None:
-        TIFF_STREAM_TILES["rerun"] += n
 
 
 def routes_for(wsi, coords, tile_hw) -> list:

@@ -184,3 +184,24 @@ def test_bad_arguments(lib, tmp_path):
     if rc == _lib.AP_ERR_INVALID:
         assert b"absent.jpg" in lib.ap_last_error()
     assert lib.ap_host_jpeg_coefficients(buf.ctypes.data, arr, 0, 8, 0) in (0, _lib.AP_ERR_UNSUPPORTED)
+
+
+def test_a_header_libjpeg_warns_about_is_probed_and_its_decode_refused(lib, tmp_path):
+    """Two stray bytes between SOI and the first marker: libjpeg warns (extraneous bytes before a marker) and reads on.  The probe
+    asks nothing of the data and answers as for the clean file; the coefficient reader and the pixel decoder count the warning and
+    refuse the tile, leaving its slot alone (Pillow, on the same code base, raises on such a stream's damage as well)."""
+    from atlaspatch_amd import _lib
+    good = js.encode(js.pixels(64, "mix"), ref.S444, 80)
+    path = tmp_path / "junk.jpg"
+    path.write_bytes(good[:2] + b"\0\0" + good[2:])
+    w, h, s = C.c_int(), C.c_int(), C.c_int()
+    rc = lib.ap_host_jpeg_probe(str(path).encode(), C.byref(w), C.byref(h), C.byref(s))
+    if rc == _lib.AP_ERR_UNSUPPORTED:
+        pytest.skip("no usable libjpeg.so.8 on this host: " + lib.ap_last_error().decode())
+    assert (rc, w.value, h.value, s.value) == (_lib.AP_OK, 64, 64, ref.S444)
+    rc, slots = js.read_slots(lib, [str(path)], 64, ref.S444)
+    assert rc == _lib.AP_ERR_INVALID and b"warning" in lib.ap_last_error() and b"junk.jpg" in lib.ap_last_error()
+    assert (slots == 0xA5).all()
+    px = np.zeros((64, 64, 3), dtype=np.uint8)
+    arr = (C.c_char_p * 1)(str(path).encode())
+    assert lib.ap_host_decode_jpeg_tiles(px.ctypes.data, arr, 1, 64) == _lib.AP_ERR_INVALID and b"warning" in lib.ap_last_error()

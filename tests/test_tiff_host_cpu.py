@@ -320,3 +320,28 @@ def test_factory_routes_only_under_the_switch(tmp_path, monkeypatch):
     w.cleanup()
     with pytest.raises(ValueError, match="JPEG 2000"):
         WSIFactory.load(str(bad), backend="tiff").get_size()
+
+
+def test_a_level_whose_first_tile_header_makes_libjpeg_warn_keeps_its_sampling(lib, tmp_path):
+    """The first tile's APP0 segment is overwritten with zeros: libjpeg warns about the stray bytes and reads the header on.  The
+    level probe asks nothing of the data, so the level keeps its sampling and its device routes; reading THAT tile as coefficients is
+    refused for the warning (the chunk takes the host route), every other tile is delivered."""
+    from atlaspatch_amd import _lib
+    path = tmp_path / "junk.tif"
+    info = tf.write_tiff(path, [tf.image(512, 512, 3)], tables=False)
+    raw, stream = bytearray(path.read_bytes()), info["streams"][0][0][0]
+    at = raw.find(stream[:40])
+    assert at > 0 and stream[2:4] == b"\xff\xe0"
+    length = 2 + int.from_bytes(stream[4:6], "big")
+    raw[at + 2:at + 2 + length] = bytes(length)
+    path.write_bytes(raw)
+    w = _open(path)
+    _need_libjpeg(lib, w)
+    assert w.levels[0]["sampling"] == _lib.AP_JPEG_420
+    slot = np.full(lib.ap_jpeg_slot_bytes(256, 3), 0xA5, dtype=np.uint8)
+    ids = np.array([0], dtype=np.int32)
+    assert lib.ap_host_tiff_tile_coefficients(w._handle, 0, ids.ctypes.data, 1, slot.ctypes.data) == _lib.AP_ERR_INVALID
+    assert b"warning" in lib.ap_last_error() and b"tile (0, 0)" in lib.ap_last_error() and (slot == 0xA5).all()
+    ids[0] = 3
+    assert lib.ap_host_tiff_tile_coefficients(w._handle, 0, ids.ctypes.data, 1, slot.ctypes.data) == 0 and not (slot == 0xA5).all()
+    w.cleanup()

@@ -138,3 +138,157 @@ def test_probe_of_a_backend_without_device_capabilities(monkeypatch):
     monkeypatch.setenv("ATLASPATCH_JPEG_DEVICE", "1")
     plain = SimpleNamespace(extract=lambda *a, **k: None, read_tiles_into=lambda rows, ptr, side: False)
     assert routes_for(plain, _grid_coords(), (256, 256)) == []
+
+
+# ----------------------------------------------------------------------------- the tile sources, without a ring or a device
+POISON = 0xA5
+
+
+def _poisoned(*shape):
+    import torch
+    t = torch.full(shape, POISON, dtype=torch.uint8)
+    assert t.data_ptr() % 16 == 0
+    return t
+
+
+def _sources(monkeypatch, wsi, coords):
+    """(the stream source, the coefficient source, tile slots per row) of the routes ``wsi`` offers under both switches."""
+    from atlaspatch_amd.services import tile_routes as tr
+    monkeypatch.setenv("ATLASPATCH_JPEG_DEVICE", "1")
+    monkeypatch.setenv("ATLASPATCH_JPEG_ENTROPY_DEVICE", "1")
+    stream, coef = tr.routes_for(wsi, coords, (256, 256))
+    assert (type(stream.source), type(coef.source)) == (tr.StreamTiles, tr.CoefficientTiles) and stream.per_row == coef.per_row
+    assert (stream.source.merges, coef.source.merges) == (False, True)
+    return stream.source, coef.source, stream.per_row
+
+
+def _check_fills(stream, coef, per_row, rows_held, start, items, share, direct_coefficients, direct_streams):
+    """``fill`` of both sources for a chunk that starts at coords row ``start`` of a slot of ``rows_held`` rows, on poisoned CPU buffers
+    the test owns: what lands where, against the C entry called directly into fresh buffers, and nothing outside the chunk's share."""
+    import torch
+    m, first, tiles, bound = len(items), start * per_row, rows_held * per_row, stream.bound
+    assert m <= share and first + share <= tiles
+    # coefficient slots: tile slot start * per_row onwards
+    buf = SimpleNamespace(host=[_poisoned(tiles, coef.slot_bytes)])
+    want = _poisoned(m, coef.slot_bytes)
+    assert direct_coefficients(want.data_ptr()) == 0
+    assert coef.fill(buf, 0, first, items, share) is True
+    assert torch.equal(buf.host[0][first:first + m], want) and not (want == POISON).all()
+    assert (buf.host[0][:first] == POISON).all() and (buf.host[0][first + m:] == POISON).all()
+    # descriptors: tile slot start * per_row onwards; the arena share: byte start * per_row * bound onwards, share * bound long
+    buf = SimpleNamespace(desc_host=[_poisoned(tiles, stream.header)], arena_host=[_poisoned(tiles * bound)])
+    descs, arena, used = _poisoned(m, stream.header), _poisoned(share * bound), C.c_size_t()
+    assert direct_streams(descs.data_ptr(), arena.data_ptr(), share * bound, C.byref(used)) == 0 and 0 < used.value <= share * bound
+    assert stream.fill(buf, 0, first, items, share) == used.value
+    assert torch.equal(buf.desc_host[0][first:first + m], descs) and not (descs == POISON).all()
+    assert torch.equal(buf.arena_host[0][first * bound:(first + share) * bound], arena) and not (arena[:used.value] == POISON).all()
+    assert (buf.desc_host[0][:first] == POISON).all() and (buf.desc_host[0][first + m:] == POISON).all()
+    assert (buf.arena_host[0][:first * bound] == POISON).all() and (buf.arena_host[0][(first + share) * bound:] == POISON).all()
+
+
+def _store_or_skip(tmp_path, width):
+    from atlaspatch_amd import _lib
+    from atlaspatch_amd.core.wsi.synth_wsi import SynthWSI
+    slide, coords, _ = jpeg_store(tmp_path, tf.image(width, 256, 21))
+    lib, w, h, s = _lib.load(), C.c_int(), C.c_int(), C.c_int()
+    if lib.ap_host_jpeg_probe(str(tmp_path / "tiles" / "0_0_256.jpg").encode(), C.byref(w), C.byref(h), C.byref(s)) == _lib.AP_ERR_UNSUPPORTED:
+        pytest.skip("no usable libjpeg.so.8 on this host: " + lib.ap_last_error().decode())
+    return lib, SynthWSI(slide), coords
+
+
+def test_the_sources_fill_a_store_chunk_at_its_tile_slot(tmp_path, monkeypatch):
+    """A 4-tile JPEG store, one tile per row; the chunk starts at row 3 of an 8-row slot."""
+    lib, wsi, coords = _store_or_skip(tmp_path, 1024)
+    stream, coef, per_row = _sources(monkeypatch, wsi, coords)
+    assert per_row == 1 and len(coords) == 4
+    paths = [str(tmp_path / "tiles" / f"{x}_{y}_256.jpg").encode() for x, y in coords[:, :2].tolist()]
+    arr = (C.c_char_p * 4)(*paths)
+    _check_fills(stream, coef, 1, 8, 3, coords.tolist(), 4,
+                 lambda slots: lib.ap_host_jpeg_coefficients(slots, arr, 4, 256, coef.sampling),
+                 lambda descs, arena, cap, used: lib.ap_host_jpeg_streams(descs, arena, cap, used, arr, 4, 256, stream.sampling))
+
+
+def test_the_sources_fill_a_tile_grid_chunk_at_its_tile_slot(tmp_path, monkeypatch):
+    """The ts = 240 TIFF: 9 tile slots per row; a chunk of three rows starts at row 2 of a 5-row slot."""
+    from atlaspatch_amd import _lib
+    wsi = _tiff(tmp_path / "t.tif", 240)
+    stream, coef, per_row = _sources(monkeypatch, wsi, _grid_coords())
+    assert per_row == 9
+    rows = _grid_coords()[[1, 6, 11]].tolist()
+    geometry = wsi.tile_gather_geometry(rows, 256)
+    ids, _ = wsi.tile_gather_plan(rows, geometry, 256)
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    lib, m = _lib.load(), int(ids.shape[0])
+    assert 9 < m <= 27, "the chunk's distinct tiles reach past its first row's slots"
+    _check_fills(stream, coef, 9, 5, 2, ids, 27,
+                 lambda slots: lib.ap_host_tiff_tile_coefficients(wsi._handle, 0, ids.ctypes.data, m, slots),
+                 lambda descs, arena, cap, used: lib.ap_host_tiff_tile_streams(wsi._handle, 0, ids.ctypes.data, m, descs, arena, cap, used))
+    wsi.cleanup()
+
+
+def test_a_chunk_the_stager_refuses_fills_to_none(tmp_path, monkeypatch):
+    """The third of four tiles is progressive: both sources refuse the chunk (None).  As at the C entries, the tiles in front of the
+    refused one are staged, its own slot / descriptor and those behind it keep the poison, and nothing outside the share is touched."""
+    from PIL import Image
+    lib, wsi, coords = _store_or_skip(tmp_path, 1024)
+    stream, coef, _ = _sources(monkeypatch, wsi, coords)
+    bad = tmp_path / "tiles" / "512_0_256.jpg"
+    with Image.open(bad) as im:
+        im.convert("RGB").save(str(bad), quality=80, progressive=True)
+    bound, first = stream.bound, 3
+    buf = SimpleNamespace(host=[_poisoned(8, coef.slot_bytes)], desc_host=[_poisoned(8, stream.header)], arena_host=[_poisoned(8 * bound)])
+    assert coef.fill(buf, 0, first, coords.tolist(), 4) is None and b"progressive" in lib.ap_last_error()
+    assert stream.fill(buf, 0, first, coords.tolist(), 4) is None and b"progressive" in lib.ap_last_error()
+    for held in (buf.host[0], buf.desc_host[0]):
+        assert not (held[first] == POISON).all() and not (held[first + 1] == POISON).all()
+        assert (held[:first] == POISON).all() and (held[first + 2:] == POISON).all()
+    assert (buf.arena_host[0][:first * bound] == POISON).all() and (buf.arena_host[0][(first + 4) * bound:] == POISON).all()
+    # inside the share: byte for byte what the C entry leaves behind a refusal at the same capacity -- the two tiles in front staged,
+    # *arena_used standing behind them (not 0, not the whole share) -- while the source's answer is None
+    import torch
+    arr = (C.c_char_p * 4)(*[str(tmp_path / "tiles" / f"{x}_{y}_256.jpg").encode() for x, y in coords[:, :2].tolist()])
+    descs, arena, used = _poisoned(4, stream.header), _poisoned(4 * bound), C.c_size_t()
+    assert lib.ap_host_jpeg_streams(descs.data_ptr(), arena.data_ptr(), 4 * bound, C.byref(used), arr, 4, 256, stream.sampling) != 0
+    assert 0 < used.value < 4 * bound and used.value % 16 == 0
+    assert torch.equal(buf.desc_host[0][first:first + 4], descs) and torch.equal(buf.arena_host[0][first * bound:(first + 4) * bound], arena)
+    assert not (arena[:used.value] == POISON).all()
+
+
+def _unprepared(route, rows_held):
+    """``route`` with the pinned half of its buffer set made here from poisoned CPU tensors, as ``prepare`` would on a ring."""
+    tiles, source = rows_held * route.per_row, route.source
+    held = dict(host=[_poisoned(tiles, route.slot_bytes)]) if not source.flags else \
+        dict(desc_host=[_poisoned(tiles, source.header)], arena_host=[_poisoned(tiles * source.bound)])
+    route.buf = SimpleNamespace(**held)
+    route.plan_np = [np.full((rows_held, 4 + route.per_row), -9, dtype=np.int32)]
+    return route.buf
+
+
+def test_the_routes_hand_their_sources_the_row_index_in_tile_slots(tmp_path, monkeypatch):
+    """``fill`` of the routes themselves: a store route's chunk at row 3 lands at tile slot 3, a tile-grid route's chunk at row 2 at
+    tile slot 2 * 9 with its plan in rows 2 .. 4, and each equals its source's ``fill`` at that slot."""
+    import torch
+    from atlaspatch_amd.services import tile_routes as tr
+    lib, store, coords = _store_or_skip(tmp_path / "s", 1024)
+    wsi = _tiff(tmp_path / "t.tif", 240)
+    monkeypatch.setenv("ATLASPATCH_JPEG_DEVICE", "1")
+    monkeypatch.setenv("ATLASPATCH_JPEG_ENTROPY_DEVICE", "1")
+    grid_rows = _grid_coords()[[1, 6, 11]].tolist()
+    for routes, rows, start in ((tr.routes_for(store, coords, (256, 256)), coords.tolist(), 3),
+                                (tr.routes_for(wsi, _grid_coords(), (256, 256)), grid_rows, 2)):
+        for route in routes:
+            per_row, source = route.per_row, route.source
+            buf = _unprepared(route, 8)
+            token, plan = route.fill(0, start, rows), route.plan_np[0]
+            items, staged = (rows, token) if per_row == 1 else (wsi.tile_gather_plan(rows, route.geometry, 256)[0], token[1])
+            want = _unprepared(route, 8)
+            assert source.fill(want, 0, start * per_row, items, len(rows) * per_row) == staged and staged is not None
+            for name, got in vars(buf).items():
+                assert torch.equal(got[0], getattr(want, name)[0]) and not (got[0] == POISON).all(), (type(route), name)
+            if per_row > 1:
+                assert token[0] == len(items) and (plan[:start] == -9).all() and (plan[start + 3:] == -9).all()
+                assert np.array_equal(plan[start:start + 3], wsi.tile_gather_plan(rows, route.geometry, 256)[1])
+            first = start * per_row
+            head = buf.host[0] if not source.flags else buf.desc_host[0]
+            assert (head[:first] == POISON).all() and not (head[first] == POISON).all()
+    wsi.cleanup()

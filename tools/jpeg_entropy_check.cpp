@@ -165,7 +165,7 @@ int main(int argc, char** argv) {
         const int side = w;
         JpegGeom g;
         jpeg_geom(side, sampling, &g);
-        const bool in_subset = side % (8 * g.hmax) == 0 && side % (8 * g.vmax) == 0 && side <= kJpegEntropyMaxSide;
+        const bool in_subset = side % (8 * g.hmax) == 0 && side % (8 * g.vmax) == 0 && side <= kJpegDeviceMaxSide;
         // the file as it is; a restart-marker or progressive file is refused by the stager, which check_stream counts
         const size_t before = (size_t)g_refused;
         check_stream(path, stream, side, sampling, scratch, false);

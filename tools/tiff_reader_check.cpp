@@ -3,7 +3,8 @@
 // copy and the slot copy.  CPU only, no device work.
 //
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
-//         -x hip tools/tiff_reader_check.cpp atlaspatch_amd/csrc/tiff_host.cpp atlaspatch_amd/csrc/jpeg_host.cpp -ldl -o tiff_reader_check
+//         -x hip tools/tiff_reader_check.cpp atlaspatch_amd/csrc/tiff_host.cpp atlaspatch_amd/csrc/jpeg_host.cpp \
+//         atlaspatch_amd/csrc/jpeg_stream_host.cpp -ldl -o tiff_reader_check
 //   ./tiff_reader_check FILE.tif ...
 //
 // Every file is opened; an accepted file has, per level, its corner patches (overhanging all four corners, and one in the
