@@ -32,7 +32,17 @@ class HipLibraryError(RuntimeError):
     pass
 
 
-ABI_VERSION = 20                # include/atlaspatch_hip.h: AP_ABI_VERSION; load() refuses a library that reports another
+AP_JPEG_STREAM_RESTART = 1       # flag of the *_streams_ex stagers: admit restart intervals (decoded by ap_jpeg_entropy_decode_tiles_rst)
+
+
+def jpeg_restart_table_bound(side: int, sampling: int) -> int:
+    """Arena bytes the restart table of one ``side`` x ``side`` tile can take: 4 per MCU (an interval of one MCU), rounded up to 16."""
+    hmax, vmax = (2 if sampling in (AP_JPEG_422, AP_JPEG_420) else 1), (2 if sampling == AP_JPEG_420 else 1)
+    mcus = -(-int(side) // (8 * hmax)) * -(-int(side) // (8 * vmax))
+    return (4 * mcus + 15) // 16 * 16
+
+
+ABI_VERSION = 20               # include/atlaspatch_hip.h: AP_ABI_VERSION; load() refuses a library that reports another
 
 
 class VitConfig(C.Structure):
@@ -137,6 +147,10 @@ SIGNATURES = {
                                                C.c_int, C.c_void_p]),
     "ap_jpeg_entropy_decode_tiles_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_int, C.c_void_p]),
+    "ap_host_jpeg_streams_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_char_p), C.c_int, C.c_int,
+                                          C.c_int, C.c_int]),
+    "ap_jpeg_entropy_decode_tiles_rst": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                   C.c_int, C.c_void_p]),
     "ap_host_format_passports": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_void_p, C.c_int]),
     "ap_host_gather_tiles": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_size_t]),
     "ap_host_synth_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
@@ -322,6 +336,8 @@ SIGNATURES = {
     "ap_host_tiff_max_tile_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "ap_host_tiff_tile_streams": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                             C.POINTER(C.c_size_t)]),
+    "ap_host_tiff_tile_streams_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                               C.POINTER(C.c_size_t), C.c_int]),
     "ap_gather_patches": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p]),
 }

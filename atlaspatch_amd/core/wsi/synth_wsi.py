@@ -255,7 +255,10 @@ class SynthWSI(IWSI):
     def jpeg_stream_bound(self, rows, tile_side: int) -> Optional[int]:
         """Optional IWSI capability beside ``jpeg_coefficient_sampling``, switched on by ATLASPATCH_JPEG_ENTROPY_DEVICE=1 on top of
         ATLASPATCH_JPEG_DEVICE=1: the arena bytes one tile of this slide's JPEG store can need when its compressed stream crosses the
-        ring (``read_streams_into``) -- the store's largest file size, rounded up to 16, found without reading a tile -- else None."""
+        ring (``read_streams_into``) -- the store's largest file size, rounded up to 16, found without reading a tile -- else None.
+        With ATLASPATCH_JPEG_RESTART_DEVICE=1 on top of the two, tiles with restart intervals are staged too, and the bound grows by
+        the room their restart table can take: 4 bytes per MCU of a ``tile_side`` frame at the store's sampling, rounded up to 16."""
+        from ... import _lib
         from ...utils.env import env_flag
         self._ensure_loaded()
         if self.jpeg_dir is None or not env_flag("ATLASPATCH_JPEG_DEVICE") or not env_flag("ATLASPATCH_JPEG_ENTROPY_DEVICE"):
@@ -265,21 +268,31 @@ class SynthWSI(IWSI):
             with os.scandir(self.jpeg_dir) as entries:
                 most = max((e.stat().st_size for e in entries if e.name.endswith(".jpg")), default=0)
             bound = self._jpeg_stream_bound = (most + 15) // 16 * 16
+        if bound and env_flag("ATLASPATCH_JPEG_RESTART_DEVICE"):
+            sampling = self.jpeg_coefficient_sampling(rows, tile_side)
+            bound += _lib.jpeg_restart_table_bound(tile_side, _lib.AP_JPEG_444 if sampling is None else sampling)
         return bound or None
 
     def read_streams_into(self, rows, descs_ptr: int, arena_ptr: int, arena_cap: int, tile_side: int, sampling: int) -> Optional[int]:
         """Stage the JPEG tiles of ``rows`` as stream descriptors at ``descs_ptr`` and unstuffed payloads in the arena at ``arena_ptr``
         (``arena_cap`` bytes) in ONE call outside the interpreter lock (``ap_host_jpeg_streams``: no libjpeg, one pass over the bytes);
         returns the arena bytes used, or None: a tile the store lacks, a progressive tile, restart markers, another sampling or size, a
-        side that is no multiple of the MCU size, or an arena that would overflow.  The caller then asks the next route."""
+        side that is no multiple of the MCU size, or an arena that would overflow.  The caller then asks the next route.  With
+        ATLASPATCH_JPEG_RESTART_DEVICE=1 the stager is ``ap_host_jpeg_streams_ex`` with ``AP_JPEG_STREAM_RESTART``: restart intervals
+        whose markers are in order are staged with their restart table, and only damaged ones are refused."""
         import ctypes as C
         from ... import _lib
+        from ...utils.env import env_flag
         self._ensure_loaded()
         arr = self._store_files(rows) if self.jpeg_dir is not None and rows and common_level(rows, tile_side) == 0 else None
         if arr is None:
             return None
         used = C.c_size_t()
-        code = _lib.load().ap_host_jpeg_streams(descs_ptr, arena_ptr, int(arena_cap), C.byref(used), arr, len(rows), tile_side, int(sampling))
+        if env_flag("ATLASPATCH_JPEG_RESTART_DEVICE"):
+            code = _lib.load().ap_host_jpeg_streams_ex(descs_ptr, arena_ptr, int(arena_cap), C.byref(used), arr, len(rows), tile_side,
+                                                       int(sampling), _lib.AP_JPEG_STREAM_RESTART)
+        else:
+            code = _lib.load().ap_host_jpeg_streams(descs_ptr, arena_ptr, int(arena_cap), C.byref(used), arr, len(rows), tile_side, int(sampling))
         if code == _lib.AP_ERR_INVALID:
             return None
         _lib.check(code, "ap_host_jpeg_streams")

@@ -254,24 +254,35 @@ class TiffWSI(IWSI):
     def tile_stream_bound(self, geometry: dict) -> Optional[int]:
         """Optional IWSI capability beside ``tile_gather_geometry``, switched on by ATLASPATCH_JPEG_ENTROPY_DEVICE=1 on top of
         ATLASPATCH_JPEG_DEVICE=1: the arena bytes one tile of the geometry's level can need when its compressed stream crosses the ring
-        (``read_tile_streams_into``) -- the level's largest TileByteCounts entry, rounded up to 16 -- else None."""
+        (``read_tile_streams_into``) -- the level's largest TileByteCounts entry, rounded up to 16 -- else None.  With
+        ATLASPATCH_JPEG_RESTART_DEVICE=1 on top of the two, tiles with restart intervals are staged too, and the bound grows by the
+        room their restart table can take: 4 bytes per MCU of a tile at the level's sampling, rounded up to 16."""
         from ... import _lib
         from ...utils.env import env_flag
         if not env_flag("ATLASPATCH_JPEG_DEVICE") or not env_flag("ATLASPATCH_JPEG_ENTROPY_DEVICE"):
             return None
-        return int(_lib.load().ap_host_tiff_max_tile_bytes(self._handle, int(geometry["level"]))) or None
+        bound = int(_lib.load().ap_host_tiff_max_tile_bytes(self._handle, int(geometry["level"])))
+        if bound and env_flag("ATLASPATCH_JPEG_RESTART_DEVICE"):
+            bound += _lib.jpeg_restart_table_bound(int(geometry["ts"]), int(geometry["sampling"]))
+        return bound or None
 
     def read_tile_streams_into(self, tile_ids: np.ndarray, geometry: dict, descs_ptr: int, arena_ptr: int, arena_cap: int) -> Optional[int]:
         """Stage the tiles ``tile_ids`` of the geometry's level as stream descriptors at ``descs_ptr`` and unstuffed payloads in the arena
         at ``arena_ptr`` in ONE call outside the interpreter lock (``ap_host_tiff_tile_streams``: pread straight into the arena, no
         libjpeg); returns the arena bytes used, or None: a progressive tile, restart markers, another sampling, an arena that would
-        overflow.  The caller then asks the next route."""
+        overflow.  The caller then asks the next route.  With ATLASPATCH_JPEG_RESTART_DEVICE=1 the stager is
+        ``ap_host_tiff_tile_streams_ex`` with ``AP_JPEG_STREAM_RESTART``, which stages restart intervals whose markers are in order."""
         import ctypes as C
         from ... import _lib
+        from ...utils.env import env_flag
         ids = np.ascontiguousarray(tile_ids, dtype=np.int32)
         used = C.c_size_t()
-        code = _lib.load().ap_host_tiff_tile_streams(self._handle, int(geometry["level"]), ids.ctypes.data, ids.shape[0], descs_ptr, arena_ptr,
-                                                     int(arena_cap), C.byref(used))
+        if env_flag("ATLASPATCH_JPEG_RESTART_DEVICE"):
+            code = _lib.load().ap_host_tiff_tile_streams_ex(self._handle, int(geometry["level"]), ids.ctypes.data, ids.shape[0], descs_ptr,
+                                                            arena_ptr, int(arena_cap), C.byref(used), _lib.AP_JPEG_STREAM_RESTART)
+        else:
+            code = _lib.load().ap_host_tiff_tile_streams(self._handle, int(geometry["level"]), ids.ctypes.data, ids.shape[0], descs_ptr,
+                                                         arena_ptr, int(arena_cap), C.byref(used))
         if code in (_lib.AP_ERR_UNSUPPORTED, _lib.AP_ERR_INVALID):
             return None
         _lib.check(code, "ap_host_tiff_tile_streams")

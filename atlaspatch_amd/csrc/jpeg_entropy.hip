@@ -12,8 +12,16 @@
 // workgroup, two workgroups per CU).  Measured: on noise-rich 4:2:0 tiles a subsequence of the default length
 // holds less than one MCU, the block-in-MCU phase of a guessed state does not re-synchronise, and the loop runs about S rounds: the
 // kernel is then as slow as one sequential pass per tile.  The fixes named there are not built.
+//
+// ap_jpeg_entropy_decode_tiles_rst takes launches that mix such tiles with tiles that carry restart intervals (jpeg_stream.h:
+// restart_interval != 0), which are decoded an interval per lane by the passes of jpeg_restart_core.h in a kernel of their own: its LDS
+// is the four tables and a few words (under 4 KB), so it keeps an occupancy the 54.6 KB of the kernel above cannot.  The device cannot
+// tell the host which kind a tile is without a copy, so both kernels are launched over the n tiles and a workgroup whose tile is
+// not of its kind returns on a uniform branch after reading the descriptor's restart fields.  For the other entries the first kernel is instantiated
+// without that branch: it is the kernel they always ran.
 #include "ap_common.h"
 #include "jpeg_entropy_core.h"
+#include "jpeg_restart_core.h"
 
 namespace ap {
 namespace {
@@ -28,9 +36,12 @@ struct EntropyArgs {
     int side, sampling, subsequence_bits, max_rounds;
 };
 
+// kMixed: the launch may hold restart tiles, which are jpeg_restart_kernel's
+template <bool kMixed>
 __global__ __launch_bounds__(kEntropyLanes) void jpeg_entropy_kernel(EntropyArgs a) {
     __shared__ EntropyShared sh;
     const int lane = (int)threadIdx.x, nl = kEntropyLanes, tile = (int)blockIdx.x;
+    if (kMixed && restart_fields_set(a.descs + tile)) return;
     EntropyTile T;
     entropy_tile(a.descs + tile, a.arena, a.arena_bytes, a.slots + (size_t)tile * a.slot_bytes, a.side, a.sampling, a.subsequence_bits, &T);
     if (lane == 0) entropy_pass0_clear(&sh);
@@ -59,12 +70,25 @@ __global__ __launch_bounds__(kEntropyLanes) void jpeg_entropy_kernel(EntropyArgs
     if (lane == 0) a.status[tile] = entropy_pass5_status(T, &sh);
 }
 
-}  // namespace
-}  // namespace ap
+__global__ __launch_bounds__(kEntropyLanes) void jpeg_restart_kernel(EntropyArgs a) {
+    __shared__ RestartShared sh;
+    const int lane = (int)threadIdx.x, nl = kEntropyLanes, tile = (int)blockIdx.x;
+    if (!restart_fields_set(a.descs + tile)) return;
+    RestartTile R;
+    restart_tile(a.descs + tile, a.arena, a.arena_bytes, a.slots + (size_t)tile * a.slot_bytes, a.side, a.sampling, &R);
+    if (lane == 0) restart_pass0_clear(&sh);
+    __syncthreads();
+    restart_pass0_tables(R, &sh, lane);
+    entropy_pass0_slot(R.T, lane, nl);
+    __syncthreads();
+    restart_pass_decode(R, &sh, lane, nl);
+    __syncthreads();
+    if (lane == 0) a.status[tile] = restart_pass_status(R, &sh);
+}
 
-extern "C" int ap_jpeg_entropy_decode_tiles_ex(const void* descs, const void* arena, size_t arena_bytes, int n, int side, int sampling,
-                                               void* slots, int32_t* status, int subsequence_bits, ap_stream_t stream) {
-    using namespace ap;
+// the argument checks and the launch of every entry; `mixed`: restart tiles are decoded by their own kernel
+int entropy_launch(const void* descs, const void* arena, size_t arena_bytes, int n, int side, int sampling, void* slots, int32_t* status,
+                   int subsequence_bits, ap_stream_t stream, bool mixed) {
     AP_REQUIRE(descs && arena && slots && status, "ap_jpeg_entropy_decode_tiles: null pointer");
     AP_REQUIRE(n >= 0, "ap_jpeg_entropy_decode_tiles: bad n %d", n);
     AP_REQUIRE((((uintptr_t)descs | (uintptr_t)arena | (uintptr_t)slots) & 15) == 0,
@@ -90,9 +114,29 @@ extern "C" int ap_jpeg_entropy_decode_tiles_ex(const void* descs, const void* ar
     // no tile has more subsequences than its payload has words, nor than the state arrays hold: the bound of the synchronisation loop
     const size_t words = arena_bytes / 4 + 1;
     a.max_rounds = (int)(words < (size_t)kEntropyMaxSubseq ? words : (size_t)kEntropyMaxSubseq);
-    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)n), dim3(kEntropyLanes), 0, (hipStream_t)stream, a);
+    if (!mixed) {
+        hipLaunchKernelGGL(jpeg_entropy_kernel<false>, dim3((unsigned)n), dim3(kEntropyLanes), 0, (hipStream_t)stream, a);
+        AP_HIP_CHECK(hipGetLastError());
+        return AP_OK;
+    }
+    hipLaunchKernelGGL(jpeg_entropy_kernel<true>, dim3((unsigned)n), dim3(kEntropyLanes), 0, (hipStream_t)stream, a);
+    AP_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_restart_kernel, dim3((unsigned)n), dim3(kEntropyLanes), 0, (hipStream_t)stream, a);
     AP_HIP_CHECK(hipGetLastError());
     return AP_OK;
+}
+
+}  // namespace
+}  // namespace ap
+
+extern "C" int ap_jpeg_entropy_decode_tiles_ex(const void* descs, const void* arena, size_t arena_bytes, int n, int side, int sampling,
+                                               void* slots, int32_t* status, int subsequence_bits, ap_stream_t stream) {
+    return ap::entropy_launch(descs, arena, arena_bytes, n, side, sampling, slots, status, subsequence_bits, stream, false);
+}
+
+extern "C" int ap_jpeg_entropy_decode_tiles_rst(const void* descs, const void* arena, size_t arena_bytes, int n, int side, int sampling,
+                                                void* slots, int32_t* status, int subsequence_bits, ap_stream_t stream) {
+    return ap::entropy_launch(descs, arena, arena_bytes, n, side, sampling, slots, status, subsequence_bits, stream, true);
 }
 
 // the four codes this entry was published with; AP_JPEG_RGB stays an unknown sampling here

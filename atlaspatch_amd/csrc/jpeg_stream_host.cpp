@@ -6,19 +6,27 @@
 // is refused with its reason, and the caller's next route (coefficients, then pixels) takes the tile:
 //   baseline sequential Huffman (SOF0), 8 bit; one scan with every component, in frame order; greyscale, YCbCr at 4:4:4 / 4:2:2
 //   (2x1) / 4:2:0 (2x2) with 1x1 chroma, or RGB coded with three 1x1 components; the requested side and sampling; a side that is a
-//   multiple of the MCU size and <= 976 (jpeg_slot.h: kJpegDeviceMaxSide); no restart interval and no RSTn marker; Huffman tables 0 / 1 that exist and form a
-//   canonical code the way libjpeg checks it (jdhuff.c: jpeg_make_d_derived_tbl), DC categories <= 15.
+//   multiple of the MCU size and <= 976 (jpeg_slot.h: kJpegDeviceMaxSide); Huffman tables 0 / 1 that exist and form a canonical
+//   code the way libjpeg checks it (jdhuff.c: jpeg_make_d_derived_tbl), DC categories <= 15; no restart interval and no RSTn marker
+//   through ap_host_jpeg_streams / ap_host_tiff_tile_streams and through their _ex twins at flags 0.  With AP_JPEG_STREAM_RESTART the
+//   _ex entries admit a DRI segment.  The one in force is the stream's own: a JPEGTables preset may hold one, but the tile's SOI resets
+//   it, as libjpeg's does.  An interval of 0, or of at least the frame's MCU count, is a restart-free tile; otherwise the scan must
+//   hold exactly ceil(MCUs / interval) - 1 markers, numbered RST0, RST1, ... modulo 8 in order, none at the scan's start, behind
+//   another marker or directly in front of the scan's end -- what libjpeg would warn about, and the host reader refuses on warnings.
+//   A restart marker outside a scan stays refused.
 // The colour space is inferred as libjpeg does (jdapimin.c: default_decompress_parms): JFIF -> YCbCr; Adobe transform 0 -> RGB;
 // neither: component ids 'R' 'G' 'B' -> RGB -- unless the container decides it (jpeg_host.h: kJpegColourRgb, a TIFF level tagged
 // Photometric 2: RGB whatever the markers say).  RGB is admitted when AP_JPEG_RGB was asked for and refused under any other code;
 // a YCbCr stream asked for as AP_JPEG_RGB is refused.
 //
-// The entropy-coded segment is walked once, memchr from FF to FF: FF 00 -> FF, FF FF -> fill, FF D0..D7 -> refused, any other marker
-// (or the end of the buffer: a truncated tile, which the device flags) ends it.  Destination <= source, so the pass runs in place when
-// the tile was read straight into the arena.
+// The entropy-coded segment is walked once, memchr from FF to FF: FF 00 -> FF, FF FF -> fill, FF D0..D7 -> refused, or on a restart
+// tile dropped with the payload offset behind it noted as the next interval's start, any other marker (or the end of the buffer: a
+// truncated tile, which the device flags) ends it.  Destination <= source, so the pass runs in place when the tile was read straight
+// into the arena; the restart table is written behind the payload only when the pass is through.
 #include <sys/stat.h>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 #include "ap_common.h"
 #include "jpeg_host.h"
 #include "jpeg_slot.h"
@@ -169,10 +177,14 @@ int jpeg_stream_tables(const unsigned char* tables, size_t tables_size, JpegStre
 }
 
 int jpeg_stream_stage(const JpegStreamTables* preset, const unsigned char* data, size_t size, int want_side, int want_sampling,
-                      JpegStreamDesc* desc, unsigned char* arena, size_t arena_cap, size_t* used, char* why, size_t why_cap, int colour) {
+                      JpegStreamDesc* desc, unsigned char* arena, size_t arena_cap, size_t* used, char* why, size_t why_cap, int colour,
+                      int flags) {
     constexpr int kInvalid = AP_ERR_INVALID;
     Tables t;
     if (preset) t = *preset;
+    // libjpeg resets the restart interval at every SOI (jdmarker.c: get_soi), so under a JPEGTables stream with a DRI segment the interval
+    // in force is still the tile's own; the entries without the flag keep refusing such a level, as they always did
+    if (flags & kJpegStreamRestart) t.restart = 0;
     Walk w{data, size, 0, why, why_cap};
 #define refuse(...) (w.fail(__VA_ARGS__), kInvalid)
     if (size < 2 || data[0] != 0xFF || data[1] != 0xD8) return refuse("not a JPEG stream");
@@ -240,7 +252,24 @@ int jpeg_stream_stage(const JpegStreamTables* preset, const unsigned char* data,
         return kInvalid;
     if (want_side > kJpegDeviceMaxSide) return refuse("side %ld is above the device decoder's %ld", want_side, kJpegDeviceMaxSide);
     if (want_side % (8 * g.hmax) || want_side % (8 * g.vmax)) return refuse("side %ld is no multiple of the MCU size", want_side);
-    if (t.restart) return refuse("restart interval %ld", (long)t.restart);
+    // MCUs per restart interval; 0: a restart-free tile, which an interval that covers the whole frame is as well
+    const size_t mcus = (size_t)(want_side / (8 * g.hmax)) * (size_t)(want_side / (8 * g.vmax));
+    size_t interval = 0, intervals = 0;
+    if (t.restart) {
+        if (!(flags & kJpegStreamRestart)) return refuse("restart interval %ld", (long)t.restart);
+        if (t.restart < mcus) {
+            interval = t.restart;
+            intervals = (mcus + interval - 1) / interval;
+        }
+    }
+    // entry k: where interval k starts in the payload.  One buffer per thread, kept from tile to tile: no allocation per tile
+    thread_local std::vector<uint32_t> starts;
+    starts.clear();
+    if (interval) {
+        starts.reserve(intervals);
+        starts.push_back(0);
+    }
+    size_t markers = 0;
     for (int c = 0; c < f.ncomp; ++c)
         if (!t.have_quant[f.tq[c]]) return refuse("component %ld selects a quantisation table that does not exist", c);
     // ---- the entropy-coded segment, unstuffed, to arena + *used
@@ -266,15 +295,34 @@ int jpeg_stream_stage(const JpegStreamTables* preset, const unsigned char* data,
         } else if (nx == 0xFF) {
             i += 1;
         } else if (nx >= 0xD0 && nx <= 0xD7) {
-            return refuse("restart marker in the scan");
+            if (!interval) return refuse("restart marker in the scan");
+            if (nx - 0xD0 != (int)(markers & 7)) return refuse("restart marker RST%ld where RST%ld is due", nx - 0xD0, (long)(markers & 7));
+            ++markers;
+            if (markers < intervals) {
+                if (o == starts.back()) return refuse("restart interval %ld is empty", (long)(markers - 1));
+                starts.push_back((uint32_t)o);
+            }
+            i += 2;
         } else {
             break;
         }
     }
     if (o > kJpegStreamMaxPayload) return refuse("entropy-coded segment of %ld bytes", (long)o);
-    const size_t padded = (o + 15) & ~(size_t)15;
+    if (interval) {
+        if (markers != intervals - 1) return refuse("restart markers: %ld found, %ld expected", (long)markers, (long)(intervals - 1));
+        if (o == starts.back()) return refuse("restart marker directly in front of the end of the scan");
+    }
+    size_t padded = (o + 15) & ~(size_t)15;
     if (padded > room) return refuse("the arena would overflow");
+    const size_t table_at = padded, table_bytes = (4 * intervals + 15) & ~(size_t)15;
+    if (table_bytes > room - padded) return refuse("the arena would overflow");
     memset(out + o, 0, padded - o);
+    if (interval) {                                                // the payload is final: the source bytes are not read again
+        memset(out + table_at, 0, table_bytes);
+        for (size_t k = 0; k < intervals; ++k)
+            for (int b = 0; b < 4; ++b) out[table_at + 4 * k + b] = (unsigned char)(starts[k] >> (8 * b));
+        padded += table_bytes;
+    }
     // ---- the descriptor
     memset(desc, 0, sizeof(*desc));
     for (int c = 0; c < f.ncomp; ++c) {
@@ -290,6 +338,11 @@ int jpeg_stream_stage(const JpegStreamTables* preset, const unsigned char* data,
     desc->ncomp = (uint32_t)f.ncomp;
     desc->payload_bytes = (uint32_t)o;
     desc->payload_offset = start;
+    if (interval) {
+        desc->restart_interval = (uint32_t)interval;
+        desc->restart_count = (uint32_t)intervals;
+        desc->restart_table_offset = start + table_at;
+    }
     *used = start + padded;
     return 0;
 #undef refuse
@@ -312,8 +365,9 @@ extern "C" int ap_host_jpeg_stream_bound(const char* const* paths, int n, size_t
     return AP_OK;
 }
 
-extern "C" int ap_host_jpeg_streams(void* descs, void* arena, size_t arena_cap, size_t* arena_used, const char* const* paths, int n,
-                                    int side, int sampling) {
+// ap_host_jpeg_streams and its _ex twin: one body, one set of messages
+static int stage_files(void* descs, void* arena, size_t arena_cap, size_t* arena_used, const char* const* paths, int n, int side,
+                       int sampling, int flags) {
     AP_REQUIRE(descs && arena && arena_used && (paths || n == 0) && n >= 0, "ap_host_jpeg_streams: bad arguments");
     AP_REQUIRE(((uintptr_t)arena & 15) == 0 && ((uintptr_t)descs & 15) == 0, "ap_host_jpeg_streams: descs and arena must be 16-byte aligned");
     AP_REQUIRE(ap_jpeg_slot_bytes_ex(side, sampling), "ap_host_jpeg_streams: bad side %d or sampling %d", side, sampling);
@@ -336,11 +390,22 @@ extern "C" int ap_host_jpeg_streams(void* descs, void* arena, size_t arena_cap, 
         AP_REQUIRE(got > 0, "ap_host_jpeg_streams: short read of %s", paths[i]);
         char why[200] = "";
         if (ap::jpeg_stream_stage(nullptr, at, got, side, sampling, (ap::JpegStreamDesc*)descs + i, (unsigned char*)arena, arena_cap,
-                                  &used, why, sizeof(why)) != 0) {
+                                  &used, why, sizeof(why), 0, flags) != 0) {
             ap::set_error("ap_host_jpeg_streams: %s: %s", paths[i], why);
             return AP_ERR_INVALID;
         }
         *arena_used = used;
     }
     return AP_OK;
+}
+
+extern "C" int ap_host_jpeg_streams(void* descs, void* arena, size_t arena_cap, size_t* arena_used, const char* const* paths, int n,
+                                    int side, int sampling) {
+    return stage_files(descs, arena, arena_cap, arena_used, paths, n, side, sampling, 0);
+}
+
+extern "C" int ap_host_jpeg_streams_ex(void* descs, void* arena, size_t arena_cap, size_t* arena_used, const char* const* paths, int n,
+                                       int side, int sampling, int flags) {
+    AP_REQUIRE((flags & ~AP_JPEG_STREAM_RESTART) == 0, "ap_host_jpeg_streams_ex: unknown flags %d", flags);
+    return stage_files(descs, arena, arena_cap, arena_used, paths, n, side, sampling, flags);
 }

@@ -469,8 +469,9 @@ extern "C" size_t ap_host_tiff_max_tile_bytes(const ap_tiff* slide, int level) {
     return (size_t)((most + 15) & ~(uint64_t)15);
 }
 
-extern "C" int ap_host_tiff_tile_streams(const ap_tiff* slide, int level, const int32_t* tile_ids, int m, void* descs, void* arena,
-                                         size_t arena_cap, size_t* arena_used) {
+// ap_host_tiff_tile_streams and its _ex twin: one body, one set of messages
+static int stage_tiles(const ap_tiff* slide, int level, const int32_t* tile_ids, int m, void* descs, void* arena, size_t arena_cap,
+                       size_t* arena_used, int flags) {
     AP_REQUIRE(slide && arena_used && (m == 0 || (tile_ids && descs && arena)) && m >= 0, "ap_host_tiff_tile_streams: bad arguments");
     AP_REQUIRE((((uintptr_t)arena | (uintptr_t)descs) & 15) == 0, "ap_host_tiff_tile_streams: descs and arena must be 16-byte aligned");
     AP_REQUIRE(level >= 0 && (size_t)level < slide->levels.size(), "ap_host_tiff_tile_streams: level %d of %zu", level, slide->levels.size());
@@ -497,7 +498,7 @@ extern "C" int ap_host_tiff_tile_streams(const ap_tiff* slide, int level, const 
         if (bytes > arena_cap - used) snprintf(why, sizeof(why), "the arena would overflow");
         else if (!pread_all(slide->fd, lv.off[(size_t)id], at, bytes)) snprintf(why, sizeof(why), "short read");
         else rc = ap::jpeg_stream_stage(&tables, at, (size_t)bytes, (int)lv.tw, lv.sampling, (ap::JpegStreamDesc*)descs + i, (unsigned char*)arena,
-                                        arena_cap, &used, why, sizeof(why), lv.colour());
+                                        arena_cap, &used, why, sizeof(why), lv.colour(), flags);
         if (rc != AP_OK) {
             ap::set_error("ap_host_tiff_tile_streams: level %d tile (%lld, %lld): %s", level, tx, ty, why);
             return rc;
@@ -505,4 +506,15 @@ extern "C" int ap_host_tiff_tile_streams(const ap_tiff* slide, int level, const 
         *arena_used = used;
     }
     return AP_OK;
+}
+
+extern "C" int ap_host_tiff_tile_streams(const ap_tiff* slide, int level, const int32_t* tile_ids, int m, void* descs, void* arena,
+                                         size_t arena_cap, size_t* arena_used) {
+    return stage_tiles(slide, level, tile_ids, m, descs, arena, arena_cap, arena_used, 0);
+}
+
+extern "C" int ap_host_tiff_tile_streams_ex(const ap_tiff* slide, int level, const int32_t* tile_ids, int m, void* descs, void* arena,
+                                            size_t arena_cap, size_t* arena_used, int flags) {
+    AP_REQUIRE((flags & ~AP_JPEG_STREAM_RESTART) == 0, "ap_host_tiff_tile_streams_ex: unknown flags %d", flags);
+    return stage_tiles(slide, level, tile_ids, m, descs, arena, arena_cap, arena_used, flags);
 }

@@ -43,6 +43,8 @@ TIFF_TILES = {"device": 0, "host": 0, "patches": 0}
 # ap_jpeg_entropy_decode_tiles does the Huffman decode as well.  "device" = tiles it decoded (distinct tiles per chunk for a tile grid),
 # "patches" = patches gathered from them, "refused" = tiles / patches of chunks the stream stager refused (they took the next route),
 # "flagged" = tiles the device decoder flagged, "rerun" = tiles / patches of the batches that were run again without the route.
+# ATLASPATCH_JPEG_RESTART_DEVICE=1 on top of the two makes the same routes take tiles with restart intervals (the *_streams_ex stagers,
+# ap_jpeg_entropy_decode_tiles_rst); they are counted here like every other tile of the route.
 JPEG_STREAM_TILES = {"device": 0, "refused": 0, "flagged": 0, "rerun": 0}
 TIFF_STREAM_TILES = {"device": 0, "patches": 0, "refused": 0, "flagged": 0, "rerun": 0}
 # csrc/jpeg_slot.h: kJpegDeviceMaxSide, the widest tile ap_jpeg_decode_tiles takes at every sampling (a band of it lies in one workgroup's LDS)
@@ -187,13 +189,17 @@ class StreamTiles(_TileSource):
     unstuffed entropy-coded segment are staged and copied, ``ap_jpeg_entropy_decode_tiles`` makes the coefficient slots in HBM.  A chunk
     owns ``bound`` arena bytes for each of its tile slots and its descriptors' offsets are relative to that share, so chunks never
     merge; what ``fill`` returns is the share's used bytes.  The decode can FLAG a tile after its chunk was accepted: the source keeps
-    the status words (``StatusLog``) and is the ring's re-run protocol, which its route hands through."""
+    the status words (``StatusLog``) and is the ring's re-run protocol, which its route hands through.  With
+    ATLASPATCH_JPEG_RESTART_DEVICE=1 (read when the source is made, as the backends read it for ``bound`` and the stager) the decode
+    is ``ap_jpeg_entropy_decode_tiles_rst``, which also takes the tiles with restart intervals that the ``_ex`` stagers then admit."""
     flags, merges = True, False
     row_bytes = property(lambda self: self.header + self.bound)
 
     def __init__(self, lib, side: int, sampling: int, counters: dict, stage, bound: int) -> None:
+        from ..utils.env import env_flag
         super().__init__(lib, side, sampling, counters, stage)
         self.bound, self.header, self.log = int(bound), int(lib.ap_jpeg_stream_header_bytes()), StatusLog()
+        self.decode_name = "ap_jpeg_entropy_decode_tiles_rst" if env_flag("ATLASPATCH_JPEG_RESTART_DEVICE") else "ap_jpeg_entropy_decode_tiles_ex"
 
     def usable(self) -> bool:
         return super().usable() and self.bound > 0 and self.bound % 16 == 0
@@ -223,9 +229,8 @@ class StreamTiles(_TileSource):
         coef, status = buf.dev[slot][first:].data_ptr(), buf.status[slot][first:first + m]
         if m == 0:                       # a chunk whose patches cover no present tile
             return coef
-        _lib.check(self.lib.ap_jpeg_entropy_decode_tiles_ex(buf.desc_dev[slot][first:].data_ptr(), buf.arena_dev[slot][first * self.bound:].data_ptr(),
-                                                         used, m, self.side, self.sampling, coef, status.data_ptr(), 0, ptr),
-                   "ap_jpeg_entropy_decode_tiles_ex")
+        _lib.check(getattr(self.lib, self.decode_name)(buf.desc_dev[slot][first:].data_ptr(), buf.arena_dev[slot][first * self.bound:].data_ptr(),
+                                                       used, m, self.side, self.sampling, coef, status.data_ptr(), 0, ptr), self.decode_name)
         self.log.note(where[0], m, where[1], where[2], status)
         return coef
 

@@ -169,19 +169,23 @@ int ap_jpeg_decode_tiles_ex(const void* slots, int n, int side, int sampling, ui
  *   bytes 1472 .. 1479   uint8 dc_sel[3], 0, ac_sel[3], 0: each component's table selectors
  *   bytes 1480 .. 1487   uint32 ncomp, uint32 payload_bytes
  *   bytes 1488 .. 1495   uint64 payload_offset into the arena, a multiple of 16
- *   bytes 1496 .. 2047   zero
+ *   bytes 1496 .. 1503   uint32 restart_interval (MCUs per interval; 0 = a restart-free tile), uint32 restart_count (intervals)
+ *   bytes 1504 .. 1511   uint64 restart_table_offset into the arena, a multiple of 16
+ *   bytes 1512 .. 2047   zero
  * and its PAYLOAD in a packed ARENA: the entropy-coded segment from the end of the SOS header to the marker that ends it (or
  * the end of the stream), byte stuffing removed, 16-byte aligned, zero filled to the next multiple of 16; whatever follows the
- * terminating marker is ignored, as libjpeg ignores it.
+ * terminating marker is ignored, as libjpeg ignores it.  The three restart fields are zero in everything the entries without
+ * AP_JPEG_STREAM_RESTART stage (see ap_host_jpeg_streams_ex below for the restart table).
  * The staging functions parse SOI, DQT, DHT, SOF0, DRI, SOS and the APPn / COM segments they skip with code of their own (no
  * libjpeg), every segment length checked against the buffer; the colour model of a three-component stream is inferred from JFIF /
  * Adobe markers and component ids exactly as libjpeg infers it.  Admitted: the subset of ap_host_jpeg_coefficients (AP_JPEG_RGB
- * included: an RGB-coded stream when, and only when, that code is asked for) restricted to
- * baseline SOF0, one scan with every component in frame order, a side that is a multiple of the MCU size (8, or 16 along a
- * subsampled axis) and <= 976, no restart interval and no RSTn marker, Huffman tables 0 / 1 that exist and form a canonical code
- * without over-subscription.  Everything else is refused with AP_ERR_INVALID and the reason; the refusal contract is the one of
- * ap_host_jpeg_coefficients: the tiles before the first refused one are complete (*arena_used covers them), the descriptors
- * from it on are untouched.  A tile that would overflow the arena is refused too.  Host only, no device work. */
+ * included: an RGB-coded stream when, and only when, that code is asked for) restricted to baseline SOF0, one scan with every
+ * component in frame order, a side that is a multiple of the MCU size (8, or 16 along a subsampled axis) and <= 976, no restart
+ * interval and no RSTn marker (ap_host_jpeg_streams, ap_host_tiff_tile_streams and their _ex twins at flags 0; the _ex entries admit
+ * both with AP_JPEG_STREAM_RESTART), Huffman tables 0 / 1 that exist and form a canonical code without over-subscription.  Everything
+ * else is refused with AP_ERR_INVALID and the reason; the refusal contract is the one of ap_host_jpeg_coefficients: the tiles before
+ * the first refused one are complete (*arena_used covers them), the descriptors from it on are untouched.  A tile that would overflow
+ * the arena is refused too.  Host only, no device work. */
 size_t ap_jpeg_stream_header_bytes(void);
 /* bytes: the largest file size among paths, rounded up to 16: n times that is an arena no n of these tiles overflow. */
 int ap_host_jpeg_stream_bound(const char* const* paths, int n, size_t* bytes);
@@ -189,6 +193,23 @@ int ap_host_jpeg_stream_bound(const char* const* paths, int n, size_t* bytes);
  * payload will start and unstuffed in place; *arena_used: the bytes of the arena that hold payloads afterwards. */
 int ap_host_jpeg_streams(void* descs, void* arena, size_t arena_cap, size_t* arena_used, const char* const* paths, int n, int side,
                          int sampling);
+/* RESTART INTERVALS (additive: AP_ABI_VERSION stays 20).  flags 0: ap_host_jpeg_streams to the letter, refusals and reasons included;
+ * any bit but AP_JPEG_STREAM_RESTART is AP_ERR_INVALID.  With AP_JPEG_STREAM_RESTART a DRI segment is admitted, in the stream and in a
+ * TIFF level's JPEGTables; the interval in force is the one of the tile's own stream, because libjpeg resets it at every SOI
+ * (jdmarker.c: get_soi): a level whose DRI stands in its JPEGTables alone is one libjpeg cannot read either.  An interval of 0, or of
+ * at least the frame's MCU count, means no marker: the tile is staged restart free, the three restart fields zero.  Otherwise
+ * restart_interval = the DRI value, restart_count = ceil(MCUs / restart_interval), the RSTn markers are removed from the payload as
+ * well (the padding bits in front of a marker stay: the tail of their interval), and the RESTART TABLE follows in the arena at the
+ * first 16-byte boundary behind the payload's zero fill: restart_count little-endian uint32, entry k = the byte offset, relative to
+ * the payload's first byte, at which interval k starts; entry 0 is 0, the entries are strictly increasing and below payload_bytes;
+ * zero filled to a multiple of 16; *arena_used covers it.  A table of interval 1 takes 4 bytes per MCU: an arena share of the largest
+ * file plus that, each rounded up to 16, is never overflowed.  Refused, because libjpeg would warn and the host reader refuses on
+ * warnings: another number of markers than restart_count - 1, a marker whose number is not the next of RST0, RST1, ... modulo 8, a
+ * marker at the scan's start, directly behind another or directly in front of the scan's end, a DRI segment whose length is not 4.  A
+ * restart marker outside a scan stays refused. */
+#define AP_JPEG_STREAM_RESTART 1
+int ap_host_jpeg_streams_ex(void* descs, void* arena, size_t arena_cap, size_t* arena_used, const char* const* paths, int n, int side,
+                            int sampling, int flags);
 /* Device: descs (n descriptors) and arena (arena_bytes bytes), both device, 16-byte aligned -> slots: exactly the coefficient
  * slots of ap_jpeg_slot_bytes(side, sampling) pitch that ap_host_jpeg_coefficients fills (quantisers copied in, every coefficient
  * the stream does not code zero, DC values accumulated; bytes 384 .. 511 are padding and unspecified), so ap_jpeg_decode_tiles and
@@ -209,6 +230,22 @@ int ap_jpeg_entropy_decode_tiles(const void* descs, const void* arena, size_t ar
                                  int32_t* status, int subsequence_bits, ap_stream_t stream);
 int ap_jpeg_entropy_decode_tiles_ex(const void* descs, const void* arena, size_t arena_bytes, int n, int side, int sampling, void* slots,
                                     int32_t* status, int subsequence_bits, ap_stream_t stream);                     /* + AP_JPEG_RGB */
+/* The same signature, argument checks and sampling codes as ap_jpeg_entropy_decode_tiles_ex, for launches that may hold tiles with
+ * restart intervals (ATLASPATCH_JPEG_RESTART_DEVICE=1 on top of the two other switches makes the ring stage and decode them). Each
+ * tile is decoded by the path its restart_interval selects; two kernels are launched over the n tiles and a workgroup whose tile is
+ * not of its kind returns after reading the restart fields.  All three zero: slot and status byte for byte those of
+ * ap_jpeg_entropy_decode_tiles_ex (an interval of 0 beside a count or a table offset is _BAD_DESCRIPTOR).  Otherwise one workgroup of
+ * 256 lanes, lane l decoding the intervals l, l + 256, ... one after the other: every interval starts byte aligned, at block 0 of MCU
+ * k * restart_interval, with the DC predictors at zero, so there is no guessed state, no rounds and no DC prefix sum, and
+ * subsequence_bits (still checked) is not used.  The status codes PER INTERVAL: _BAD_CODE and _BAD_INDEX as above; _EXHAUSTED: an
+ * interval's bits ran out before its last block; _LEFTOVER: one or more whole bytes are left in an interval behind its last block
+ * (libjpeg counts them as discarded and warns); _BAD_DESCRIPTOR also: a restart_interval at or above the frame's MCU count (the
+ * stager stages such a tile restart free), a restart_count that is not ceil(MCUs / restart_interval), a table that does not lie
+ * inside arena_bytes, entry 0 not 0, an entry not strictly above its predecessor or not below payload_bytes.  The tile's status is
+ * the first error in interval order.  The same memory-safety contract on any input: a table entry is read only below the checked
+ * count, a payload word only below the interval's checked end. */
+int ap_jpeg_entropy_decode_tiles_rst(const void* descs, const void* arena, size_t arena_bytes, int n, int side, int sampling, void* slots,
+                                     int32_t* status, int subsequence_bits, ap_stream_t stream);
 
 /* The same for a slide OpenSlide can open (the reference's production tile source): core/wsi/openslide_wsi.py:184-205 reads
  * one region per call in the interpreter -- openslide-python's read_region (premultiplied ARGB -> RGBA in its C helper, a
@@ -276,6 +313,10 @@ int ap_host_tiff_tile_coefficients(const ap_tiff* slide, int level, const int32_
 size_t ap_host_tiff_max_tile_bytes(const ap_tiff* slide, int level);
 int ap_host_tiff_tile_streams(const ap_tiff* slide, int level, const int32_t* tile_ids, int m, void* descs, void* arena,
                               size_t arena_cap, size_t* arena_used);
+/* flags as for ap_host_jpeg_streams_ex: 0 is ap_host_tiff_tile_streams to the letter; AP_JPEG_STREAM_RESTART admits a DRI segment in
+ * the level's JPEGTables and in a tile's own stream; the tile's own is the one in force (its SOI resets the level's, as in libjpeg). */
+int ap_host_tiff_tile_streams_ex(const ap_tiff* slide, int level, const int32_t* tile_ids, int m, void* descs, void* arena,
+                                 size_t arena_cap, size_t* arena_used, int flags);
 
 /* Device: patches that do not sit on the tile grid, assembled from decoded tiles (the output of ap_jpeg_decode_tiles).
  *   tiles  uint8 [m, ts, ts, 3]      device, 16-byte aligned
