@@ -174,61 +174,8 @@ class SAM2SegmentationService(SegmentationService):
 
 
 def random_sam2_state_dict(seed: int = 0) -> dict:
-    """Seeded random SAM2.1 Hiera-T image-path parameters under the package's state-dict names."""
-    import math
+    """Seeded random SAM2.1 Hiera-T image-path parameters under the package's state-dict names (drawn from the predictor's
+    own parameter table, ``sam2_hip.param_table``)."""
+    from .sam2_hip import random_state_dict
+    return random_state_dict(seed)
 
-    import torch
-
-    from .sam2_hip import EMBED, WINDOW_SPEC, block_plan
-    g = torch.Generator().manual_seed(seed)
-    w = lambda *s, sc=0.02: torch.randn(*s, generator=g) * sc
-    sd = {}
-
-    def lin(name, o, i):
-        sd[name + ".weight"] = w(o, i, sc=1.0 / math.sqrt(i)); sd[name + ".bias"] = w(o)
-
-    def ln(name, d):
-        sd[name + ".weight"] = 1.0 + w(d, sc=0.1); sd[name + ".bias"] = w(d)
-
-    t = "image_encoder.trunk."
-    sd[t + "patch_embed.proj.weight"] = w(EMBED, 3, 7, 7, sc=0.08); sd[t + "patch_embed.proj.bias"] = w(EMBED)
-    sd[t + "pos_embed"] = w(1, EMBED, 7, 7, sc=0.2)
-    sd[t + "pos_embed_window"] = w(1, EMBED, WINDOW_SPEC[0], WINDOW_SPEC[0], sc=0.2)
-    for i, (din, dout, heads, window, qpool) in enumerate(block_plan()[0]):
-        b = f"{t}blocks.{i}."
-        ln(b + "norm1", din); lin(b + "attn.qkv", 3 * dout, din); lin(b + "attn.proj", dout, dout); ln(b + "norm2", dout)
-        lin(b + "mlp.layers.0", 4 * dout, dout); lin(b + "mlp.layers.1", dout, 4 * dout)
-        if din != dout:
-            lin(b + "proj", dout, din)
-    for n, c in enumerate((768, 384, 192, 96)):
-        sd[f"image_encoder.neck.convs.{n}.conv.weight"] = w(256, c, 1, 1, sc=1.0 / math.sqrt(c))
-        sd[f"image_encoder.neck.convs.{n}.conv.bias"] = w(256)
-    sd["no_mem_embed"] = w(1, 1, 256)
-    p = "sam_prompt_encoder."
-    sd[p + "pe_layer.positional_encoding_gaussian_matrix"] = torch.randn(2, 128, generator=g)
-    for i in range(4):
-        sd[p + f"point_embeddings.{i}.weight"] = w(1, 256, sc=0.5)
-    sd[p + "not_a_point_embed.weight"] = w(1, 256, sc=0.5); sd[p + "no_mask_embed.weight"] = w(1, 256, sc=0.5)
-    d = "sam_mask_decoder."
-
-    def attn(name, internal):
-        lin(name + ".q_proj", internal, 256); lin(name + ".k_proj", internal, 256)
-        lin(name + ".v_proj", internal, 256); lin(name + ".out_proj", 256, internal)
-
-    for l in range(2):
-        b = f"{d}transformer.layers.{l}."
-        attn(b + "self_attn", 256); attn(b + "cross_attn_token_to_image", 128); attn(b + "cross_attn_image_to_token", 128)
-        for k in range(1, 5):
-            ln(b + f"norm{k}", 256)
-        lin(b + "mlp.layers.0", 2048, 256); lin(b + "mlp.layers.1", 256, 2048)
-    attn(d + "transformer.final_attn_token_to_image", 128); ln(d + "transformer.norm_final_attn", 256)
-    sd[d + "iou_token.weight"] = w(1, 256, sc=0.5); sd[d + "mask_tokens.weight"] = w(4, 256, sc=0.5)
-    sd[d + "obj_score_token.weight"] = w(1, 256, sc=0.5)
-    sd[d + "output_upscaling.0.weight"] = w(256, 64, 2, 2, sc=1.0 / 16); sd[d + "output_upscaling.0.bias"] = w(64)
-    ln(d + "output_upscaling.1", 64)
-    sd[d + "output_upscaling.3.weight"] = w(64, 32, 2, 2, sc=1.0 / 8); sd[d + "output_upscaling.3.bias"] = w(32)
-    sd[d + "conv_s0.weight"] = w(32, 256, 1, 1, sc=1.0 / 16); sd[d + "conv_s0.bias"] = w(32)
-    sd[d + "conv_s1.weight"] = w(64, 256, 1, 1, sc=1.0 / 16); sd[d + "conv_s1.bias"] = w(64)
-    for k, (o, i) in enumerate(((256, 256), (256, 256), (32, 256))):
-        lin(d + f"output_hypernetworks_mlps.0.layers.{k}", o, i)
-    return sd

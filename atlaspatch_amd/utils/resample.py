@@ -188,7 +188,8 @@ class DeviceResampler:
         self.bx, self.kx, self.by, self.ky = to(bx), to(kx), to(by), to(ky)
         self._tmp = None
 
-    def __call__(self, tiles):
+    def __call__(self, tiles, out=None):
+        """-> uint8 [n, oh, ow, 3]: a new tensor, or `out` (contiguous, of that shape) written in place."""
         import torch
         from .. import _lib
         assert tiles.is_cuda and tiles.dtype == torch.uint8 and tiles.is_contiguous() and tuple(tiles.shape[1:3]) == self.in_hw
@@ -197,7 +198,9 @@ class DeviceResampler:
         need = n * self.in_hw[0] * ow * 3
         if self._tmp is None or self._tmp.numel() < need:
             self._tmp = torch.empty(need, dtype=torch.uint8, device=self.device)
-        out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=self.device)
+        if out is None:
+            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=self.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, oh, ow, 3)
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().ap_resample_u8(tiles.data_ptr(), n, self.in_hw[0], self.in_hw[1], out.data_ptr(), oh, ow,
                                                   self.bx.data_ptr(), self.kx.data_ptr(), self.ksx, self.by.data_ptr(),

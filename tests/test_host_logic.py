@@ -615,6 +615,61 @@ def test_sam2_checkpoint_loader_accepts_the_reference_layout_and_names_what_is_m
     torch.save({"model": broken}, p)
     with pytest.raises(KeyError, match="iou_token"):
         load_sam2_state_dict(p)
+    # every name is there but one tensor has another Hiera size's shape: refused up front, by name
+    broken = dict(sd)
+    broken["image_encoder.trunk.blocks.1.attn.qkv.weight"] = torch.zeros(3 * 224, 112)
+    torch.save({"model": broken}, p)
+    with pytest.raises(ValueError, match=r"blocks\.1\.attn\.qkv\.weight \(672, 112\) \(expected \(576, 96\)\)"):
+        load_sam2_state_dict(p)
+
+
+def test_sam2_parameter_table_is_the_one_list_of_names_and_shapes():
+    """sam2_hip.param_table(): the names the predictor reads are required_sam2_keys(), the names it draws are the random
+    weights' keys (in order, at the table's shapes), and every shape it reads is the oracle's -- the independent restatement
+    of the sam2 package's modules."""
+    from atlaspatch_amd.services.sam2_hip import param_table, required_sam2_keys
+    from atlaspatch_amd.services.segmentation import random_sam2_state_dict
+    from oracle import sam2_oracle as so
+    table = param_table()
+    names = [p.name for p in table]
+    assert len(set(names)) == len(names) == 271
+    read = [p.name for p in table if p.read]
+    assert read == required_sam2_keys() and len(read) == 269
+    assert set(names) - set(read) == {f"sam_prompt_encoder.point_embeddings.{i}.weight" for i in (0, 1)}
+    drawn = random_sam2_state_dict(0)
+    assert list(drawn) == names and all(tuple(drawn[p.name].shape) == p.shape and drawn[p.name].dtype == torch.float32 for p in table)
+    oracle = so.random_state_dict(0)
+    assert [p.name for p in table if p.read and tuple(oracle[p.name].shape) != p.shape] == []
+    keys = [p.key for p in table if p.key is not None]
+    assert len(set(keys)) == len(keys) and all(p.read for p in table if p.key is not None)
+    assert all(p.draw in ("linear", "layernorm", "plain") for p in table)
+
+
+def test_sam2_gemm_route_names_the_entry_point_of_every_recorded_gemm():
+    """Every GEMM of the recorded launch trace (tests/golden/sam2_launch_trace.json: both arithmetic modes, one and two
+    images) replayed through the pure route function: it names the entry point the record holds.  A weight has a
+    split-f16 copy in the default mode when both its dimensions are multiples of 32 (the constructor's rule); a row-wise
+    layer of the trunk runs on all images of the forward, the neck and the decoder on one."""
+    from atlaspatch_amd.services.sam2_hip import gemm_route
+    from tests import sam2_trace as st
+    fixture = st.load_fixture()
+    assert set(fixture) == set(st.MODES) and all(set(per) == {str(b) for b in st.BATCHES} for per in fixture.values())
+    seen = set()
+    for mode, per_batch in fixture.items():
+        for b, collapsed in per_batch.items():
+            records = st.expand(collapsed)
+            # the trunk's launches end where the first image's neck begins: four lateral GEMMs in front of its upsample-add
+            trunk_end = [r[0] for r in records].index("ap_upsample2x_add") - 4
+            for i, r in enumerate(records):
+                if r[0] not in st.GEMM_ENTRIES:
+                    continue
+                name, kw = st.gemm_route_inputs(r, stack=int(b) if i < trunk_end else 1)
+                split_copy = mode == "default" and kw["n"] % 32 == 0 and kw["k"] % 32 == 0 and kw["w16"]
+                got = gemm_route(split_copy=split_copy, exact_f32=mode == "exact_f32", **kw)
+                assert got == name, (mode, b, i, r, got)
+                seen.add((mode, name))
+    assert seen == {("default", n) for n in st.GEMM_ENTRIES if n != "ap_gemm"} | \
+        {("exact_f32", n) for n in ("ap_gemm", "ap_sgemm_stacked", "ap_sgemm")}
 
 
 def test_host_scale_contours_matches_reference_golden(golden_dir):

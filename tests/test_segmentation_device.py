@@ -155,6 +155,23 @@ def test_sam2_batched_forward_equals_the_single_slide_forwards_bit_for_bit():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["default", "exact_f32"])
+def test_sam2_forward_makes_the_recorded_launches(mode):
+    """One eager forward on seeded random weights, for one image and for two: every C-ABI call -- entry point, scalar
+    arguments, which pointers are set and aligned -- equals tests/golden/sam2_launch_trace.json call by call, in the
+    default arithmetic and with ATLASPATCH_SAM2_EXACT_F32=1.  The recording is what the host code's restructurings are
+    held to: a forward that launches the same kernels on the same arguments in the same order computes the same bits."""
+    from tests import sam2_trace as st
+    want, got = st.load_fixture()[mode], st.record_mode(mode)
+    assert set(got) == set(want)
+    for b in want:
+        w, g = st.expand(want[b]), st.expand(got[b])
+        first = next((i for i, (x, y) in enumerate(zip(w, g)) if x != y), None)
+        assert first is None, f"{mode}, {b} image(s): call {first} is {g[first]}, recorded {w[first]}"
+        assert len(g) == len(w), f"{mode}, {b} image(s): {len(g)} calls, recorded {len(w)}; the first one off: {max(g, w, key=len)[min(len(g), len(w))]}"
+
+
+@pytest.mark.gpu
 def test_openslide_level_read_in_parallel_strips_equals_one_read_region(tmp_path):
     """OpenSlideWSI.read_level_device: full-width strips read by libopenslide on a thread pool == extract((0, 0), level,
     dims) through openslide-python, for a level with an integer downsample (strips) -- run in a subprocess, the stub
