@@ -128,6 +128,9 @@ SIGNATURES = {
     "ap_preproc_u8hwc_to_chw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p,
                                           C.c_int, C.c_void_p]),
+    "ap_preproc_u8hwc_to_chw_any": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p,
+                                              C.c_int, C.c_void_p]),
     "ap_preproc_u8hwc_to_patchrows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
                                                 C.POINTER(C.c_float), C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

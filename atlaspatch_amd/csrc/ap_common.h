@@ -316,6 +316,8 @@ int get_norm_lut(const float mean[3], const float stdv[3], int dtype, hipStream_
                  const void** out);
 int preproc_chw(const uint8_t* src, int n, int h, int w, int top, int left, int oh, int ow,
                 const float mean[3], const float stdv[3], void* dst, int dtype, hipStream_t stream);
+int preproc_chw_any(const uint8_t* src, int n, int h, int w, int top, int left, int oh, int ow,
+                    const float mean[3], const float stdv[3], void* dst, int dtype, hipStream_t stream);
 int preproc_patchrows(const uint8_t* src, int n, int h, int w, int top, int left, int oh, int ow,
                       int ps, const float mean[3], const float stdv[3], void* dst, int ld, int dtype,
                       hipStream_t stream);

@@ -55,6 +55,13 @@ int ap_preproc_u8hwc_to_chw(const uint8_t* src, int n, int h, int w, int crop_to
                            (hipStream_t)stream);
 }
 
+int ap_preproc_u8hwc_to_chw_any(const uint8_t* src, int n, int h, int w, int crop_top, int crop_left,
+                                int oh, int ow, const float mean[3], const float stdv[3], void* dst,
+                                int dst_dtype, ap_stream_t stream) {
+    return ap::preproc_chw_any(src, n, h, w, crop_top, crop_left, oh, ow, mean, stdv, dst, dst_dtype,
+                               (hipStream_t)stream);
+}
+
 int ap_preproc_u8hwc_to_patchrows(const uint8_t* src, int n, int h, int w, int crop_top,
                                   int crop_left, int oh, int ow, int ps, const float mean[3],
                                   const float stdv[3], void* dst, int ld, int dst_dtype,

@@ -238,11 +238,63 @@ int preproc_common(int layout, const uint8_t* src, int n, int h, int w, int top,
     return dispatch_dtype("preproc", dtype, [&](auto tag) { return launch_pre<typename decltype(tag)::type>(layout, a, stream); });
 }
 
+// [n, 3, oh, ow] for an output width that is no multiple of 8 (the transform of a plugin's torch module on a tile of any size):
+// the same table look-up, one element per task.  Rows of such a width do not start on 16 bytes, so there is nothing to
+// vectorise; consecutive lanes write consecutive elements of one (channel, row), and the 3-byte-strided source bytes of a
+// band are read three times through the vector L1.  One workgroup per image and band of kAnyBand rows, as above.
+constexpr int kAnyBand = 8;
+
+template <typename T>
+__global__ __launch_bounds__(256) void preproc_chw_anyw_kernel(PreArgs a) {
+    __shared__ T lut[768];
+    const int tid = threadIdx.x;
+    const int bands = (a.oh + kAnyBand - 1) / kAnyBand;
+    const int img = blockIdx.x / bands, bnd = blockIdx.x - img * bands;
+    const int y0 = bnd * kAnyBand;
+    const int nrows = min(kAnyBand, a.oh - y0);
+    for (int i = tid; i < 768; i += 256) lut[i] = ((const T*)a.lut)[i];
+    __syncthreads();
+    const size_t srcStride = (size_t)a.w * 3;
+    const uint8_t* win = a.src + ((size_t)img * a.h + (a.top + y0)) * srcStride + (size_t)a.left * 3;
+    const int plane = nrows * a.ow;                      // <= 8 * 2^27: ow is bounded by the launcher
+    for (int t = tid; t < 3 * plane; t += 256) {
+        const int c = t / plane, rem = t - c * plane;
+        const int r = rem / a.ow, x = rem - r * a.ow;
+        ((T*)a.dst)[(((size_t)img * 3 + c) * a.oh + (y0 + r)) * (size_t)a.ow + x] = lut[c * 256 + win[r * srcStride + (size_t)x * 3 + c]];
+    }
+}
+
 }  // namespace
 
 int preproc_chw(const uint8_t* src, int n, int h, int w, int top, int left, int oh, int ow,
                 const float mean[3], const float stdv[3], void* dst, int dtype, hipStream_t stream) {
     return preproc_common(LAYOUT_CHW, src, n, h, w, top, left, oh, ow, 0, 0, mean, stdv, dst, dtype, stream);
+}
+
+int preproc_chw_any(const uint8_t* src, int n, int h, int w, int top, int left, int oh, int ow,
+                    const float mean[3], const float stdv[3], void* dst, int dtype, hipStream_t stream) {
+    if (ow > 0 && ow % 8 == 0 && ow <= 16384 / 3)       // the vectorised kernel, with its own checks
+        return preproc_common(LAYOUT_CHW, src, n, h, w, top, left, oh, ow, 0, 0, mean, stdv, dst, dtype, stream);
+    AP_REQUIRE(src && dst && mean && stdv, "preproc_chw_any: null pointer");
+    AP_REQUIRE(n >= 0 && h > 0 && w > 0 && oh > 0 && ow > 0, "preproc_chw_any: bad shape");
+    AP_REQUIRE(top >= 0 && left >= 0 && top <= h - oh && left <= w - ow,
+               "preproc_chw_any: crop window %d,%d+%dx%d outside %dx%d", top, left, oh, ow, h, w);
+    AP_REQUIRE(ow <= (1 << 24), "preproc_chw_any: output width %d too large", ow);
+    AP_REQUIRE(dtype == AP_F32 || dtype == AP_F16 || dtype == AP_BF16, "preproc_chw_any: unknown dtype %d", dtype);
+    if (n == 0) return AP_OK;
+    const int bands = (oh + kAnyBand - 1) / kAnyBand;
+    AP_REQUIRE((long long)n * bands <= 0x7FFFFFFFLL, "preproc_chw_any: n %d x %d bands exceeds the grid", n, bands);
+    PreArgs a;
+    a.src = src; a.n = n; a.h = h; a.w = w; a.top = top; a.left = left; a.oh = oh; a.ow = ow;
+    a.dst = dst; a.ps = 0; a.ld = 0; a.band = kAnyBand;
+    int rc = get_norm_lut(mean, stdv, dtype, stream, &a.lut);
+    if (rc != AP_OK) return rc;
+    return dispatch_dtype("preproc_chw_any", dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        preproc_chw_anyw_kernel<T><<<dim3((unsigned)(n * bands)), dim3(256), 0, stream>>>(a);
+        AP_HIP_CHECK(hipGetLastError());
+        return AP_OK;
+    });
 }
 
 int preproc_patchrows(const uint8_t* src, int n, int h, int w, int top, int left, int oh, int ow,

@@ -14,6 +14,9 @@
   encoders registered through ``register_custom_encoder`` (same contract as
   base.py:48-114 but without the per-batch DataLoader spawn); it exists so that
   third-party plugins keep working and is NOT what the benchmark measures.
+* ``DeviceTorchFeatureExtractor`` -- the same plugin module fed from the tile ring: the plugin's
+  transform restated as a ``DeviceTransform`` runs on the device (``ap_resample_u8`` +
+  ``ap_preproc_u8hwc_to_chw_any``) in front of the torch module.
 """
 from __future__ import annotations
 
@@ -144,45 +147,15 @@ def _as_uint8_hwc(patch) -> np.ndarray:
     return arr
 
 
-class HipViTFeatureExtractor(FeatureExtractor):
-    """ViT-family encoder running entirely in hand-written HIP kernels (gfx950).
-
-    Parameters
-    ----------
-    vit : atlaspatch_amd.encoders.vit.HipViT
-        Device-resident encoder (weights already uploaded).
-    mean, std : normalisation constants of the reference transform.
-    resize : optional ``(size, "bicubic" | "bilinear")`` -- the ``Resize(size)`` that opens the reference
-        transform (timm's ``Resize(224, bicubic)`` for uni_v1, open_clip's ``Resize(448, bicubic)`` for
-        conch_v1): shorter side -> size with the aspect kept, done on the device by ``ap_resample_u8``
-        bit-identically to Pillow (the reference's resampler); the centre crop that follows is part of
-        the preprocess kernel.  ``None`` = torchvision's ``ImageClassification(crop 224, resize 256)``
-        on 256-px tiles, which is a pure centre crop.
-    """
-
-    def __init__(self, *, name: str, vit, mean, std, max_batch: int = 1024,
-                 resize: Optional[tuple] = None, expect_size: Optional[int] = None) -> None:
-        self.name = name
-        self.vit = vit
-        self.embedding_dim = int(vit.embed_dim)
-        self.mean = tuple(float(v) for v in mean)
-        self.std = tuple(float(v) for v in std)
-        self.max_batch = int(max_batch)
-        self.resize = resize
-        self.expect_size = expect_size
-        self.device = vit.device
-        self._resamplers: dict = {}
+class PinnedTileUpload:
+    """Host patches -> a device batch through a grow-only pinned buffer: what ``extract_batch`` of every extractor that owns
+    a ``forward_device`` does in front of it (the native encoders and ``DeviceTorchFeatureExtractor``)."""
 
     def _validated(self, patches: Sequence) -> list:
         arrs = [_as_uint8_hwc(p) for p in patches]
         shape0 = arrs[0].shape
         if any(a.shape != shape0 for a in arrs):
             raise ValueError("all patches of one batch must have the same shape")
-        if self.resize is None and self.expect_size is not None and \
-                (shape0[0] != self.expect_size or shape0[1] != self.expect_size):
-            raise ValueError(
-                f"{self.name}: the device preprocess implements the reference transform for "
-                f"{self.expect_size}x{self.expect_size} tiles only (got {shape0[1]}x{shape0[0]})")
         return arrs
 
     def _prepare(self, patches: Sequence) -> np.ndarray:
@@ -217,6 +190,46 @@ class HipViTFeatureExtractor(FeatureExtractor):
                 view[i] = arrs[i]
             dev[s:e].copy_(pin[s:e], non_blocking=True)
 
+
+class HipViTFeatureExtractor(PinnedTileUpload, FeatureExtractor):
+    """ViT-family encoder running entirely in hand-written HIP kernels (gfx950).
+
+    Parameters
+    ----------
+    vit : atlaspatch_amd.encoders.vit.HipViT
+        Device-resident encoder (weights already uploaded).
+    mean, std : normalisation constants of the reference transform.
+    resize : optional ``(size, "bicubic" | "bilinear")`` -- the ``Resize(size)`` that opens the reference
+        transform (timm's ``Resize(224, bicubic)`` for uni_v1, open_clip's ``Resize(448, bicubic)`` for
+        conch_v1): shorter side -> size with the aspect kept, done on the device by ``ap_resample_u8``
+        bit-identically to Pillow (the reference's resampler); the centre crop that follows is part of
+        the preprocess kernel.  ``None`` = torchvision's ``ImageClassification(crop 224, resize 256)``
+        on 256-px tiles, which is a pure centre crop.
+    """
+
+    def __init__(self, *, name: str, vit, mean, std, max_batch: int = 1024,
+                 resize: Optional[tuple] = None, expect_size: Optional[int] = None) -> None:
+        self.name = name
+        self.vit = vit
+        self.embedding_dim = int(vit.embed_dim)
+        self.mean = tuple(float(v) for v in mean)
+        self.std = tuple(float(v) for v in std)
+        self.max_batch = int(max_batch)
+        self.resize = resize
+        self.expect_size = expect_size
+        self.device = vit.device
+        self._resamplers: dict = {}
+
+    def _validated(self, patches: Sequence) -> list:
+        arrs = super()._validated(patches)
+        shape0 = arrs[0].shape
+        if self.resize is None and self.expect_size is not None and \
+                (shape0[0] != self.expect_size or shape0[1] != self.expect_size):
+            raise ValueError(
+                f"{self.name}: the device preprocess implements the reference transform for "
+                f"{self.expect_size}x{self.expect_size} tiles only (got {shape0[1]}x{shape0[0]})")
+        return arrs
+
     def resized(self, tiles_u8: torch.Tensor) -> torch.Tensor:
         """The transform's leading ``Resize`` on a device batch uint8 [n, H, W, 3] (identity when absent)."""
         if self.resize is None:
@@ -227,10 +240,9 @@ class HipViTFeatureExtractor(FeatureExtractor):
             return tiles_u8
         rs = self._resamplers.get((h, w))
         if rs is None:
-            from ..utils.resample import DeviceResampler
+            from ..utils.resample import DeviceResampler, shorter_side_hw
             # torchvision/timm Resize(int): shorter side -> size, aspect kept
-            out_hw = (int(size * h / w), size) if w <= h else (size, int(size * w / h))
-            rs = self._resamplers[(h, w)] = DeviceResampler((h, w), out_hw, filt, self.device)
+            rs = self._resamplers[(h, w)] = DeviceResampler((h, w), shorter_side_hw((h, w), size), filt, self.device)
         return rs(tiles_u8)
 
     def forward_device(self, tiles_u8: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
@@ -325,3 +337,85 @@ class PatchFeatureExtractor(FeatureExtractor):
             self.model.cpu()
         except Exception:  # noqa: BLE001
             pass
+
+
+class DeviceTorchFeatureExtractor(PinnedTileUpload, PatchFeatureExtractor):
+    """A plugin's torch module fed from the tile ring: the module and its ``forward_fn`` are the plugin's, the transform in
+    front of them is a ``DeviceTransform`` (the plugin's PIL ``preprocess`` restated for the device: Pillow's bytes for the
+    resize, torchvision's arithmetic for ToTensor + Normalize), so the module sees the tensors the host route would give it.
+    Speaks ``forward_device(tiles_u8, out)`` like the native encoders, which is what the embedding service asks for.
+
+    ``max_batch`` is the model chunk: a memory knob for a module of unknown size, not a tuned value.  On a CPU device, for
+    patches that are not uniform uint8 RGB arrays, or when the transform refuses the tiles' shape (a crop larger than the
+    resized tile), every call behaves exactly as ``PatchFeatureExtractor`` (the PIL ``preprocess`` on the host)."""
+
+    def __init__(self, *, device_transform, max_batch: int = 256, **kw) -> None:
+        super().__init__(**kw)
+        self.device_transform = device_transform
+        self.max_batch = max(1, int(max_batch))
+        self._warned: set = set()
+
+    def _device_route(self, hw) -> bool:
+        if self.device.type != "cuda":
+            return False
+        try:
+            self.device_transform.plan(hw)
+        except ValueError as exc:
+            if hw not in self._warned:
+                self._warned.add(hw)
+                logger.warning("%s: %s; using the host preprocess for these tiles.", self.name, exc)
+            return False
+        return True
+
+    def _forward_chunks(self, tiles_u8: torch.Tensor, out: torch.Tensor, step: int) -> None:
+        n = int(tiles_u8.shape[0])
+        for s in range(0, n, step):
+            e = min(n, s + step)
+            batch = self.device_transform(tiles_u8[s:e], self.dtype)
+            feats = self._forward_fn(batch) if self._forward_fn else self.model(batch)
+            if feats.ndim > 2:
+                feats = torch.flatten(feats, start_dim=1)
+            if tuple(feats.shape) != (e - s, self.embedding_dim):
+                raise ValueError(f"{self.name}: the model returned {tuple(feats.shape)} for {e - s} tiles; "
+                                 f"[{e - s}, {self.embedding_dim}] (embedding_dim as registered) is expected")
+            out[s:e].copy_(feats)                                   # converts to float32
+
+    def forward_device(self, tiles_u8: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """One device chunk uint8 [n, H, W, 3] -> out float32 [n, D] (written), in model chunks of ``max_batch``."""
+        with torch.inference_mode():
+            if self._device_route((int(tiles_u8.shape[1]), int(tiles_u8.shape[2]))):
+                self._forward_chunks(tiles_u8, out, self.max_batch)
+            elif tiles_u8.shape[0]:
+                host = PatchFeatureExtractor.extract_batch(self, list(tiles_u8.cpu().numpy()), batch_size=self.max_batch)
+                out.copy_(torch.from_numpy(host))
+        return out
+
+    @torch.inference_mode()
+    def extract_batch(self, patches: Sequence[np.ndarray], *, batch_size: Optional[int] = None) -> np.ndarray:
+        if not patches:
+            return np.empty((0, self.embedding_dim), dtype=np.float32)
+        try:
+            arrs = self._validated(patches) if self.device.type == "cuda" else None
+        except ValueError:
+            arrs = None                                                 # PIL images of other modes, mixed shapes: the host's business
+        if arrs is None or not self._device_route(arrs[0].shape[:2]):
+            return PatchFeatureExtractor.extract_batch(self, patches, batch_size=batch_size)
+        n = len(arrs)
+        step = max(1, min(n, int(batch_size or self.max_batch)))       # the operator's batch_size is the model chunk, as in the reference
+        out = torch.empty((n, self.embedding_dim), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            for s in range(0, n, step):
+                part = arrs[s:s + step]
+                dev = torch.empty((len(part), *part[0].shape), dtype=torch.uint8, device=self.device)
+                if s:
+                    torch.cuda.current_stream(self.device).synchronize()    # the pinned buffer is reused: its copies must have left
+                self._upload(part, dev)
+                self._forward_chunks(dev, out[s:s + step], step)
+        return out.cpu().numpy()
+
+    @torch.inference_mode()
+    def extract_device(self, tiles_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Device-resident variant: tiles uint8 [n, H, W, 3] in HBM -> float32 [n, D] in HBM."""
+        if out is None:
+            out = torch.empty((tiles_u8.shape[0], self.embedding_dim), dtype=torch.float32, device=tiles_u8.device)
+        return self.forward_device(tiles_u8, out)

@@ -6,6 +6,10 @@
   loader=..., device=..., dtype=..., num_workers=0, non_blocking=False)`` whose ``loader(device,
   dtype)`` returns ``CustomEncoderComponents(model, preprocess, forward_fn=None)``.
 
+MI355X addition: a loader may also return ``device_transform=DeviceTransform(...)``, its ``preprocess`` restated for the
+device (encoders/device_transform.py).  The module then runs from the tile ring like a native encoder
+(``DeviceTorchFeatureExtractor``); without it nothing changes.
+
 MI355X addition: ``register_hip_vit_encoder`` / ``register_hip_resnet_encoder`` let a plugin hand over a ViT / ResNet
 state dict and have it run in the native HIP kernels instead of as a torch module.
 """
@@ -21,7 +25,8 @@ from typing import Callable, Optional, Protocol
 import torch
 from PIL import Image
 
-from .base import PatchFeatureExtractor
+from .base import DeviceTorchFeatureExtractor, PatchFeatureExtractor
+from .device_transform import DeviceTransform
 from .registry import PatchFeatureExtractorRegistry
 
 logger = logging.getLogger("atlaspatch_amd.encoders.custom")
@@ -36,20 +41,28 @@ class CustomEncoderComponents:
     model: torch.nn.Module
     preprocess: Callable[[Image.Image], torch.Tensor]
     forward_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None
+    device_transform: Optional[DeviceTransform] = None        # ``preprocess`` restated for the device; None = the host route
 
 
 def register_custom_encoder(*, registry: PatchFeatureExtractorRegistry, name: str, embedding_dim: int,
                             loader: CustomEncoderLoader, device: torch.device, dtype: torch.dtype,
-                            num_workers: int = 0, non_blocking: bool = False) -> None:
+                            num_workers: int = 0, non_blocking: bool = False, device_batch: int = 256) -> None:
+    """``device_batch``: tiles per model call when the loader returns a ``device_transform`` (the ring's own batch stays
+    capped at 2048 as for every encoder).  A memory knob for a model of unknown size, not a tuned value: lower it when the
+    model's activations do not fit, raise it for a small model."""
     def build() -> PatchFeatureExtractor:
         parts = loader(device, dtype)
         if not isinstance(parts, CustomEncoderComponents):
             raise TypeError(f"Custom encoder loader for '{name}' must return CustomEncoderComponents, "
                             f"got {type(parts)}.")
-        return PatchFeatureExtractor(name=name, model=parts.model, embedding_dim=embedding_dim,
-                                     preprocess=parts.preprocess, device=device, dtype=dtype,
-                                     num_workers=num_workers, non_blocking=non_blocking,
-                                     forward_fn=parts.forward_fn)
+        kw = dict(name=name, model=parts.model, embedding_dim=embedding_dim, preprocess=parts.preprocess, device=device,
+                  dtype=dtype, num_workers=num_workers, non_blocking=non_blocking, forward_fn=parts.forward_fn)
+        if parts.device_transform is not None and torch.device(device).type == "cuda":
+            if not isinstance(parts.device_transform, DeviceTransform):
+                raise TypeError(f"Custom encoder loader for '{name}': device_transform must be a DeviceTransform, "
+                                f"got {type(parts.device_transform)}.")
+            return DeviceTorchFeatureExtractor(device_transform=parts.device_transform, max_batch=device_batch, **kw)
+        return PatchFeatureExtractor(**kw)
 
     registry.register(name, build)
 
@@ -109,6 +122,6 @@ def register_feature_extractors_from_module(module_path, registry: PatchFeatureE
     hook(registry=registry, device=device, dtype=dtype, num_workers=num_workers)
 
 
-__all__ = ["CustomEncoderComponents", "CustomEncoderLoader", "CustomRegistryHook",
+__all__ = ["CustomEncoderComponents", "DeviceTransform", "CustomEncoderLoader", "CustomRegistryHook",
            "register_custom_encoder", "register_hip_vit_encoder", "register_hip_resnet_encoder",
            "register_feature_extractors_from_module"]

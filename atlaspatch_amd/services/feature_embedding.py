@@ -3,7 +3,8 @@
 Same public surface (``resolve_feature_dtype``, ``PatchFeatureEmbeddingService.embed_features /
 embed_all``), same sequencing (extractor-major, slide-minor; one model resident at a time; lock
 file per slide; skip feature sets that are already complete; failures collected, not raised).
-For extractors on the native HIP path the per-slide work runs through the pinned tile ring
+For extractors that take device batches (``forward_device``: the native HIP encoders, and a plugin's
+torch module registered with a device transform) the per-slide work runs through the pinned tile ring
 (``tile_ring.TileRing``) and the feature matrix is written in one bulk append; any other
 extractor goes through the reference's buffered ``append_features`` loop.
 """
@@ -23,7 +24,6 @@ from ..core.models import ExtractionResult
 from ..core.paths import patch_lock_path
 from ..core.wsi.iwsi import IWSI
 from ..encoders import build_default_registry
-from ..encoders.base import HipViTFeatureExtractor
 from ..encoders.custom import register_feature_extractors_from_module
 from ..encoders.registry import PatchFeatureExtractorRegistry
 from ..utils.features import get_existing_features
@@ -59,6 +59,14 @@ def _to_patch_size(tiles: torch.Tensor, ps: int) -> torch.Tensor:
         return tiles
     from ..utils.resample import INTER_LINEAR, cv2_resize_device
     return cv2_resize_device(tiles, (ps, ps), INTER_LINEAR)
+
+
+def _speaks_ring(extractor) -> bool:
+    """The ring feeds any extractor that takes device batches: ``forward_device(tiles_u8, out)`` on its ``device``, rows of
+    ``embedding_dim`` (the native encoders; a plugin's torch module with a device transform)."""
+    device = getattr(extractor, "device", None)
+    return callable(getattr(extractor, "forward_device", None)) and device is not None and \
+        torch.device(device).type == "cuda" and getattr(extractor, "embedding_dim", None) is not None
 
 
 class PatchFeatureEmbeddingService(FeatureEmbeddingService):
@@ -201,7 +209,7 @@ class PatchFeatureEmbeddingService(FeatureEmbeddingService):
                 return self._stamp(result)
             attrs = {"name": extractor.name, "embedding_dim": extractor.embedding_dim}
             writer = self._writer(result, wsi)
-            if isinstance(extractor, HipViTFeatureExtractor):
+            if _speaks_ring(extractor):
                 slot = self._result_slot() if defer is not None else None
                 with stage("embed_matrix"):
                     feats = self.embed_matrix(result, wsi, extractor, slot=slot)
@@ -312,7 +320,7 @@ class PatchFeatureEmbeddingService(FeatureEmbeddingService):
         by_bytes = max(64, self._SLOT_BYTES // max(tile_hw[0] * tile_hw[1] * 3, int(staged_bytes)))
         return max(1, min(cap, by_bytes))
 
-    def embed_matrix(self, result: ExtractionResult, wsi: IWSI, extractor: HipViTFeatureExtractor, *, slot=None) -> np.ndarray:
+    def embed_matrix(self, result: ExtractionResult, wsi: IWSI, extractor, *, slot=None) -> np.ndarray:
         """float32 [N, D] for one slide through the pinned tile ring (device pipeline).  Tiles cross the ring at
         their read size; ``cv2.resize`` to ``patch_size`` (feature_embedding.py:94-95) runs on the device."""
         from .tile_ring import TileRing

@@ -76,7 +76,39 @@ def _bilinear(x: float) -> float:
     return 1.0 - x if x < 1.0 else 0.0
 
 
-_FILTERS = {"bicubic": (_bicubic, 2.0), "bilinear": (_bilinear, 1.0)}
+def _box(x: float) -> float:
+    return 1.0 if -0.5 < x <= 0.5 else 0.0
+
+
+_F054, _F046 = float(np.float32(0.54)), float(np.float32(0.46))      # float literals in Resample.c (0.54f, 0.46f), widened
+
+
+def _hamming(x: float) -> float:
+    import math
+    if x < 0.0:
+        x = -x
+    if x == 0.0:
+        return 1.0
+    if x >= 1.0:
+        return 0.0
+    x = x * math.pi
+    return math.sin(x) / x * (_F054 + _F046 * math.cos(x))
+
+
+def _sinc(x: float) -> float:
+    import math
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x
+
+
+def _lanczos(x: float) -> float:
+    return _sinc(x) * _sinc(x / 3) if -3.0 <= x < 3.0 else 0.0       # truncated sinc
+
+
+_FILTERS = {"bicubic": (_bicubic, 2.0), "bilinear": (_bilinear, 1.0), "box": (_box, 0.5), "hamming": (_hamming, 1.0),
+            "lanczos": (_lanczos, 3.0)}
 
 
 def _bicubic_v(x: np.ndarray) -> np.ndarray:
@@ -92,7 +124,16 @@ def _bilinear_v(x: np.ndarray) -> np.ndarray:
     return np.where(x < 1.0, 1.0 - x, 0.0)
 
 
-_FILTERS_V = {"bicubic": _bicubic_v, "bilinear": _bilinear_v}
+def _box_v(x: np.ndarray) -> np.ndarray:
+    return np.where((x > -0.5) & (x <= 0.5), 1.0, 0.0)
+
+
+# sin / cos element by element through the C library, as Resample.c calls them (a vector sin may differ in the last bit, and
+# the 22-bit rounding of a coefficient can turn on it); the tables are small and cached
+_hamming_v = np.vectorize(_hamming, otypes=[np.float64])
+_lanczos_v = np.vectorize(_lanczos, otypes=[np.float64])
+
+_FILTERS_V = {"bicubic": _bicubic_v, "bilinear": _bilinear_v, "box": _box_v, "hamming": _hamming_v, "lanczos": _lanczos_v}
 _TABLE_CACHE: dict = {}
 
 
@@ -172,6 +213,16 @@ def _pillow_resample_tables_scalar(in_size: int, out_size: int, filter_name: str
     return bounds, coeffs, ksize
 
 
+def shorter_side_hw(in_hw, size: int):
+    """(h, w) after torchvision's / timm's ``Resize(size)`` with an int: shorter side -> ``size``, the other side
+    ``int(size * long / short)`` (truncated), the image untouched when its shorter side already is ``size``
+    (torchvision.transforms.functional.resize / _compute_resized_output_size)."""
+    h, w, size = int(in_hw[0]), int(in_hw[1]), int(size)
+    if min(h, w) == size:
+        return h, w
+    return (int(size * h / w), size) if w <= h else (size, int(size * w / h))
+
+
 class DeviceResampler:
     """``PIL.Image.resize((ow, oh), resample)`` for device batches of uint8 HWC tiles (bit-identical)."""
 
@@ -212,7 +263,7 @@ class DeviceResampler:
 # ----------------------------------------------------------------------------- Pillow thumbnail (reduce + resize) on the device
 import threading
 
-_FILTER_SUPPORT = {"bicubic": 2.0, "bilinear": 1.0}
+_FILTER_SUPPORT = {name: support for name, (_, support) in _FILTERS.items()}
 _RESAMPLER_CACHE: dict = {}          # (in shape, out size, filter, box, device) -> DeviceResampler (its scratch is per instance:
 _RESAMPLER_LOCK = threading.Lock()   #  calls are serialised by the lock; they only enqueue)
 

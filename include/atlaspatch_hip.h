@@ -82,6 +82,14 @@ int ap_preproc_u8hwc_to_chw(const uint8_t* src, int n, int h, int w,
                             const float mean[3], const float stdv[3],
                             void* dst /* [n,3,oh,ow] */, int dst_dtype, ap_stream_t stream);
 
+/* The same call for any output width (additive to ABI v20): a width that is a multiple of 8 runs the kernel above under its
+ * own checks; any other width (the transform of a plugin's torch module on a tile of any size, encoders/device_transform.py)
+ * runs an element-per-lane kernel with the same table, so the same bits.  ow <= 2^24; n * ceil(oh / 8) <= 2^31 - 1. */
+int ap_preproc_u8hwc_to_chw_any(const uint8_t* src, int n, int h, int w,
+                                int crop_top, int crop_left, int oh, int ow,
+                                const float mean[3], const float stdv[3],
+                                void* dst /* [n,3,oh,ow] */, int dst_dtype, ap_stream_t stream);
+
 /* Same arithmetic, output laid out for the patch-embed GEMM: dst[(i*gh+py)*gw+px][c*ps*ps+ky*ps+kx]
  * with gh = oh/ps, gw = ow/ps, row length ld (>= 3*ps*ps, zero padded). */
 int ap_preproc_u8hwc_to_patchrows(const uint8_t* src, int n, int h, int w,
